@@ -5,7 +5,10 @@ One "step" = one full training step of the reference loop (/root/reference/train
 synthetic batch already resident in HBM: forward (CLC N=64, lambda=0.0067, n_refs=1) + RD loss + backward +
 clip_grad_norm_(1.0) + nan_to_num_ + AdamW + aux-loss step, fp32, through the HIP kernels of libclc_hip.so.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+K timed steps after W warm-up steps; `ms_per_step` is the wall time of the K timed steps / K.  --dump-outputs writes what the last
+timed step returned, and the parameters it left, as DIR/<name>.npy (dump_outputs(); inputs and weights are seeded, so two builds
+run with the same arguments can be compared file for file).
 For N > 1 the driver launches it under torch.distributed.run (one rank per GPU, RCCL): every rank draws its
 own synthetic shard (weak scaling), gradients are averaged with all-reduce over the flat gradient arena.
 Rank 0 prints ONE JSON line (contract in the task description) with the extra objects
@@ -53,6 +56,40 @@ def synthetic_batch(batch, size, seed, device):
     g = torch.Generator().manual_seed(seed)
     x = torch.randint(0, 256, (batch, 3, size, size), generator=g, dtype=torch.uint8).float() / 255.0
     return x.to(device)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_PARAM_SAMPLE = 8 << 20    # parameter elements kept when all of them do not fit the budget (32 MiB of float32)
+
+
+def dump_outputs(out_dir, out, model):
+    """--dump-outputs DIR: what the timed path handed its caller in its LAST timed step, so two builds can be compared output for output.
+      <key>.npy     the step's returned device scalars (loss, bpp_loss, mse_loss / ms_ssim_loss, aux_loss), float64, shape ()
+      params.npy    the model's parameters after that step's optimizer updates, named_parameters() order, flattened, float32: all of
+                    them when they fit the budget, else the elements at a fixed seeded sample of positions (one per equal slice, ascending; seed 0)
+    Returns {name: what} for the JSON line."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.asarray(float(v.item()), dtype=np.float64))
+        files[k] = "float64 scalar returned by the step"
+    flat = torch.cat([p.detach().reshape(-1) for _, p in model.named_parameters()]).float()
+    n = flat.numel()
+    if n * 4 + 4096 <= DUMP_BUDGET_BYTES:
+        sample, what = flat, f"all {n} parameter elements after the step, float32"
+    else:
+        # stratified: one seeded position inside each of k equal slices of the flattened parameters (no repeats, the whole model covered)
+        k = DUMP_PARAM_SAMPLE
+        lo = torch.arange(k + 1, dtype=torch.int64) * n // k
+        u = torch.rand(k, generator=torch.Generator().manual_seed(0), dtype=torch.float64)
+        idx = lo[:-1] + (u * (lo[1:] - lo[:-1]).double()).long()
+        sample, what = flat[idx.to(flat.device)], f"{DUMP_PARAM_SAMPLE} seeded sample positions of the {n} parameter elements after the step, float32"
+    np.save(os.path.join(out_dir, "params.npy"), sample.cpu().numpy().astype(np.float32))
+    files["params"] = what
+    return files
 
 
 def _host_threads():
@@ -773,7 +810,11 @@ def main():
     ap.add_argument("--no-reference-loop", action="store_true", help="skip the leg that times the reference's literal (eager) training loop body")
     ap.add_argument("--launch-selftest", action="store_true", help="ranks only rendezvous (gloo, CPU), all-reduce a counter and exit: checks the "
                     "self-launcher / torchrun wiring of --gpus N on a box without N GPUs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned and the "
+                    "parameters it left (a seeded sample when large) as DIR/<name>.npy, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the number of timed steps)")
 
     # Launched bare with --gpus N > 1 (no torchrun environment): become the launcher, BEFORE anything imports torch or touches the GPU.
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -869,6 +910,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     loss = float(out["loss"].item())
+    # (before anything below runs another step: the roofline leg's eager step and exposed_comm_ms() update the parameters again)
+    dumped = dump_outputs(args.dump_outputs, out, model) if (args.dump_outputs and rank == 0) else None
     exposed_comm = engine.exposed_comm_ms(x, refs) if (use_dist and not args.no_graph) else None
 
     result = {
@@ -898,6 +941,8 @@ def main():
                                  "buckets_per_step": len(engine.sync.buckets) + len(engine.aux_sync.buckets), "dist_backend": engine.sync.backend,
                                  "graphs_per_step": (len(engine.graph) if isinstance(engine.graph, tuple) else 1),
                                  "forced_one_rank_group": bool(force_coll and world == 1)})
+    if dumped is not None:
+        result["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "files": dumped}
     if trace is not None:
         result["config"]["loss_trace"] = [float(t.item()) for t in trace]
     if not args.no_roofline:  # every rank runs it (the eager step contains the gradient all-reduce); rank 0 reports

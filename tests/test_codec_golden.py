@@ -2,8 +2,9 @@
 
 tests/golden/codec_{clc_r1,clc_r3,tcm}.npz were produced by tools/make_golden.py running
 /root/reference/models/CLC_run.py:629-716, 738-814 (and tcm.py's twins) through tools/ref_shim.py on seeded inputs: the y / z
-stream bytes, `shape`, the tensors the coder saw (y, z, means, scales) and a digest of the decoded x_hat.  Checked here:
-  * CPU: the oracle model's compress() reproduces both streams byte for byte and its decompress() the x_hat digest;
+stream bytes, `shape`, the tensors the coder saw (y, z, means, scales) and the decoded x_hat (its checksum, mean and a 16x16 patch;
+tests/golden/codec_x_hat.npz: a stride-4 pixel grid of it).  Checked here:
+  * CPU: the oracle model's compress() reproduces both streams byte for byte and its decompress() the decoded x_hat;
          from the stored tensors, the oracle's quantise / build_indexes + all three coders (pure Python, plain C, the product's
          C++ coder through the C ABI — host code, no GPU) reproduce the y stream; the product coder decodes it back.
   * GPU: the HIP quantise/build_indexes kernel on the stored tensors + the product coder, in the order the product's
@@ -11,7 +12,6 @@ stream bytes, `shape`, the tensors the coder saw (y, z, means, scales) and a dig
          stream; end to end the HIP compress() emits the same container layout with sizes within 1 % (rounding flips only).
 So symbol order, slice concatenation and the strings layout come from reference code, not from a reading of it.
 """
-import hashlib
 import os
 
 import numpy as np
@@ -48,7 +48,14 @@ def test_oracle_compress_reproduces_reference_streams(name, R):
         enc = m.compress(x, refs) if R else m.compress(x)
         assert enc["strings"][0][0] == ys and enc["strings"][1][0] == zs and list(enc["shape"]) == g["shape"].tolist()
         dec = m.decompress([[ys], [zs]], torch.Size(g["shape"].tolist()), refs) if R else m.decompress([[ys], [zs]], torch.Size(g["shape"].tolist()))
-    assert hashlib.sha256(dec["x_hat"].numpy().tobytes()).hexdigest() == str(g["x_hat_sha256"])
+    # the decoder starts from the reference's exact symbols, so no rounding can flip: the reference decoder's x_hat (a stride-4 pixel grid
+    # over the whole image, the 16x16 patch, the mean) within CPU summation-order noise, which moves with the size of the torch thread pool
+    # (<= 3e-6 measured; the stored x_hat_sha256 holds only under the generating machine's pool)
+    xh = dec["x_hat"].numpy()
+    grid = np.load(os.path.join(GOLD, "codec_x_hat.npz"))[f"{name}_x_hat_grid4"]
+    np.testing.assert_allclose(xh[0, :, ::4, ::4], grid, rtol=0, atol=2e-5, err_msg="decoded x_hat grid vs the reference decoder's")
+    np.testing.assert_allclose(xh[0, :, 96:112, 96:112], g["x_hat_patch"], rtol=0, atol=2e-5, err_msg="decoded x_hat patch vs the reference decoder's")
+    assert abs(float(dec["x_hat"].double().mean()) - float(g["x_hat_mean"])) <= 2e-5
     assert abs(8.0 * (len(ys) + len(zs)) / 65536 - float(g["bpp"])) == 0.0
 
 

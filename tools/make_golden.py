@@ -5,6 +5,8 @@ Runs in the BUILD CONTAINER (needs /root/reference); the fixtures it writes are 
   graph_*.npz   outputs of the reference's OWN model classes (imported through tools/ref_shim.py, i.e.
                 genuine CLC/TCM/WMSA/Block/ConvTransBlock/SWAtten code over the oracle's restated leaves)
                 on recipe weights (oracle/recipe.py) and seeded inputs  -> pins the oracle's graph wiring
+  classes_clc_r1.npz  state_dict keys and sampled outputs of the reference's CLC class on one forward (the oracle reproduces
+                the class bit for bit where they are generated)
   blocks.npz    outputs of the reference's WMSA / Block / SwinBlock / ConvTransBlock classes -> pins window
                 attention, shift mask, relative-position indexing, LN/MLP exactly
   rans_kat.json known-answer bitstreams from the pure-Python coder (oracle/rans_py.py) incl. bypass escapes,
@@ -174,6 +176,34 @@ def dormant_goldens(ref):
     print("dormant:", {k: v.shape for k, v in out.items()})
 
 
+def classes_goldens(ref):
+    """One eval forward of the reference's OWN CLC class (N=64, one reference frame) on recipe-5 weights and seeded images 7 / 8 ->
+    tests/golden/classes_clc_r1.npz: its state_dict keys in order; x_hat on a stride-4 grid of pixels (all channels); the y likelihoods,
+    means and scales on every 8th latent channel (8 of each 64-channel slice, all positions); the float64 mean of each whole tensor.
+    The oracle must reproduce the class bit for bit HERE (same machine, same thread pool), else no fixture is written."""
+    from oracle import graph
+
+    torch.manual_seed(0)
+    rm = ref.CLC(N=64, num_ref_frames=1).eval()
+    om = graph.CLC(N=64, num_ref_frames=1).eval()
+    apply_weight_recipe(rm, 5)
+    apply_weight_recipe(om, 5)
+    x, r = synthetic_image(1, 256, 256, 7, smooth=True), [synthetic_image(1, 256, 256, 8, smooth=True)]
+    with torch.no_grad():
+        a, b = rm(x, r), om(x, r)
+    pick = lambda o: {"x_hat": o["x_hat"], "lik_y": o["likelihoods"]["y"], "means": o["para"]["means"], "scales": o["para"]["scales"]}
+    pa, pb = pick(a), pick(b)
+    assert list(rm.state_dict().keys()) == list(om.state_dict().keys()), "oracle state_dict keys differ from the reference class's"
+    assert all(torch.equal(pa[k], pb[k]) for k in pa), "oracle is not bit-identical to the reference class"
+    out = {"state_keys": np.array(list(rm.state_dict().keys())), "x_hat_grid4": pa["x_hat"][0, :, ::4, ::4].numpy()}
+    for k in ("lik_y", "means", "scales"):
+        out[f"{k}_ch8"] = pa[k][0, ::8].numpy()
+    for k, v in pa.items():
+        out[f"{k}_mean"] = np.float64(v.double().mean().item())
+    np.savez_compressed(os.path.join(OUT, "classes_clc_r1.npz"), **out)
+    print("classes:", {k: v.shape for k, v in out.items()}, os.path.getsize(os.path.join(OUT, "classes_clc_r1.npz")) // 1024, "KB")
+
+
 def rans_goldens():
     gc = leaves.GaussianConditional(None)
     gc.update_scale_table(leaves.get_scale_table())
@@ -271,7 +301,10 @@ def codec_goldens(ref):
     """Streams of the reference's OWN compress() / decompress() (models/CLC_run.py:629-716, 738-814; models/tcm.py) run through
     the shim on the seeded 256x256 inputs -> tests/golden/codec_<name>.npz: y / z stream bytes, shape, the tensors the coder
     saw (y, z, means, scales — so a coder can be checked on IDENTICAL inputs, independent of float summation order in the
-    transforms) and a checksum of the decoded x_hat.  Pins symbol order, slice concatenation and the `strings` layout."""
+    transforms) and a checksum of the decoded x_hat.  Pins symbol order, slice concatenation and the `strings` layout.
+    tests/golden/codec_x_hat.npz: the decoded x_hat of every case on a stride-4 grid of pixels (all channels): the checksum holds only
+    under the generating machine's CPU thread pool, the grid (with x_hat_mean) anywhere within summation-order noise."""
+    grid = {}
     for name, R in (("clc_r1", 1), ("clc_r3", 3), ("tcm", 0)):
         torch.manual_seed(0)
         m = (ref.CLC(N=64, num_ref_frames=R) if R else ref.TCM(N=64)).eval()
@@ -296,7 +329,10 @@ def codec_goldens(ref):
             "bpp": np.float64(8.0 * (len(enc["strings"][0][0]) + len(enc["strings"][1][0])) / (256 * 256)),
         }
         np.savez_compressed(os.path.join(OUT, f"codec_{name}.npz"), **out)
+        grid[f"{name}_x_hat_grid4"] = xh[0, :, ::4, ::4].numpy()
         print("codec", name, "y bytes", len(enc["strings"][0][0]), "z bytes", len(enc["strings"][1][0]), "bpp", float(out["bpp"]))
+    np.savez_compressed(os.path.join(OUT, "codec_x_hat.npz"), **grid)
+    print("codec_x_hat:", os.path.getsize(os.path.join(OUT, "codec_x_hat.npz")) // 1024, "KB")
 
 
 def pins_goldens(ref):
@@ -392,7 +428,11 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "block_large":
         block_large_goldens(ref)
         return
+    if len(sys.argv) > 1 and sys.argv[1] == "classes":
+        classes_goldens(ref)
+        return
     graph_goldens(ref)
+    classes_goldens(ref)
     codec_goldens(ref)
     block_goldens(ref)
     block_large_goldens(ref)
