@@ -23,3 +23,12 @@ def get_precision() -> str:
     old = L.clc_set_tuning(14, 0)
     L.clc_set_tuning(14, old)
     return "bf16" if old else "f32"
+
+
+def graphed_training(model, enabled: bool = True):
+    """Plain PyTorch training loops over CLC / TCM: a training forward replays a captured hipGraph and its outputs hang off ONE autograd
+    node whose backward replays the captured backward (clc_amd.graphed).  Also switched on for every model by CLC_GRAPH_TRAIN=1.
+    Returns the model."""
+    from .graphed import graphed_training as _g
+
+    return _g(model, enabled)

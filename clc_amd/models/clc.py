@@ -24,7 +24,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import ans, ops
+from .. import ans, graphed, ops
 from ..entropy_models import EntropyBottleneck, GaussianConditional
 from ..layers import (GELU, ConvTransBlock, Conv2d, ResidualBlockUpsample, ResidualBlockWithStride, SWAtten, conv1x1,
                       conv3x3, subpel_conv3x3)
@@ -239,6 +239,14 @@ class _SliceCodec(CompressionModel):
         return x.float().contiguous(memory_format=CL)
 
     def forward(self, x, ref_frames=None):
+        # clc_amd.graphed_training / CLC_GRAPH_TRAIN=1: a training forward replays a captured hipGraph behind ONE autograd node
+        if graphed.GRAPH_TRAIN or self.__dict__.get("_clc_graph_train"):
+            out = graphed.forward(self, x, ref_frames)
+            if out is not None:
+                return out
+        return self._forward_eager(x, ref_frames)
+
+    def _forward_eager(self, x, ref_frames=None):
         x = self._prep(x)
         prof = ops.PROFILE is not None   # bench.py's roofline leg: launches are tagged with the sub-network they belong to
         if prof:
@@ -337,6 +345,8 @@ class _SliceCodec(CompressionModel):
         d.pop("_codec_eng", None)
         d.pop("_codec_eng_stamp", None)
         d.pop("_codec_probe", None)
+        d.pop("_clc_graphed", None)   # (clc_amd.graphed: captured plans of THIS instance's storage, and whether they were released)
+        d.pop("_clc_graph_released", None)
         return d
 
     def _codec_engine(self, x_like):

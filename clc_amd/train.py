@@ -406,6 +406,9 @@ class TrainEngine:
             raise ValueError("precision must be None, 'f32' or 'bf16'")
         self.precision = precision
         self.model, self.criterion = model, (criterion or RateDistortionLoss(lmbda, loss_type))
+        from .graphed import claim
+
+        claim(model, self)   # (the model's forwards stay eager under clc_amd.graphed_training: this engine captures the step itself)
         self.lean_outputs = criterion is None
         self._make_opt = optimizer_factory or (lambda params, lr, max_norm: FusedAdamW(params, lr=lr, max_norm=max_norm))
         self.lr, self.aux_lr, self.clip = lr, aux_lr, clip_max_norm
