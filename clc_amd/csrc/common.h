@@ -12,8 +12,9 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 void clc_set_error(const char* fmt, ...);
 
 // Process-wide tuning switches (clc_set_tuning): A/B knobs that select between kernel variants computing the SAME bits.
-enum { CLC_TUNE_DMA_LOOP = 0 /* 1: conv_igemm_dma_kernel, 2: conv_igemm_dma2_kernel (re-timed K loop) */, CLC_TUNE_WGRAD_STREAMK = 1,
-       CLC_TUNE_DMA_PLACE = 2 /* dma2 kernel: 1 = DMA pieces at the top of the K iteration, 0 = between the MFMA groups */, CLC_TUNE_SK_HALF = 3 /* stream-K grids of one workgroup per CU */,
+// Keys 0, 2, 3, 12 and 19 are RETIRED: their numbers stay reserved, and clc_set_tuning accepts only their last defaults (rans_host.cpp).
+enum { /* 0: retired (LDS-DMA K loop; always conv_igemm_dma2_kernel) */ CLC_TUNE_WGRAD_STREAMK = 1,
+       /* 2: retired (DMA piece placement), 3: retired (stream-K grids of one workgroup per CU) */
        CLC_TUNE_SPLITK_PIX = 4 /* per-image map size up to which the split-K conv family is used (>= 256) */, CLC_TUNE_SPLITK_MAXC = 5 /* ... for at most this many output channels */,
        CLC_TUNE_SPLITK_PF = 6 /* K-tiles in flight per wave of the 8-wave split-K conv kernel: 3 (one workgroup per CU) or 1 (two) */,
        CLC_TUNE_1X1_TILE = 7 /* large-map 1x1 convolutions with at most this many K-tiles use the 128x64 tile (0: off) */,
@@ -21,14 +22,14 @@ enum { CLC_TUNE_DMA_LOOP = 0 /* 1: conv_igemm_dma_kernel, 2: conv_igemm_dma2_ker
        CLC_TUNE_WGRAD_DMA = 9 /* filter-gradient tile kernels: LDS-DMA staging for problems without operand arithmetic */,
        CLC_TUNE_REG_EPI = 10 /* conv_igemm_dma2_kernel: per-wave register epilogue where the launch qualifies */,
        CLC_TUNE_DGRAD_SPLITK = 11 /* data gradients on the 64x64 tile whose grid under-fills the chip: K split over 2-4 workgroups + finish launch */,
-       CLC_TUNE_ABLATE = 12 /* diagnostic: conv_igemm_dma2_kernel without its MFMAs (1) / result stores (2) / operand DMA (4) — wrong results, timing only */,
+       /* 12: retired (timing ablations) */
        CLC_TUNE_P1X1 = 13 /* large-map 1x1 layers on the persistent pipelined kernel (conv_igemm_p1x1_kernel) */,
        CLC_TUNE_BF16 = 14 /* opt-in reduced-precision mode: bf16-in / f32-accumulate MFMA in the 3x3 convolutions, data- and filter-gradient kernels of maps larger than 16x16 */,
        CLC_TUNE_TILE256 = 15 /* 64-channel 3x3 layers on >= 131072 rows: 256 x 64 tiles (64 x 32 per wave) */,
        CLC_TUNE_ATTN_4B = 16 /* window attention: the N = head_dim products on 4-block 16x16x1 MFMAs; bit mask: 1 = head_dim 16, 2 = head_dim-8 backward, 4 = head_dim-8 forward (off: see winattn.hip) */,
        CLC_TUNE_HEAVY128 = 17 /* long-K 3x3 layers on <= 16x16 maps (the slice-parameter nets): 128x128 LDS tiles with the K range split to fill the chip */,
        CLC_TUNE_ATTN_SPLIT = 18 /* attention backward on small grids (<= 1024 workgroups): two workgroups per window group, one tile each */,
-       CLC_TUNE_MLP_PK = 19 /* fused Swin MLP forward: GELU on the packed-f32 VALU instructions (same bits either way) */,
+       /* 19: retired (packed-f32 GELU in the fused Swin MLP forward: always on) */
        CLC_TUNE_N16 = 20 /* <= 16 output channels on large maps (the 12-channel tail of g_s): 16-column MFMAs (v_mfma_f32_16x16x4_f32); ANOTHER summation order */,
        CLC_TUNE_LIN = 21 /* 128 -> 128 / 64 -> 64 1x1 layers on >= 32 768 rows: the wave-private persistent kernel with whole-line stores (fused_mlp.hip: lin_kernel; same bits) */,
        CLC_TUNE_HALO = 22 /* 3x3 / stride-1 layers with 128 input channels whose caller supplies the packed filter (clc_conv_desc.w_packed): the halo-resident barrier-free kernel (conv_halo.hip; same bits); bit mask: 1 = 128-input-channel layers, 2 = 64-input-channel layers */,

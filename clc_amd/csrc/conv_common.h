@@ -36,12 +36,10 @@ struct ConvParams {
   const float* res_gate; int ldg, rg_act, rg_pre;   // residual term *= act'(res_gate)
   const float* out_gate; int ldog, og_act, og_pre;   // whole result *= act'(out_gate)
   int xcd_map;                 // conv_igemm_dma2_kernel: workgroups that share a pixel tile run back to back on ONE XCD (see the kernel)
-  int dma_place;               // conv_igemm_dma2_kernel: 1 = next tile's DMA pieces at the top of the iteration, 0 = between the MFMA groups
   int ksplit; float* partial;   // conv_igemm_dma2_kernel: K range split over `ksplit` workgroups per tile (blockIdx.z = class * ksplit + split), raw partial tiles to `partial`
   int reg_epi;                 // conv_igemm_dma2_kernel: per-wave register epilogue (epilogue_regs) instead of the C tile through LDS
   int batch_variant_ok;        // clc_conv_desc.batch_variant_ok
   int bf16;                    // reduced-precision mode for THIS launch: set by clc_conv2d for the LDS-tiled family on maps larger than 16x16 only
-  int ablate;                  // CLC_TUNE_ABLATE (diagnostic builds of the timing only, results are WRONG): 1 = no MFMAs, 2 = no result stores, 4 = no operand DMA
 };
 
 __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t rsrc, unsigned byte_off) {

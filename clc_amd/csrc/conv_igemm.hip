@@ -185,145 +185,8 @@ void conv_igemm_kernel(const ConvParams p) {
 // that belongs in its slot (the global source address is per lane) and the fragment reads apply the same XOR — the 16
 // rows of each ds_read_b128 lane group then fall in 16 distinct 16-B bank groups.  Halo pixels / rows past M / channels
 // past Cin go through the SRD's range check and deposit zeros.  K order and MFMA sequence are those of
-// conv_igemm_kernel, so the results are the same bits.  No input prologue (square / fused activation derivative).
-template <int BM, int BN, int WM, int WN, bool TR>
-__global__ __launch_bounds__(64 * WM * WN, (64 * WM * WN) >= 512 ? 4 : ((64 * WM * WN) >= 256 ? 2 : 4))
-void conv_igemm_dma_kernel(const ConvParams p) {
-  constexpr int NT = 64 * WM * WN;
-  constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-  constexpr int A_P = BM * 8 / NT, B_P = BN * 8 / NT;
-  static_assert(TM >= 1 && TN >= 1 && A_P * NT == BM * 8 && B_P * NT == BN * 8, "tile");
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* As = smem;                    // [2][BM][BK], slot-swizzled
-  float* Bs = smem + 2 * BM * BK;      // [2][BN][BK]
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave / WN, wn = wave % WN;
-  const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-  const int cls = blockIdx.z, ph = cls >> 1, pw = cls & 1;
-  const bool half = p.transposed && p.stride == 2;
-  const int DH = half ? p.OH / 2 : p.OH, DW = half ? p.OW / 2 : p.OW;
-  const TapGrid tg = make_taps(p, ph, pw);
-
-  const int fset = p.group_rows ? min(m0 / p.group_rows, 3) : 0;   // block-uniform: tiles never straddle two filter sets
-  const float* wsel = fset == 0 ? p.w : (fset == 1 ? p.w2 : (fset == 2 ? p.w3 : p.w4));
-  const float* bsel = fset == 0 ? p.bias : (fset == 1 ? p.bias2 : (fset == 2 ? p.bias3 : p.bias4));
-  const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wsel), 0, p.w_bytes, 0x00020000);
-
-  RowState rows[A_P];
-  int a_c4[A_P], b_c4[B_P];          // channel offset (floats) of the chunk this lane fetches for its slot
-  unsigned b_row_off[B_P];
-  bool b_ok[B_P];
-#pragma unroll
-  for (int i = 0; i < A_P; ++i) {
-    const int r = (tid + i * NT) >> 3;
-    rows[i] = make_row<TR>(p, m0 + r, DH, DW, ph, pw);
-    a_c4[i] = ((tid & 7) ^ ((r >> 1) & 7)) * 4;
-  }
-#pragma unroll
-  for (int i = 0; i < B_P; ++i) {
-    const int r = (tid + i * NT) >> 3;
-    const int co = n0 + r;
-    b_ok[i] = co < p.Cout;
-    b_row_off[i] = (unsigned)co * (unsigned)p.ldw;
-    b_c4[i] = ((tid & 7) ^ ((r >> 1) & 7)) * 4;
-  }
-  const int wave_row = wave * 8;     // first tile row of this wave's DMA pieces (8 rows per wave-instruction)
-
-  auto dma_tile = [&](int buf, int kh, int kw, int kc) {
-#pragma unroll
-    for (int i = 0; i < A_P; ++i) {
-      const int c = kc * BK + a_c4[i];
-      const unsigned pix = a_pixel<TR>(p, rows[i], kh, kw);
-      float* dst = As + (buf * BM + wave_row + i * (NT / 8)) * BK;
-      dma16(xr, dst, pix_off(pix, p.ldx, c, c < p.Cin));
-    }
-    const unsigned tap_off = (unsigned)((kh * p.ks + kw) * p.Cin + kc * BK);
-#pragma unroll
-    for (int i = 0; i < B_P; ++i) {
-      const bool ok = b_ok[i] && (kc * BK + b_c4[i] < p.Cin);
-      float* dst = Bs + (buf * BN + wave_row + i * (NT / 8)) * BK;
-      dma16(wr, dst, ok ? (b_row_off[i] + tap_off + (unsigned)b_c4[i]) * 4u : kOOB);
-    }
-  };
-
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const int total = tg.nkh * tg.nkw * p.kc_tiles;
-  int tj = 0, ti = 0, kc = 0;
-  auto advance = [&]() {
-    if (++kc == p.kc_tiles) { kc = 0; if (++ti == tg.nkw) { ti = 0; ++tj; } }
-  };
-  dma_tile(0, tg.kh0, tg.kw0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  // fragment (row lr of a 32-row group, chunk 2*t8 + h) sits in slot (2*t8 + h) ^ ((lr >> 1) & 7)
-  const int lr = lane & 31, hh = lane >> 5, sw = (lr >> 1) & 7;
-  int fo[4];
-#pragma unroll
-  for (int t8 = 0; t8 < 4; ++t8) fo[t8] = ((2 * t8 + hh) ^ sw) * 4;
-  for (int it = 0; it < total; ++it) {
-    const int buf = it & 1;
-    advance();
-    if (it + 1 < total) dma_tile(buf ^ 1, tg.kh0 + tg.step * tj, tg.kw0 + tg.step * ti, kc);   // block-uniform branch
-    const float* Ab = As + (buf * BM + wm * (BM / WM) + lr) * BK;
-    const float* Bb = Bs + (buf * BN + wn * (BN / WN) + lr) * BK;
-#pragma unroll
-    for (int t8 = 0; t8 < 4; ++t8) {
-      f32x4 af[TM], bf[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const f32x4*>(Ab + i * 32 * BK + fo[t8]);
-#pragma unroll
-      for (int j = 0; j < TN; ++j) bf[j] = *reinterpret_cast<const f32x4*>(Bb + j * 32 * BK + fo[t8]);
-#pragma unroll
-      for (int ss = 0; ss < 4; ++ss)
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][ss], bf[j][ss], acc[i][j], 0, 0, 0);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this iteration's DMA pieces have landed
-    __syncthreads();
-  }
-
-  constexpr int LDC = BN + 4;
-  float* Cs = smem;   // [BM][LDC]
-  {
-    const int col = lane & 31, rhalf = 4 * (lane >> 5);
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          Cs[(wm * (BM / WM) + i * 32 + (r & 3) + 8 * (r >> 2) + rhalf) * LDC + wn * (BN / WN) + j * 32 + col] = acc[i][j][r];
-  }
-  __syncthreads();
-  if (p.vec_epi) {   // block-uniform
-    for (int e = tid; e < BM * BN / 4; e += NT) {
-      const int row = e / (BN / 4), cc = (e - row * (BN / 4)) * 4;
-      const int m = m0 + row, co = n0 + cc;
-      if (m < p.M && co < p.Cout) epilogue_store4(p, bsel, *reinterpret_cast<const f32x4*>(Cs + row * LDC + cc), m, co, DH, DW, ph, pw);
-    }
-    return;
-  }
-  for (int e = tid; e < BM * BN; e += NT) {
-    const int row = e / BN, cc = e - row * BN;
-    const int m = m0 + row, co = n0 + cc;
-    if (m < p.M && co < p.Cout) epilogue_store(p, Cs[row * LDC + cc], bsel ? bsel[co] : 0.f, m, co, DH, DW, ph, pw);
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// conv_igemm_dma_kernel with the K loop re-timed (same tiles, same K order, same MFMA sequence -> same bits):
+// conv_igemm_kernel, so the results are the same bits.  No input prologue except the square of OP = 1.
+// Its K loop is re-timed against the first LDS-DMA kernel (conv_igemm_dma_kernel, since removed):
 //   * the gather address of a row is (origin + tap delta): origin byte offset and a 9-bit tap-validity mask are computed
 //     once per row, the tap delta is a scalar -> ~4 VALU instructions per DMA piece instead of ~12 with two v_mul_lo_u32;
 //   * the next tile's DMA pieces are issued BETWEEN the MFMA groups of the current tile (their address VALU executes in
@@ -745,7 +608,7 @@ __global__ __launch_bounds__(512, 4)
 void conv_igemm_p1x1_kernel(const ConvParams p, int tiles_m, int tiles_n) {
   constexpr int BM = 128, BN = 64, NT = 512, NS = 3, SLOT = (BM + BN) * BK;
   constexpr int P = 3;   // DMA pieces per wave and K-step: 2 of the A tile (16 rows), 1 of the B tile (8 rows)
-  extern __shared__ __attribute__((aligned(16))) float smem[];   // [NS][BM + BN][BK], slot-swizzled (see conv_igemm_dma_kernel)
+  extern __shared__ __attribute__((aligned(16))) float smem[];   // [NS][BM + BN][BK], slot-swizzled (see conv_igemm_dma2_kernel)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int G = gridDim.x;
@@ -1059,19 +922,6 @@ int launch_t(const ConvParams& p, int classes, hipStream_t st) {
   CLC_LAUNCH_CHECK();
   return (1 << 20) | (WM << 16) | (WN << 12) | (BM << 3) | (BN >> 5);  // kernel-variant id (> 1): family 1 = conv_igemm_kernel<BM,BN,WM,WN>
 }
-template <int BM, int BN, int WM, int WN, bool TR>
-int launch_dma_t(const ConvParams& p, int classes, hipStream_t st) {
-  dim3 grid((p.M + BM - 1) / BM, (p.Cout + BN - 1) / BN, classes);
-  constexpr size_t lds_ab = (size_t)2 * (BM + BN) * BK * sizeof(float), lds_c = (size_t)BM * (BN + 4) * sizeof(float);
-  constexpr size_t lds = lds_ab > lds_c ? lds_ab : lds_c;
-  static PerDeviceOnce attr_once;
-  if (attr_once.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_dma_kernel<BM, BN, WM, WN, TR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
-  hipLaunchKernelGGL((conv_igemm_dma_kernel<BM, BN, WM, WN, TR>), grid, dim3(64 * WM * WN), lds, st, p);
-  CLC_LAUNCH_CHECK();
-  return (2 << 20) | (WM << 16) | (WN << 12) | (BM << 3) | (BN >> 5);  // family 2 = conv_igemm_dma_kernel<BM,BN,WM,WN>
-}
 template <int BM, int BN, int WM, int WN, bool TR, int KS, int OP = 0, bool BF = false>
 int launch_dma2_t(const ConvParams& p, int classes, hipStream_t st) {
   dim3 grid((p.M + BM - 1) / BM, (p.Cout + BN - 1) / BN, classes);
@@ -1134,18 +984,16 @@ int launch_p1x1(const ConvParams& p, int classes, hipStream_t st) {
 }
 template <int BM, int BN, int WM, int WN>
 int launch(const ConvParams& p, int classes, hipStream_t st) {
-  static const int use_dma = getenv("CLC_DMA") ? atoi(getenv("CLC_DMA")) : 1;   // CLC_DMA=0: register staging everywhere (A/B knob)
-  static const int dma_small = getenv("CLC_DMA_SMALL") ? atoi(getenv("CLC_DMA_SMALL")) : 1;
-  if (use_dma && p.in_op == CLC_IN_SQUARE && p.xs == nullptr && p.ks == 1 && p.stride == 1 && (BM >= 128 || dma_small) && clc_tuning[CLC_TUNE_DMA_LOOP] == 2)
+  // LDS-DMA staging wherever the operand needs no input prologue on its way into LDS (the square of a 1x1 layer is applied on the way out)
+  if (p.in_op == CLC_IN_SQUARE && p.xs == nullptr && p.ks == 1 && p.stride == 1)
     return p.transposed ? launch_dma2_t<BM, BN, WM, WN, true, 1, 1>(p, classes, st) : launch_dma2_t<BM, BN, WM, WN, false, 1, 1>(p, classes, st);
-  if (use_dma && p.in_op == CLC_IN_NONE && p.xs == nullptr && (BM >= 128 || dma_small) && clc_tuning[CLC_TUNE_DMA_LOOP] == 2)
+  if (p.in_op == CLC_IN_NONE && p.xs == nullptr)
     return p.ks == 1 && p.stride == 1
                ? (p.transposed ? launch_dma2_t<BM, BN, WM, WN, true, 1>(p, classes, st) : launch_dma2_t<BM, BN, WM, WN, false, 1>(p, classes, st))
                : (p.bf16   // reduced-precision mode: the 3x3 layers of the LDS-tiled family (maps larger than 16x16 = the transforms)
                       ? (p.transposed ? launch_dma2_t<BM, BN, WM, WN, true, 3, 0, true>(p, classes, st) : launch_dma2_t<BM, BN, WM, WN, false, 3, 0, true>(p, classes, st))
                       : (p.transposed ? launch_dma2_t<BM, BN, WM, WN, true, 3>(p, classes, st) : launch_dma2_t<BM, BN, WM, WN, false, 3>(p, classes, st)));
-  if (use_dma && p.in_op == CLC_IN_NONE && p.xs == nullptr && (BM >= 128 || dma_small))   // no input prologue -> the tiles can go straight to LDS
-    return p.transposed ? launch_dma_t<BM, BN, WM, WN, true>(p, classes, st) : launch_dma_t<BM, BN, WM, WN, false>(p, classes, st);
+  // the register-staged kernel: a squared operand of a 3x3 / strided layer, or the fused activation derivative on the gathered one (p.xs)
   return p.transposed ? launch_t<BM, BN, WM, WN, true>(p, classes, st) : launch_t<BM, BN, WM, WN, false>(p, classes, st);
 }
 
@@ -1168,8 +1016,7 @@ int launch_splitk_o(const ConvParams& p, int classes, hipStream_t st) {
 template <int BN>
 int launch_splitk(const ConvParams& p, int classes, hipStream_t st) {
   // the K-split factor is a function of the layer shape alone (never of the batch), like the family itself
-  static const int kw4 = getenv("CLC_SPLITK_KW4") ? atoi(getenv("CLC_SPLITK_KW4")) : 1;   // 0: always 8 waves (A/B knob)
-  if (kw4 && p.ks * p.ks * p.kc_tiles <= 4)
+  if (p.ks * p.ks * p.kc_tiles <= 4)
     return p.transposed ? launch_splitk_o<BN, true, 4, 1>(p, classes, st) : launch_splitk_o<BN, false, 4, 1>(p, classes, st);
   if (clc_tuning[CLC_TUNE_SPLITK_PF] == 1)
     return p.transposed ? launch_splitk_o<BN, true, 8, 1>(p, classes, st) : launch_splitk_o<BN, false, 8, 1>(p, classes, st);
@@ -1268,8 +1115,7 @@ extern "C" int clc_filter_transpose_batched(const clc_transpose_entry* table_dev
 // turns the K split on for this launch when the caller provided the scratch for it
 static void use_split(ConvParams& p, const clc_conv_desc* d, int classes) {
   const int k = conv_ksplit(p, classes);
-  if (k > 1 && d->workspace && d->workspace_bytes >= (size_t)k * classes * p.M * p.Cout * sizeof(float) && aligned16(d->workspace) &&
-      clc_tuning[CLC_TUNE_DMA_LOOP] == 2) {
+  if (k > 1 && d->workspace && d->workspace_bytes >= (size_t)k * classes * p.M * p.Cout * sizeof(float) && aligned16(d->workspace)) {
     p.ksplit = k;
     p.partial = (float*)d->workspace;
   }
@@ -1323,7 +1169,7 @@ static int fill_params(const clc_conv_desc* d, ConvParams& p, int& classes) {
   p.M = d->N * d->OH * d->OW;
   if (d->transposed && d->stride == 2) { classes = 4; p.M = d->N * (d->OH / 2) * (d->OW / 2); }
   p.w2 = d->w2; p.bias2 = d->bias2; p.group_rows = 0; p.pre_deriv = d->pre_deriv;
-  p.dma_place = clc_tuning[CLC_TUNE_DMA_PLACE]; p.xcd_map = 0; p.ablate = clc_tuning[CLC_TUNE_ABLATE]; p.reg_epi = 0; p.ksplit = 1; p.partial = nullptr; p.batch_variant_ok = d->batch_variant_ok; p.bf16 = 0;
+  p.xcd_map = 0; p.reg_epi = 0; p.ksplit = 1; p.partial = nullptr; p.batch_variant_ok = d->batch_variant_ok; p.bf16 = 0;
   p.res_gate = d->res ? d->res_gate : nullptr; p.ldg = d->ldg; p.rg_act = d->res_gate_act; p.rg_pre = d->res_gate_pre;
   p.out_gate = d->out_gate; p.ldog = d->ldog; p.og_act = d->out_gate_act; p.og_pre = d->out_gate_pre;
   CLC_CHECK(!d->out_gate || !d->shuffle, "clc_conv2d: out_gate with shuffle");
@@ -1389,22 +1235,14 @@ extern "C" int clc_conv2d(const clc_conv_desc* d, clc_stream_t stream) {
     // chip without splitting K, and the LDS-tiled kernel shares each operand tile among 4 waves where the split-K family
     // re-fetches fragments per wave (224 -> 704 @ 4096 rows: 192 -> 130 us).  Data gradients exist in training only, so the
     // codec path's batch-invariant family rule is untouched.  (The forward layers of the same nets measured slower this way.)
-    static const int heavy_dgrad = getenv("CLC_HEAVY_DGRAD") ? atoi(getenv("CLC_HEAVY_DGRAD")) : 1;   // 0: A/B knob
-    static const int heavy_min = getenv("CLC_HEAVY_MIN") ? atoi(getenv("CLC_HEAVY_MIN")) : 60;   // K-tiles (224-channel 3x3: 63); the 36-tile ones measured faster on split-K in the step
-    if (heavy_dgrad && img_pix <= 256 && d->transposed && d->ks * d->ks * p.kc_tiles >= heavy_min && C >= 128 &&
+    // (>= 60 K-tiles: the 224-channel 3x3 layers have 63; the 36-tile ones measured faster on split-K in the step)
+    if (img_pix <= 256 && d->transposed && d->ks * d->ks * p.kc_tiles >= 60 && C >= 128 &&
         (long)((p.M + 63) / 64) * ((C + 63) / 64) * classes >= 128) {
       use_split(p, d, classes);
       return launch<64, 64, 2, 2>(p, classes, st);
     }
     // 32x32 tiles: these layers are bound by how many CUs get MFMA work (f32 MFMA = 64 cycles each), not by operand
-    // re-use, so the smaller tile (2x the workgroups of 32x64) wins on every 16x16 shape measured
-    // ... except the slice-parameter nets with multi-MB filters (448..704 -> 224), where halving the number of N tiles
-    // halves the filter re-reads that dominate them
-    static const int sk_rule = getenv("CLC_SPLITK_RULE") ? atoi(getenv("CLC_SPLITK_RULE")) : 1;   // 0: old rule (A/B knob)
-    if (sk_rule == 0) {
-      if ((long)d->Cout * d->ks * d->ks * d->Cin > 200000 && C > 32) return launch_splitk<64>(p, classes, st);
-      return launch_splitk<32>(p, classes, st);
-    }
+    // re-use, so the smaller tile (2x the workgroups of 32x64) wins on every 16x16 shape measured:
     // 32x32 tiles while they fit the chip in one round (256 workgroups), 32x64 beyond that.  Both variants give every
     // output element the same K order (same wave / K-tile assignment, same combine tree), so the choice may look at M.
     const long wg32 = (long)((p.M + 31) / 32) * ((C + 31) / 32) * classes;

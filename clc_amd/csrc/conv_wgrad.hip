@@ -1054,12 +1054,6 @@ __global__ __launch_bounds__(256) void wgrad_small_kernel(const WgradParams p, i
 
 struct Plan { int bm, bn, splits, k_per_split, nci; bool small; int taps; };   // taps = TW of the all-taps kernel, or 0
 
-int taps_mode() {   // CLC_WGRAD_TAPS: 0 = never, 1 = where the tap-per-workgroup plan is not 128x128, 2 = wherever eligible (default)
-  static int mode = -1;
-  if (mode < 0) { const char* e = getenv("CLC_WGRAD_TAPS"); mode = e ? atoi(e) : 2; }
-  return mode;
-}
-
 Plan make_plan(const clc_wgrad_desc* d) {
   Plan pl;
   pl.taps = 0;
@@ -1074,6 +1068,25 @@ Plan make_plan(const clc_wgrad_desc* d) {
     long kps = (K + splits - 1) / splits;
     pl.k_per_split = (int)kps; pl.splits = (int)((K + kps - 1) / kps);
     return pl;
+  }
+  {   // the all-taps kernel wherever the layer is eligible
+    auto lg = [](int v) { int s = 0; while ((1 << s) < v) ++s; return (1 << s) == v ? s : -1; };
+    const int la = lg(d->OW), lb = lg(d->OH * d->OW), tw = d->OW < 32 ? d->OW : 32;
+    const bool eligible = d->ks == 3 && d->stride == 1 && d->pad == 1 && la >= 3 && lb >= 0 && d->OH >= 32 / tw;
+    if (eligible) {
+      pl.taps = tw; pl.bm = 64; pl.bn = 64; pl.nci = (d->Cin + 63) / 64;
+      const long ktiles = K / 32, tiles = (long)((d->Cout + 63) / 64) * pl.nci;
+      long sp = (ktiles + 15) / 16;                    // <= ~16 K-tiles (a ~60 us MFMA chain) per workgroup,
+      const long fill = (256 + tiles - 1) / tiles;     // enough workgroups for one per CU while K-tiles last (>= 2 each),
+      if (sp < fill) sp = fill;
+      if (sp > ktiles / 2) sp = ktiles / 2 > 0 ? ktiles / 2 : 1;
+      const long cap = 512 / tiles > 0 ? 512 / tiles : 1;
+      if (sp > cap) sp = cap;                          // and no more slabs than two workgroups per CU need
+      const long kt = (ktiles + sp - 1) / sp;
+      pl.k_per_split = (int)(kt * 32);
+      pl.splits = (int)((ktiles + kt - 1) / kt);
+      return pl;
+    }
   }
   // Tile and K-split choice by a small cost model (cycles): time = max(longest MFMA chain of one workgroup,
   // total MFMA work / 256 CUs) + slab traffic of the fixed-order reduce (launch + 2 x splits x |dW| bytes at ~4 TB/s).
@@ -1103,26 +1116,6 @@ Plan make_plan(const clc_wgrad_desc* d) {
         if (best_cost < 0 || cost < best_cost) { best_cost = cost; pl.bm = bm; pl.bn = bn; splits = sp; }
       }
     }
-  {
-    auto lg = [](int v) { int s = 0; while ((1 << s) < v) ++s; return (1 << s) == v ? s : -1; };
-    const int la = lg(d->OW), lb = lg(d->OH * d->OW), tw = d->OW < 32 ? d->OW : 32;
-    const bool eligible = d->ks == 3 && d->stride == 1 && d->pad == 1 && la >= 3 && lb >= 0 && d->OH >= 32 / tw;
-    const int mode = taps_mode();
-    if (eligible && (mode == 2 || (mode == 1 && !(pl.bm == 128 && pl.bn == 128)))) {
-      pl.taps = tw; pl.bm = 64; pl.bn = 64; pl.nci = (d->Cin + 63) / 64;
-      const long ktiles = K / 32, tiles = (long)((d->Cout + 63) / 64) * pl.nci;
-      long sp = (ktiles + 15) / 16;                    // <= ~16 K-tiles (a ~60 us MFMA chain) per workgroup,
-      const long fill = (256 + tiles - 1) / tiles;     // enough workgroups for one per CU while K-tiles last (>= 2 each),
-      if (sp < fill) sp = fill;
-      if (sp > ktiles / 2) sp = ktiles / 2 > 0 ? ktiles / 2 : 1;
-      const long cap = 512 / tiles > 0 ? 512 / tiles : 1;
-      if (sp > cap) sp = cap;                          // and no more slabs than two workgroups per CU need
-      const long kt = (ktiles + sp - 1) / sp;
-      pl.k_per_split = (int)(kt * 32);
-      pl.splits = (int)((ktiles + kt - 1) / kt);
-      return pl;
-    }
-  }
   pl.nci = (d->Cin + pl.bn - 1) / pl.bn;
   long kps = (K + splits - 1) / splits;
   kps = (kps + BK - 1) / BK * BK;
@@ -1318,7 +1311,6 @@ bool sk_collect(const Pending* pend, int n, SKGroup& g, float* region, int slot_
   }
   if (g.count == 0) return false;
   long G = g.total / min_units;                     // a workgroup's chain of MFMAs must amortise its prologue / partial-tile write
-  if (clc_tuning[CLC_TUNE_SK_HALF] && max_g > kCUs) max_g = kCUs;   // one workgroup per CU: leaves wave slots to a concurrent stream
   g.G = (int)(G < 1 ? 1 : (G > max_g ? max_g : G));
   return true;
 }

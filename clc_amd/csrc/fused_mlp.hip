@@ -21,7 +21,7 @@
 //     same epilogue expressions are used, so the fused launch produces THE SAME BITS as the two-launch chain (checked by the tests): the
 //     codec may use either, whatever the batch size;
 //   * both filters (2 x 64 KB) are resident in LDS for the lifetime of a persistent workgroup, as slot-swizzled [K-tile][row][32] images
-//     (conv_igemm_dma_kernel's layout: conflict-free ds_read_b128 fragments), deposited once by LDS-DMA.
+//     (conv_igemm_dma2_kernel's layout: conflict-free ds_read_b128 fragments), deposited once by LDS-DMA.
 //
 // Backward (`clc_mlp_bwd`), per 32-pixel wave tile and 32-channel block hb of the hidden layer:
 //   h  = W1[hb] x + b1          recomputed from the saved LayerNorm output (+ 8.6 GFLOP per 8 x 128 x 128 block; - 670 MB of traffic)
@@ -144,7 +144,6 @@ __device__ __forceinline__ void colsum_block(float* scratch, const f32x4 (&v)[4]
 // The LayerNorm gradient as the epilogue of a data-gradient launch: dxacc = the gradient of LN's output in the accumulator layout, xh = the raw
 // x of the tile's pixels in the same layout (destroyed), add = the residual branch's gradient.  layernorm_bwd_vec_kernel<16>'s expressions and
 // row-sum order (-> its bits); the tile's dgamma / dbeta column sums are added to the lane-private slots `wacc`.
-template <bool NO_COLSUM>
 __device__ __forceinline__ void ln_bwd_epilogue(const f32x16 (&dxacc)[2], f32x4 (&xh)[2][4], const f32x4 (&add)[2][4], const float* lns, float* scratch,
                                                 float* wacc, __amdgpu_buffer_rsrc_t dxr, unsigned pix, unsigned lddx, int lane, int h) {
   f32x4 dv[2][4];
@@ -174,7 +173,6 @@ __device__ __forceinline__ void ln_bwd_epilogue(const f32x16 (&dxacc)[2], f32x4 
       o += add[ib][q];   // the residual branch's gradient
       st4(o, dxr, (pix * lddx + (unsigned)(ib * 32 + 8 * q + 4 * h)) * 4u);
     }
-  if (NO_COLSUM) return;
   int ln_ = lane;
   asm volatile("" : "+v"(ln_));   // (addresses derived from here are recomputed per tile: hoisted out of the tile loop they spill)
 #pragma unroll
@@ -201,7 +199,7 @@ __device__ __forceinline__ void ln_ws_row(const float* slots, float* ln_ws, int 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- forward
-// Measured on the way (8 x 128 x 128, one launch, graph-replayed; tools/bench_mlp.py with CLC_TUNING=12:x):
+// Measured on the way (8 x 128 x 128, one launch, graph-replayed; tools/bench_mlp.py with the timing ablations of the since retired tuning key 12):
 //   * f32 MFMAs and VALU instructions do NOT overlap on this hardware (the f32 matrix rate IS the vector rate): the GELU's ~19 VALU
 //     instructions per value add their full time (20 us of 111) whether they are interleaved with the MFMAs or not, with one or two
 //     waves per SIMD.  A software pipeline that issued the next block's fc1 MFMAs between the GELU of the current one was SLOWER
@@ -209,9 +207,9 @@ __device__ __forceinline__ void ln_ws_row(const float* slots, float* ln_ws, int 
 //   * consecutive MFMAs on ONE accumulator pay the dependent-issue latency (a block of 32 dependent 32x32x2 MFMAs ran at ~83 % of the
 //     independent rate), so two hidden blocks are computed side by side and every MFMA alternates between two accumulators;
 //   * LDS fragment reads cost nothing measurable (ablated: 105 vs 111 us).
-// SAVE: store fc1's pre-activation (training, save mode).  PK: GELU on the packed-f32 instructions (gelu_parts2; same bits).
+// SAVE: store fc1's pre-activation (training, save mode).  GELU runs on the packed-f32 instructions (gelu_parts2; the bits of gelu_parts).
 // LN: LayerNorm in front, computed in registers from the raw input, which is also the residual (p.res is not read).
-template <int NW, int ABL = 0, bool SAVE = false, bool PK = true, bool LN = false>   // ABL: timing diagnostics of CLC_TUNE_ABLATE (results WRONG): 1 = no GELU arithmetic, 2 = no fc1 MFMAs, 4 = no LDS fragment reads
+template <int NW, bool SAVE = false, bool LN = false>
 __global__ __launch_bounds__(64 * NW, 2) void mlp_fwd_kernel(const MlpParams p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* W1s = smem;                    // [2][256][32]  fc1: rows = hidden, K = input channels
@@ -290,8 +288,7 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_fwd_kernel(const MlpParams p) 
       for (int j = 0; j < 8; ++j) {       // K-steps (kt, t8) in the tiled kernels' order
         f32x4 a[2];
 #pragma unroll
-        for (int b = 0; b < 2; ++b) a[b] = (ABL & 4) ? xf[b][j & 3] : *reinterpret_cast<const f32x4*>(w1b + (((j >> 2) * CH + b * 32) << 5) + fo[j & 3]);
-        if (ABL & 2) { asm volatile("" ::"v"(a[0]), "v"(a[1])); continue; }
+        for (int b = 0; b < 2; ++b) a[b] = *reinterpret_cast<const f32x4*>(w1b + (((j >> 2) * CH + b * 32) << 5) + fo[j & 3]);
 #pragma unroll
         for (int s = 0; s < 4; ++s)
 #pragma unroll
@@ -309,21 +306,11 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_fwd_kernel(const MlpParams p) 
           if (SAVE) st4(v, hr, (pix * (unsigned)CH + (unsigned)((2 * hp + b) * 32 + 8 * q + 4 * h)) * 4u);   // (training, save mode)
 #pragma unroll
           for (int s = 0; s < 4; s += 2) {
-            if (ABL & 1) { hacc[b][4 * q + s] = v[s]; hacc[b][4 * q + s + 1] = v[s + 1]; continue; }
-            if (PK) {
-              f32x2 cdf, pdf;
-              const f32x2 vv = {v[s], v[s + 1]};
-              gelu_parts2(vv, cdf, pdf);
-              const f32x2 gg = vv * cdf;
-              hacc[b][4 * q + s] = gg[0]; hacc[b][4 * q + s + 1] = gg[1];
-            } else {
-#pragma unroll
-              for (int e = 0; e < 2; ++e) {
-                float cdf, pdf;
-                gelu_parts(v[s + e], cdf, pdf);
-                hacc[b][4 * q + s + e] = v[s + e] * cdf;
-              }
-            }
+            f32x2 cdf, pdf;
+            const f32x2 vv = {v[s], v[s + 1]};
+            gelu_parts2(vv, cdf, pdf);
+            const f32x2 gg = vv * cdf;
+            hacc[b][4 * q + s] = gg[0]; hacc[b][4 * q + s + 1] = gg[1];
           }
         }
       // fc2: K-tiles 2 hp, 2 hp + 1 of the hidden layer; B operands = the registers just computed
@@ -334,7 +321,7 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_fwd_kernel(const MlpParams p) 
         for (int q = 0; q < 4; ++q) {
           f32x4 a[2];
 #pragma unroll
-          for (int ob = 0; ob < 2; ++ob) a[ob] = (ABL & 4) ? xf[ob][q] : *reinterpret_cast<const f32x4*>(w2b + ((ob * 32) << 5) + fo[q]);
+          for (int ob = 0; ob < 2; ++ob) a[ob] = *reinterpret_cast<const f32x4*>(w2b + ((ob * 32) << 5) + fo[q]);
 #pragma unroll
           for (int s = 0; s < 4; ++s)
 #pragma unroll
@@ -380,7 +367,7 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_fwd_kernel(const MlpParams p) 
 // LN: x is the block's raw input and ln_out the LN(x) the forward launch stored (fc1's operand here); dx is the gradient of the whole
 // `x + mlp(LN(x))` — layernorm_bwd_vec_kernel<16>'s expressions on the accumulator registers (row statistics again from x), dy added as
 // the residual's gradient — and the per-workgroup column sums for dgamma / dbeta go to ln_ws.
-template <int NW, bool LOADH, bool LN = false, int ABL = 0>   // ABL (timing diagnostics, results WRONG): 1 = no dgamma / dbeta column sums, 4 = x not read again
+template <int NW, bool LOADH, bool LN = false>
 __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_kernel(const MlpParams p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* W1s = smem;                    // [2][256][32]  fc1 filter: rows = hidden, K = input channels (also read column-wise for dx)
@@ -529,14 +516,14 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_kernel(const MlpParams p) 
 #pragma unroll
         for (int ib = 0; ib < 2; ++ib)
 #pragma unroll
-          for (int q = 0; q < 4; ++q) xh[ib][q] = (ABL & 4) ? xf[ib][q] : ld4(xr, xo + (unsigned)(ib * 32 + 8 * q) * 4u);
+          for (int q = 0; q < 4; ++q) xh[ib][q] = ld4(xr, xo + (unsigned)(ib * 32 + 8 * q) * 4u);
       });
     } else {
 #pragma unroll 1
       for (int hp = 0; hp < 4; ++hp) hp_iter(hp, [] {});
     }
     if (LN) {
-      ln_bwd_epilogue<(ABL & 1) != 0>(dxacc, xh, df, lns, scratch, wacc, dxr, pix, (unsigned)p.lddx, lane, h);
+      ln_bwd_epilogue(dxacc, xh, df, lns, scratch, wacc, dxr, pix, (unsigned)p.lddx, lane, h);
       continue;
     }
 #pragma unroll
@@ -723,7 +710,7 @@ __global__ __launch_bounds__(64 * NW, 2) void lnlin_bwd_kernel(const LnLinParams
 #pragma unroll
         for (int t8 = 0; t8 < 4; ++t8) dq[b][t8] = dqn[b][t8];
     }
-    ln_bwd_epilogue<false>(dxacc, xh, da, lns, scratch, wacc, dxr, pix, (unsigned)p.lddx, lane, h);
+    ln_bwd_epilogue(dxacc, xh, da, lns, scratch, wacc, dxr, pix, (unsigned)p.lddx, lane, h);
   }
   __syncthreads();   // (every wave leaves the tile loop after the same number of rounds)
   ln_ws_row<NW>(lns + 2 * CI + NW * 512, p.ln_ws, tid);
@@ -988,41 +975,21 @@ static int mlp_launch(MlpParams& p, bool bwd, hipStream_t st) {
   p.tiles = (p.M + 32 * NW - 1) / (32 * NW);
   const int grid = mlp_grid(p.M, NW);
   const size_t lds_f = (size_t)(2 * CH * 32 + 8 * CO * 32 + CH + CO + 2 * CI + NW * 512) * sizeof(float), lds_b = (size_t)(4 * CH * 32 + CH + NW * 512 + 2 * CI + NW * 256) * sizeof(float);
-  const int abl = clc_tuning[CLC_TUNE_ABLATE];
   static PerDeviceOnce attr_once;
   if (attr_once.first()) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_bwd_kernel<NW, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_bwd_kernel<NW, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_bwd_kernel<NW, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
     auto optin = [&](auto kern) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f); };
-    optin(&mlp_fwd_kernel<NW, 0, true, true>); optin(&mlp_fwd_kernel<NW, 0, false, true>);
-    optin(&mlp_fwd_kernel<NW, 0, true, false>); optin(&mlp_fwd_kernel<NW, 0, false, false>);
-    optin(&mlp_fwd_kernel<NW, 0, false, true, true>);
-    if (NW == 8) { optin(&mlp_fwd_kernel<8, 1>); optin(&mlp_fwd_kernel<8, 2>); optin(&mlp_fwd_kernel<8, 4>); optin(&mlp_fwd_kernel<8, 5>); }
+    optin(&mlp_fwd_kernel<NW, true>); optin(&mlp_fwd_kernel<NW, false>); optin(&mlp_fwd_kernel<NW, false, true>);
   }
   auto fwd = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds_f, st, p); };
-  if (bwd && p.ln_gamma && NW == 8 && abl) {   // timing diagnostics (wrong results)
-    auto go = [&](auto kern) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds_b, st, p);
-    };
-    if (abl == 1) go(&mlp_bwd_kernel<8, false, true, 1>);
-    else if (abl == 4) go(&mlp_bwd_kernel<8, false, true, 4>);
-    else go(&mlp_bwd_kernel<8, false, true, 5>);
-  } else if (bwd && p.ln_gamma) hipLaunchKernelGGL((mlp_bwd_kernel<NW, false, true>), dim3(grid), dim3(64 * NW), lds_b, st, p);
-  else if (!bwd && p.ln_gamma) fwd(&mlp_fwd_kernel<NW, 0, false, true, true>);
+  if (bwd && p.ln_gamma) hipLaunchKernelGGL((mlp_bwd_kernel<NW, false, true>), dim3(grid), dim3(64 * NW), lds_b, st, p);
+  else if (!bwd && p.ln_gamma) fwd(&mlp_fwd_kernel<NW, false, true>);
   else if (bwd && p.hsave) hipLaunchKernelGGL((mlp_bwd_kernel<NW, true>), dim3(grid), dim3(64 * NW), lds_b, st, p);
   else if (bwd) hipLaunchKernelGGL((mlp_bwd_kernel<NW, false>), dim3(grid), dim3(64 * NW), lds_b, st, p);
-  else if (NW == 8 && abl) {   // timing diagnostics (wrong results): see the template argument
-    if (abl == 1) fwd(&mlp_fwd_kernel<8, 1>);
-    else if (abl == 2) fwd(&mlp_fwd_kernel<8, 2>);
-    else if (abl == 4) fwd(&mlp_fwd_kernel<8, 4>);
-    else fwd(&mlp_fwd_kernel<8, 5>);
-  } else if (clc_tuning[CLC_TUNE_MLP_PK]) {
-    if (p.hsave) fwd(&mlp_fwd_kernel<NW, 0, true, true>); else fwd(&mlp_fwd_kernel<NW, 0, false, true>);
-  } else {
-    if (p.hsave) fwd(&mlp_fwd_kernel<NW, 0, true, false>); else fwd(&mlp_fwd_kernel<NW, 0, false, false>);
-  }
+  else if (p.hsave) fwd(&mlp_fwd_kernel<NW, true>);
+  else fwd(&mlp_fwd_kernel<NW, false>);
   CLC_LAUNCH_CHECK();
   return 0;
 }

@@ -37,7 +37,6 @@ struct RUParams {
   // g2 / g1 / dx, and the saved activations of the forward pass (dense):
   const float* sy; const float* st2; const float* st1;
   int N, per_set;                          // images, images per filter set
-  int ablate;                              // CLC_TUNE_ABLATE (timing diagnostics, results WRONG): 2 = no result stores
   unsigned x_bytes;
 };
 
@@ -155,7 +154,7 @@ __global__ __launch_bounds__(512, 1) void ru_fused_kernel(const RUParams p) {
         v = in_img[r] ? v : 0.f;                                  // the 3x3's zero padding / rows past the halo
         T1s[hrs[r] * LDT + co] = v;
         const int hy = (hrs[r] * 205) >> 11, hx = hrs[r] - hy * HW;
-        if (in_img[r] && hy >= 1 && hy <= TH && hx >= 1 && hx <= TW && !(p.ablate & 2)) p.t1[pix[r]] = v;
+        if (in_img[r] && hy >= 1 && hy <= TH && hx >= 1 && hx <= TW) p.t1[pix[r]] = v;
       }
     };
     if (kh == 0) finish(std::integral_constant<int, 0>{}); else finish(std::integral_constant<int, 8>{});
@@ -209,7 +208,7 @@ __global__ __launch_bounds__(512, 1) void ru_fused_kernel(const RUParams p) {
         else v = v > 0.f ? v : 0.f;
         const int i = rowidx(4 * q + r) + 4 * h;
         T2s[i * LDT + co] = v;
-        if (!(p.ablate & 2)) p.t2[pix[r]] = v;
+        p.t2[pix[r]] = v;
       }
     };
     switch (kq) {
@@ -258,7 +257,7 @@ __global__ __launch_bounds__(512, 1) void ru_fused_kernel(const RUParams p) {
         const float other = red[((ct * 2 + (kh ^ 1)) * 8 + r) * 64 + lane];
         float v = ((kh == 0 ? acc[R0 + r] + other : other + acc[R0 + r]) + bv3) + xv;   // residual BEFORE the activation (relu(out + identity))
         if constexpr (!BWD) v = v > 0.f ? v : 0.f;
-        if (!(p.ablate & 2) || v == 123.456f) p.y[((size_t)(img * H + y0 + qy) * W + x0 + qx) * C + co] = v;
+        p.y[((size_t)(img * H + y0 + qy) * W + x0 + qx) * C + co] = v;
       }
     };
     if (kh == 0) finish(std::integral_constant<int, 0>{}); else finish(std::integral_constant<int, 8>{});
@@ -286,7 +285,6 @@ static int ru_launch(const clc_ru_desc* d, bool bwd, clc_stream_t stream, const 
   const size_t xb = ((size_t)d->N * 256 - 1) * d->ldx * 4 + 128 * 4;
   CLC_CHECK(xb < (1ull << 31), "%s: tensor larger than 2 GiB", who);
   p.x_bytes = (unsigned)xb;
-  p.ablate = clc_tuning[CLC_TUNE_ABLATE];
   constexpr size_t lds_f = (size_t)(64 * 128 + 64 * 68 + 32 * 68 + 8192) * sizeof(float), lds_b = lds_f + 64 * 128 * sizeof(float);
   static PerDeviceOnce attr_once;
   if (attr_once.first()) {

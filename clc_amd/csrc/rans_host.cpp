@@ -36,8 +36,14 @@ extern "C" int clc_version(void) { return 200; }
 #define CLC_TUNING_DEFAULTS {2, 1, 1, 0, 1024, 64, 1, 8, 1, 1, 1, 1, 0, 1, 0, 1, 3, 1, 1, 1, 1, 1, 1, 7, 3}
 int clc_tuning[25] = CLC_TUNING_DEFAULTS;   // (CLC_TUNE_COUNT entries: csrc/common.h, which this host-only file cannot include)
 static const int clc_tuning_default[25] = CLC_TUNING_DEFAULTS;
+// Retired keys keep their numbers (the C ABI) and their last default, which is the only value they accept.
+static bool clc_tuning_retired(int key) { return key == 0 || key == 2 || key == 3 || key == 12 || key == 19; }
 extern "C" int clc_set_tuning(int key, int value) {
   if (key < 0 || key >= (int)(sizeof(clc_tuning) / sizeof(clc_tuning[0]))) { clc_set_error("clc_set_tuning: key %d out of range", key); return -1; }
+  if (clc_tuning_retired(key) && value != clc_tuning_default[key]) {
+    clc_set_error("clc_set_tuning: key %d is retired; it only accepts its last default, %d (got %d)", key, clc_tuning_default[key], value);
+    return -1;
+  }
   const int old = clc_tuning[key];
   clc_tuning[key] = value;
   return old;
@@ -50,13 +56,14 @@ extern "C" int clc_get_tuning(int key) {
 // The slice loop is autoregressive through the arithmetic decoder, so a decoder only stays in sync with an encoder that produced the
 // same float means / scales bit for bit.  kGeneration is bumped by hand whenever a kernel the codec path launches changes the order
 // in which it sums; the tuning keys that select between kernels of DIFFERENT order (kernel family limits, the reduced-precision mode,
-// the forward halves of the attention tiling, the diagnostic ablation) are folded in when they are off their defaults.
+// the forward halves of the attention tiling) are folded in when they are off their defaults.
 // (key 11 — K split of under-filled data gradients, with a threshold value — reaches TRANSPOSED launches only, i.e. backward passes: not an
 //  order key of the codec path.)
 static uint32_t clc_order_hash(bool* dflt_out) {
   const int kGeneration = 6;
   // (key 23 — Winograd kernel — reaches only launches that carry a transformed filter (clc_conv_desc.w_wino), which the host side hands over for
   //  TRAINING forward passes and data gradients alone: not an order key of the codec path.)
+  // (keys 0 and 12 are retired: pinned at 2 and 0, they hash as those constants in their old positions, which keeps every tag and hash)
   static const int order_keys[] = {0, 4, 5, 12, 14, 16};
   uint32_t h = 2166136261u ^ (uint32_t)kGeneration;
   bool dflt = true;

@@ -50,7 +50,8 @@ __device__ __forceinline__ bool masked(const AttnParams& p, int wy, int wx, int 
   return m;
 }
 
-// T = tokens per window (64 or 16), HD = head dim. One wave per workgroup; G = 64/T window slots.
+// T = tokens per window (64 or 16; only the 4x4 windows, T = 16, are launched: the 8x8 ones run on the MFMA kernels below),
+// HD = head dim. One wave per workgroup; G = 64/T window slots.
 // Two sweeps over the keys (softmax statistics online, then P.V) instead of a T-long score
 // array per lane: keeps the kernel in registers (no scratch) at the price of computing q.k twice.
 template <int T, int HD>
@@ -722,10 +723,6 @@ int check_geom(const char* who, int B, int H, int W, int C, int heads, int ws, i
   return 0;
 }
 
-static bool attn_use_mfma() {
-  static const int use_mfma = getenv("CLC_ATTN_MFMA") ? atoi(getenv("CLC_ATTN_MFMA")) : 1;   // 0: VALU kernels (A/B knob)
-  return use_mfma != 0;
-}
 void fill(AttnParams& p, int B, int H, int W, int C, int heads, int ws, int shift, int target_blocks, bool paired = false, bool bwd = false) {
   p.B = B; p.H = H; p.W = W; p.C = C; p.heads = heads; p.ws = ws; p.shift = shift;
   p.nwin_y = H / ws; p.nwin_x = W / ws;
@@ -743,7 +740,7 @@ void fill(AttnParams& p, int B, int H, int W, int C, int heads, int ws, int shif
   p.groups_per_block = per;
   // backward on a grid that leaves most wave slots empty: two workgroups per window group (winattn_bwd_mfma_kernel)
   const int nbx = (p.groups_total + per - 1) / per;
-  p.split = (bwd && ws == 8 && attn_use_mfma() && clc_tuning[CLC_TUNE_ATTN_SPLIT] && (long)nbx * heads <= 1024) ? 1 : 0;
+  p.split = (bwd && ws == 8 && clc_tuning[CLC_TUNE_ATTN_SPLIT] && (long)nbx * heads <= 1024) ? 1 : 0;
 }
 
 #define DISPATCH(KERNEL, T_, hd, grid, p, st)                                                          \
@@ -783,10 +780,8 @@ static int winattn_fwd_impl(const float* qkv, int ldq, const float* relbias, con
   AttnParams p{};
   p.qkv = qkv; p.relbias = relbias; p.out = out; p.lse = lse; p.ldq = ldq; p.ldo = ldo;
   const int hd = C / heads;
-  static const int use_mfma = getenv("CLC_ATTN_MFMA") ? atoi(getenv("CLC_ATTN_MFMA")) : 1;   // 0: VALU kernels (A/B knob)
-  static const int nh_on = getenv("CLC_ATTN_NH") ? atoi(getenv("CLC_ATTN_NH")) : 1;          // 0: one head per single-wave workgroup (A/B knob)
   // forward MFMA kernel: the heads that share a 128-byte line of a token's row as the waves of ONE workgroup (whole-line loads and stores)
-  const int nh = (ws == 8 && use_mfma && nh_on && (hd == 8 || hd == 16) && heads % (32 / hd) == 0 && ldq % 4 == 0 && ldo % 4 == 0 && (hd * (32 / hd)) % 32 == 0) ? 32 / hd : 1;
+  const int nh = (ws == 8 && (hd == 8 || hd == 16) && heads % (32 / hd) == 0 && ldq % 4 == 0 && ldo % 4 == 0 && (hd * (32 / hd)) % 32 == 0) ? 32 / hd : 1;
   fill(p, B, H, W, C, heads / nh, ws, shift, nh > 1 ? 4096 : 8192, relbias2 != nullptr);
   p.heads = heads;
   p.relbias2 = relbias2;
@@ -795,7 +790,7 @@ static int winattn_fwd_impl(const float* qkv, int ldq, const float* relbias, con
     const int m4 = clc_tuning[CLC_TUNE_ATTN_4B];
     if (hd == 8) { if (m4 & 4) hipLaunchKernelGGL((winattn_fwd_mfma_kernel<8, true, 4>), grid, dim3(256), 0, (hipStream_t)stream, p); else hipLaunchKernelGGL((winattn_fwd_mfma_kernel<8, false, 4>), grid, dim3(256), 0, (hipStream_t)stream, p); }
     else { if (m4 & 1) hipLaunchKernelGGL((winattn_fwd_mfma_kernel<16, true, 2>), grid, dim3(128), 0, (hipStream_t)stream, p); else hipLaunchKernelGGL((winattn_fwd_mfma_kernel<16, false, 2>), grid, dim3(128), 0, (hipStream_t)stream, p); }
-  } else if (ws == 8 && use_mfma) {
+  } else if (ws == 8) {
     // head_dim <= 16: the N = head_dim products on 4-block 16x16x1 MFMAs (key 16, bit mask: 1 = head_dim 16, 2 = head_dim-8 backward,
     // 4 = head_dim-8 forward).  The head_dim-8 FORWARD (the analysis / synthesis transforms) is off by default: another summation order
     // moves y by ~4e-6, and on the parity sample one hyper-latent sits that close to .5 — its flip costs 9e-4 bpp against the oracle
@@ -804,8 +799,7 @@ static int winattn_fwd_impl(const float* qkv, int ldq, const float* relbias, con
     if (hd == 8) { if (m4 & 4) hipLaunchKernelGGL((winattn_fwd_mfma_kernel<8, true>), grid, dim3(64), 0, (hipStream_t)stream, p); else hipLaunchKernelGGL((winattn_fwd_mfma_kernel<8, false>), grid, dim3(64), 0, (hipStream_t)stream, p); }
     else if (hd == 16) { if (m4 & 1) hipLaunchKernelGGL((winattn_fwd_mfma_kernel<16, true>), grid, dim3(64), 0, (hipStream_t)stream, p); else hipLaunchKernelGGL((winattn_fwd_mfma_kernel<16, false>), grid, dim3(64), 0, (hipStream_t)stream, p); }
     else hipLaunchKernelGGL((winattn_fwd_mfma_kernel<32, false>), grid, dim3(64), 0, (hipStream_t)stream, p);
-  } else if (ws == 8) DISPATCH(winattn_fwd_kernel, 64, hd, grid, p, (hipStream_t)stream);
-  else DISPATCH(winattn_fwd_kernel, 16, hd, grid, p, (hipStream_t)stream);
+  } else DISPATCH(winattn_fwd_kernel, 16, hd, grid, p, (hipStream_t)stream);
   CLC_LAUNCH_CHECK();
   return 0;
 }
@@ -838,14 +832,12 @@ static int winattn_bwd_impl(const float* dout, int lddo, const float* qkv, int l
   const int nbx = ((p.groups_total + p.groups_per_block - 1) / p.groups_per_block) * (p.split ? 2 : 1);   // (= clc_winattn_bwd_blocks)
   dim3 grid(nbx, heads);
   const int hd = C / heads;
-  const bool use_mfma = attn_use_mfma();
-  if (ws == 8 && use_mfma) {
+  if (ws == 8) {
     const int m4 = clc_tuning[CLC_TUNE_ATTN_4B];
     if (hd == 8) { if (m4 & 2) hipLaunchKernelGGL((winattn_bwd_mfma_kernel<8, true>), grid, dim3(64), 0, (hipStream_t)stream, p); else hipLaunchKernelGGL((winattn_bwd_mfma_kernel<8, false>), grid, dim3(64), 0, (hipStream_t)stream, p); }
     else if (hd == 16) { if (m4 & 1) hipLaunchKernelGGL((winattn_bwd_mfma_kernel<16, true>), grid, dim3(64), 0, (hipStream_t)stream, p); else hipLaunchKernelGGL((winattn_bwd_mfma_kernel<16, false>), grid, dim3(64), 0, (hipStream_t)stream, p); }
     else hipLaunchKernelGGL((winattn_bwd_mfma_kernel<32, false>), grid, dim3(64), 0, (hipStream_t)stream, p);
-  } else if (ws == 8) DISPATCH(winattn_bwd_kernel, 64, hd, grid, p, (hipStream_t)stream);
-  else DISPATCH(winattn_bwd_kernel, 16, hd, grid, p, (hipStream_t)stream);
+  } else DISPATCH(winattn_bwd_kernel, 16, hd, grid, p, (hipStream_t)stream);
   CLC_LAUNCH_CHECK();
   if (drelbias == nullptr) return 0;   // partial rows [blocks][n] stay in wsb for clc_partial_reduce_batched
   const int n = heads * (2 * ws - 1) * (2 * ws - 1);

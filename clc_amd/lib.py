@@ -221,10 +221,13 @@ def load():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    # CLC_TUNING="key:value,..." -> clc_set_tuning (A/B switches between kernel variants that compute the same results)
+    # CLC_TUNING="key:value,..." -> clc_set_tuning (A/B switches between kernel variants); an unknown key or a value a retired key
+    # refuses raises instead of being dropped
     for item in filter(None, os.environ.get("CLC_TUNING", "").split(",")):
         k, v = item.split(":")
-        L.clc_set_tuning(int(k), int(v))
+        if L.clc_set_tuning(int(k), int(v)) < 0:
+            msg = L.clc_last_error()
+            raise ClcError(f"CLC_TUNING={item}: {msg.decode() if msg else 'rejected'}")
     if os.environ.get("CLC_WINO"):   # Winograd F(2x2, 3x3) for the 3x3 layers of the transforms (tuning key 23): bit 0 forward, bit 1 data gradients, bit 2 the 64-wide kernel
         L.clc_set_tuning(23, int(os.environ["CLC_WINO"]))
     _lib = L

@@ -36,8 +36,9 @@ typedef void* clc_stream_t; /* hipStream_t */
 
 const char* clc_last_error(void);
 int clc_version(void);
-/* A/B switch between kernel variants that compute the same bits (key 0: K-loop timing of the LDS-DMA convolution, 1 or 2;
- * key 1: stream-K filter gradients, 0 or 1); returns the previous value.  Benchmark tooling only. */
+/* A/B switch between kernel variants (key 1: stream-K filter gradients, 0 or 1; the keys are listed in clc_amd/csrc/common.h);
+ * returns the previous value, or -1 for an unknown key.  Keys 0, 2, 3, 12 and 19 are retired: they read as their last defaults
+ * (2, 1, 0, 0, 1), and setting one to any other value returns -1 (clc_last_error says why).  Benchmark tooling only. */
 int clc_set_tuning(int key, int value);
 int clc_get_tuning(int key);
 /* The codec container's kernel-configuration tag (clc_amd/codec.py): which generation of context-model summation orders this build,

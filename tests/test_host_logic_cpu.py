@@ -225,3 +225,55 @@ def test_container_header_errors_and_kernel_tag():
     for bad in (blob2[:27], blob2 + b"!"):
         with pytest.raises(ValueError):
             codec.unpack(bad, strict=False)
+
+
+RETIRED_TUNING_KEYS = {0: 2, 2: 1, 3: 0, 12: 0, 19: 1}   # key -> the last default, the one value it still accepts
+
+
+def test_retired_tuning_keys_accept_only_their_default():
+    from clc_amd import lib
+
+    L = lib.load()
+    for key, default in RETIRED_TUNING_KEYS.items():
+        assert L.clc_get_tuning(key) == default
+        assert L.clc_set_tuning(key, default) == default
+        for other in (default + 1, default - 1, 7):
+            assert L.clc_set_tuning(key, other) < 0, (key, other)
+            assert b"retired" in L.clc_last_error(), (key, L.clc_last_error())
+            assert L.clc_get_tuning(key) == default
+
+
+def test_kernel_config_tag_and_hash_literals():
+    """The codec's kernel-config tag and 32-bit hash of a few reachable tuning states, recorded from the build that still had the
+    retired keys: streams written by either build carry the same values."""
+    from clc_amd import lib
+
+    L = lib.load()
+    cases = (({}, 6, 0xFB105E66), ({14: 1}, 163, 0xD70DE723), ({4: 256}, 230, 0x3F772D66), ({16: 7}, 178, 0xFF1064B2),
+             ({16: 7, 14: 1}, 239, 0xDB0DED6F))
+    for state, tag, h in cases:
+        prev = {k: L.clc_set_tuning(k, v) for k, v in state.items()}
+        try:
+            assert (L.clc_kernel_config_tag(), L.clc_kernel_config_hash()) == (tag, h), state
+        finally:
+            for k, v in prev.items():
+                L.clc_set_tuning(k, v)
+
+
+def test_clc_tuning_env_rejects_unknown_and_retired_settings():
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = "from clc_amd import lib\ntry:\n    lib.load()\nexcept lib.ClcError as e:\n    print('raised:', e)\nelse:\n    print('loaded')\n"
+
+    def run(setting):
+        out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120, cwd=root,
+                             env=dict(os.environ, CLC_TUNING=setting))
+        assert out.returncode == 0, out.stderr[-2000:]
+        return out.stdout.strip()
+
+    retired, unknown = run("12:2"), run("99:1")
+    assert retired.startswith("raised:") and "retired" in retired, retired
+    assert unknown.startswith("raised:") and "out of range" in unknown, unknown
+    assert run("0:2,13:0") == "loaded"          # a retired key at its default, a live key at any value

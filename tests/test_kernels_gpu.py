@@ -53,7 +53,7 @@ CONV_CASES = [
     (1, 64, 64, 128, 64, 3, 1),  # all-taps filter gradient, 1x32 pixel tiles, non-square map
     (2, 96, 32, 16, 160, 3, 1),  # all-taps filter gradient, 2x16 tiles, channel counts that are not tile multiples
     # the tiles that dominate the timed step (selection rules at the end of clc_conv2d, csrc/conv_igemm.hip): per-image map
-    # > 1024 pixels and Cout % 128 == 0 -> conv_igemm_dma_kernel<128,128,4,2,*>; 64 channels -> <128,64,...>; with the fused
+    # > 1024 pixels and Cout % 128 == 0 -> conv_igemm_dma2_kernel<128,128,4,2,*>; 64 channels -> <128,64,...>; with the fused
     # activation derivative (act 1 / 3) the data gradients run on the register-staged conv_igemm_kernel<...,true>; the 3x3
     # filter gradients of these maps run on conv_wgrad_taps(_grouped)_kernel<32>
     (8, 128, 128, 128, 128, 3, 1),

@@ -85,7 +85,6 @@ def main():
                 line += f"  [{sset}] {us:6.1f} us {flops / us / 1e6:5.1f} TF {nbytes / us / 1e3:4.0f} GB/s{'' if same else ' !!DIFF'}"
             print(line, flush=True)
     L.clc_set_tuning(13, 1)
-    L.clc_set_tuning(12, 0)
 
 
 if __name__ == "__main__":

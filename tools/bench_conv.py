@@ -50,13 +50,7 @@ for name, N, Cin, H, W, Cout, ks, s in SHAPES:
     def dgrad(): ops.conv_raw(dy, wt.view(Cin, -1), None, ks=ks, stride=s, pad=ks // 2, transposed=True, out_hw=(H, W))
     def wgrad(): ops.wgrad_raw(x, dy, ks=ks, stride=s, pad=ks // 2, Cout=Cout, Cin=Cin, want_bias=True)
     res = []
-    from clc_amd import lib as _lib
-    variants = [(fwd, "fwd", 2), (dgrad, "dgrad", 2), (wgrad, "wgrad", None)]
-    if os.environ.get("AB", "0") == "1":   # A/B of the DMA K-loop variants in ONE process (tuning key 0)
-        variants = [(fwd, "fwd.v1", 1), (fwd, "fwd.v2", 2), (dgrad, "dgrad.v1", 1), (dgrad, "dgrad.v2", 2), (wgrad, "wgrad", None)]
-    for fn, label, tune in variants:
-        if tune is not None:
-            _lib.load().clc_set_tuning(0, tune)
+    for fn, label in ((fwd, "fwd"), (dgrad, "dgrad"), (wgrad, "wgrad")):
         for _ in range(3): fn()
         torch.cuda.synchronize()
         # capture the launches in a hipGraph so the number is GPU time, not Python/ctypes launch overhead

@@ -1,5 +1,5 @@
 """Kernel-level look at the LayerNorm form of the fused Swin-block MLP (csrc/fused_mlp.hip): forward + backward of `x + mlp(ln2(x))` at
-8 x 128 x 128, LN inside the launches vs separate LayerNorm launches, and the backward kernel's timing ablations (CLC_TUNE_ABLATE; wrong results).
+8 x 128 x 128, LN inside the launches vs separate LayerNorm launches.
 Times are hipGraph replays (launches back to back, as in the step): an eager kernel trace of the same launches overstates every phase that the
 graph's neighbours overlap (csrc/fused_mlp.hip).   python tools/bench_mlp_ln.py [reps]"""
 import os
@@ -8,7 +8,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
-from clc_amd import layers, lib, ops
+from clc_amd import layers, ops
 
 CL = torch.channels_last
 
@@ -17,7 +17,6 @@ def main():
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 12
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
-    L = lib.load()
     fc1, fc2, ln = layers.Linear(64, 256).to(dev), layers.Linear(256, 64).to(dev), layers.LayerNorm(64).to(dev)
     prms = list(fc1.parameters()) + list(fc2.parameters()) + list(ln.parameters())
     N, H, W = 8, 128, 128
@@ -36,9 +35,7 @@ def main():
         for prm in prms:
             prm.grad = None
 
-    legs = [("separate", False, 0, None), ("ln-fused", True, 0, None), ("abl1", True, 1, None), ("abl4", True, 4, None), ("abl5", True, 5, None)]
-    for label, fused, abl, stag in legs:
-        prev = L.clc_set_tuning(12, abl)
+    for label, fused in (("separate", False), ("ln-fused", True)):
         for i in range(nbuf):
             step(i, fused)
         torch.cuda.synchronize()
@@ -46,7 +43,6 @@ def main():
         with torch.cuda.graph(g):
             for r in range(reps):
                 step(r % nbuf, fused)
-        L.clc_set_tuning(12, prev)
         g.replay()
         torch.cuda.synchronize()
         ts = []
