@@ -1,8 +1,8 @@
 """Import-surface shim: lets the reference's scripts resolve every name they import to this package, unmodified.
 
 `train_CLC.py:17-26` and `eval_CLC.py:1-17` import `models` (TCM, CLC), `compressai.datasets.ImageFolder`,
-`compressai.zoo.models`, `pytorch_msssim.ms_ssim`; `models/CLC_run.py:1-20` (if it is imported at all) imports
-`compressai.{entropy_models,ans,models,layers}` and `timm.models.layers`.  `install()` registers modules of those names in
+`compressai.zoo.models`, `pytorch_msssim.ms_ssim` (`ssim`, `SSIM`, `MS_SSIM` are there too, for other code);
+`models/CLC_run.py:1-20` (if it is imported at all) imports `compressai.{entropy_models,ans,models,layers}` and `timm.models.layers`.  `install()` registers modules of those names in
 `sys.modules`, each backed by the HIP implementation of this package, so
 
     python -c "import clc_amd.compat as c; c.install(); import runpy; runpy.run_path('train_CLC.py', run_name='__main__')" ...
@@ -64,7 +64,7 @@ def install(force: bool = False):
     """Register the shim modules; returns the list of module names that now resolve to this package."""
     import torch
 
-    from . import ans, entropy_models, layers, models, train
+    from . import ans, entropy_models, layers, models, ssim, train
     from .models import clc as _clc
 
     done = []
@@ -105,5 +105,6 @@ def install(force: bool = False):
         sys.modules["timm"].models = tm
         tm.layers = tl
         done += ["timm.models", "timm.models.layers"]
-    put("pytorch_msssim", ms_ssim=train.ms_ssim)   # train_CLC.py:23,33-34 / eval_CLC.py:16: ms_ssim(a, b, data_range=1.)
+    # train_CLC.py:23,33-34 / eval_CLC.py:16: ms_ssim(a, b, data_range=1.); ssim / SSIM / MS_SSIM keep pytorch_msssim's data_range=255
+    put("pytorch_msssim", ms_ssim=train.ms_ssim, ssim=ssim.ssim, SSIM=ssim.SSIM, MS_SSIM=ssim.MS_SSIM)
     return done

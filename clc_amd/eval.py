@@ -12,7 +12,7 @@ from typing import Iterable, List, Sequence, Tuple
 import torch
 import torch.nn.functional as F
 
-from . import ops
+from . import ops, ssim
 
 
 def pad(x, p: int = 128):
@@ -34,6 +34,11 @@ def compute_psnr(a, b) -> float:
     return -10 * math.log10(mse)
 
 
+def compute_msssim(a, b) -> float:
+    """MS-SSIM in dB, the reference's form (eval_CLC.py:137-138): -10 log10(1 - ms_ssim(a, b, data_range=1))."""
+    return -10 * math.log10(1 - ssim.ms_ssim(a.float(), b.float(), data_range=1.0).item())
+
+
 def compute_bpp(out_net) -> float:
     size = out_net["x_hat"].size()
     num_pixels = size[0] * size[2] * size[3]
@@ -41,9 +46,11 @@ def compute_bpp(out_net) -> float:
 
 
 @torch.no_grad()
-def evaluate(net, samples: Iterable[Tuple[torch.Tensor, Sequence[torch.Tensor]]], p: int = 128, device="cuda", engine=None):
+def evaluate(net, samples: Iterable[Tuple[torch.Tensor, Sequence[torch.Tensor]]], p: int = 128, device="cuda", engine=None, ms_ssim=False):
     """samples: iterable of (image [3,h,w] in [0,1], [reference images]). Returns per-image rows and averages.
-    engine: a clc_amd.codec.CodecEngine over `net` (graph-captured codec, same bitstreams); default: net.compress / net.decompress."""
+    engine: a clc_amd.codec.CodecEngine over `net` (graph-captured codec, same bitstreams); default: net.compress / net.decompress.
+    ms_ssim: also score each cropped reconstruction (outside the timed region): rows gain "ms_ssim" and "ms_ssim_db"
+    (compute_msssim), the result "avg_ms_ssim_db"."""
     net.eval()
     net.update()
     rows, t_total = [], 0.0
@@ -67,8 +74,14 @@ def evaluate(net, samples: Iterable[Tuple[torch.Tensor, Sequence[torch.Tensor]]]
         num_pixels = x.size(0) * x.size(2) * x.size(3)
         bitrate = sum(len(s[0]) for s in enc["strings"]) * 8.0 / num_pixels
         rows.append({"bpp": bitrate, "psnr": compute_psnr(x, x_hat)})
+        if ms_ssim:
+            v = ssim.ms_ssim(x.float(), x_hat.float(), data_range=1.0).item()
+            rows[-1].update(ms_ssim=v, ms_ssim_db=-10 * math.log10(1 - v))
     n = max(1, len(rows))
-    return {"rows": rows, "avg_bpp": sum(r["bpp"] for r in rows) / n, "avg_psnr": sum(r["psnr"] for r in rows) / n, "avg_time_s": t_total / n}
+    res = {"rows": rows, "avg_bpp": sum(r["bpp"] for r in rows) / n, "avg_psnr": sum(r["psnr"] for r in rows) / n, "avg_time_s": t_total / n}
+    if ms_ssim:
+        res["avg_ms_ssim_db"] = sum(r["ms_ssim_db"] for r in rows) / n
+    return res
 
 
 # ----------------------------------------------------------------------------------------------- checkpoints / RD sweep (§8(f)-3)

@@ -87,6 +87,17 @@ class ReduceEntry(C.Structure):
     _fields_ = [("partial", fp), ("nblocks", C.c_int), ("n", C.c_int), ("out0", fp), ("out1", fp), ("split", C.c_int), ("accumulate", C.c_int)]
 
 
+SSIM_MAX_WIN = 15
+
+
+class SsimDesc(C.Structure):
+    _fields_ = [("x", fp), ("ldx", C.c_int), ("y", fp), ("ldy", C.c_int),
+                ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int),
+                ("win_size", C.c_int), ("win", C.c_float * SSIM_MAX_WIN), ("C1", C.c_float), ("C2", C.c_float),
+                ("pad_h", C.c_int), ("pad_w", C.c_int),
+                ("dx", fp), ("lddx", C.c_int), ("dy", fp), ("lddy", C.c_int), ("dnext_x", fp), ("dnext_y", fp)]
+
+
 class ParamEntry(C.Structure):
     _fields_ = [("p", fp), ("g", fp), ("m", fp), ("v", fp), ("n", C.c_long)]
 
@@ -177,6 +188,11 @@ SIGNATURES = {
     "clc_ssim_scale_fwd": (_i, [fp, _i, fp, _i, _i, _i, _i, _i, _f, fp, fp, _sz, fp]),
     "clc_ssim_scale_bwd": (_i, [fp, _i, fp, _i, _i, _i, _i, _i, _f, fp, fp, fp, _i, fp, _sz, fp]),
     "clc_avgpool2": (_i, [fp, _i, fp, _i, _i, _i, _i, fp]),
+    "clc_ssim_window": (_i, [_i, _f, C.POINTER(C.c_float)]),
+    "clc_ssim_desc_workspace_bytes": (_sz, [C.POINTER(SsimDesc)]),
+    "clc_ssim_desc_fwd": (_i, [C.POINTER(SsimDesc), fp, fp, _sz, fp]),
+    "clc_ssim_desc_bwd": (_i, [C.POINTER(SsimDesc), fp, fp, _sz, fp]),
+    "clc_avgpool2_pad": (_i, [fp, _i, fp, _i, _i, _i, _i, _i, _i, fp]),
     "clc_residual_unit_fwd": (_i, [C.POINTER(RUDesc), fp]),
     "clc_residual_unit_dgrad": (_i, [C.POINTER(RUDesc), fp]),
     "clc_mlp_fwd": (_i, [C.POINTER(MlpDesc), fp]),

@@ -12,6 +12,7 @@ There is no CPU path: a CPU tensor raises.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 import os
 
@@ -2349,61 +2350,131 @@ def rd_loss_mse(lik_y, lik_z, x_hat, target, lmbda, num_pixels):
 # ------------------------------------------------------------------------------------- MS-SSIM
 
 
-class _MsSsimMeansFn(Function):
-    """Per-scale (mean cs, mean ssim) of x vs y over `levels` dyadic scales -> [levels, B*C, 2]; gradient flows to x."""
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+
+
+@functools.lru_cache(maxsize=None)
+def ssim_window(win_size=11, win_sigma=1.5):
+    """pytorch_msssim's _fspecial_gauss_1d(win_size, win_sigma) as fp32 taps, built on the host by clc_ssim_window (no GPU).
+    (11, 1.5) is bit for bit the window clc_ssim_init uploads."""
+    if win_size % 2 != 1:
+        raise ValueError("Window size should be odd.")
+    if not 3 <= win_size <= _lib.SSIM_MAX_WIN:
+        raise ValueError(f"win_size {win_size}: the HIP SSIM kernels take odd windows of 3 to {_lib.SSIM_MAX_WIN} taps")
+    buf = (C.c_float * win_size)()
+    _lib.check(_lib.load().clc_ssim_window(win_size, float(win_sigma), buf), "clc_ssim_window")
+    return tuple(buf)
+
+
+def ssim_window_taps(win_size=11, win_sigma=1.5, win=None):
+    """The 1-D window as a tuple of fp32 taps: ssim_window(win_size, win_sigma), or pytorch_msssim's `win` tensor ([C, 1, 1, ws] or
+    anything whose last dimension holds the taps; every channel must carry the same window).  A `win` on the GPU is read back
+    to the host, so pass it on the CPU (as the SSIM / MS_SSIM modules keep it) where the call is to be captured."""
+    if win is None:
+        return ssim_window(int(win_size), float(win_sigma))
+    ws = int(win.shape[-1])
+    if ws % 2 != 1:
+        raise ValueError("Window size should be odd.")
+    if not 3 <= ws <= _lib.SSIM_MAX_WIN:
+        raise ValueError(f"win_size {ws}: the HIP SSIM kernels take odd windows of 3 to {_lib.SSIM_MAX_WIN} taps")
+    rows = win.detach().to("cpu", torch.float32).reshape(-1, ws)
+    if not bool((rows == rows[0]).all()):
+        raise ValueError("win: every channel must use the same window")
+    return tuple(rows[0].tolist())
+
+
+def _f32(v):
+    return C.c_float(v).value
+
+
+def ssim_constants(data_range, K=(0.01, 0.03)):
+    """(C1, C2) = ((K1 * data_range)^2, (K2 * data_range)^2) in fp32 arithmetic, as clc_ssim_scale_fwd forms them.  (A product of
+    two fp32 values is exact in a double, so rounding it once to fp32 is the fp32 product.)"""
+    dr = _f32(data_range)
+    k1, k2 = _f32(_f32(K[0]) * dr), _f32(_f32(K[1]) * dr)
+    return _f32(k1 * k1), _f32(k2 * k2)
+
+
+def _ssim_desc(xc, yc, taps, C1, C2):
+    B, Cc, h, w = xc.shape
+    d = _lib.SsimDesc()
+    d.x, d.ldx, d.y, d.ldy = xc.data_ptr(), Cc, yc.data_ptr(), Cc
+    d.B, d.H, d.W, d.C = B, h, w, Cc
+    d.win_size = len(taps)
+    d.win[:len(taps)] = taps
+    d.C1, d.C2 = C1, C2
+    d.pad_h, d.pad_w = h % 2, w % 2
+    return d
+
+
+class _SsimMeansFn(Function):
+    """Per-scale (mean cs, mean ssim) of x vs y over `levels` scales -> [levels, B*C, 2].  Between scales both images go through
+    avg_pool2d(2, padding=(H % 2, W % 2)), as pytorch_msssim.  Gradients flow to x and / or y, whichever requires one."""
 
     @staticmethod
-    def forward(ctx, x, y, levels, data_range):
+    def forward(ctx, x, y, levels, taps, C1, C2):
         x, y = dense(x), dense(y)
         B, Cc, H, W = x.shape
         L = _L()
-        _lib.check(L.clc_ssim_init(), "clc_ssim_init")
         xs, ys = [x], [y]
         means = torch.empty((levels, B * Cc, 2), device=x.device, dtype=torch.float32)
         for s in range(levels):
             xc, yc = xs[-1], ys[-1]
             h, w = xc.shape[2], xc.shape[3]
-            nbytes = L.clc_ssim_workspace_bytes(B, h, w, Cc)
+            d = _ssim_desc(xc, yc, taps, C1, C2)
+            nbytes = L.clc_ssim_desc_workspace_bytes(C.byref(d))
             ws = torch.empty((nbytes + 3) // 4, device=x.device, dtype=torch.float32)
-            _lib.check(L.clc_ssim_scale_fwd(xc.data_ptr(), Cc, yc.data_ptr(), Cc, B, h, w, Cc, float(data_range), means[s].data_ptr(),
-                                            ws.data_ptr(), nbytes, _stream()), "clc_ssim_scale_fwd")
+            _lib.check(L.clc_ssim_desc_fwd(C.byref(d), means[s].data_ptr(), ws.data_ptr(), nbytes, _stream()), "clc_ssim_desc_fwd")
             if s + 1 < levels:
-                if h % 2 or w % 2:
-                    raise _lib.ClcError("ms_ssim: image sides must stay even across the scales (e.g. multiples of 16)")
-                xn, yn = new_act(B, Cc, h // 2, w // 2, x), new_act(B, Cc, h // 2, w // 2, x)
-                _lib.check(L.clc_avgpool2(xc.data_ptr(), Cc, xn.data_ptr(), B, h, w, Cc, _stream()), "clc_avgpool2")
-                _lib.check(L.clc_avgpool2(yc.data_ptr(), Cc, yn.data_ptr(), B, h, w, Cc, _stream()), "clc_avgpool2")
+                xn, yn = new_act(B, Cc, (h + 1) // 2, (w + 1) // 2, x), new_act(B, Cc, (h + 1) // 2, (w + 1) // 2, x)
+                _lib.check(L.clc_avgpool2_pad(xc.data_ptr(), Cc, xn.data_ptr(), B, h, w, Cc, h % 2, w % 2, _stream()), "clc_avgpool2_pad")
+                _lib.check(L.clc_avgpool2_pad(yc.data_ptr(), Cc, yn.data_ptr(), B, h, w, Cc, h % 2, w % 2, _stream()), "clc_avgpool2_pad")
                 xs.append(xn)
                 ys.append(yn)
-        ctx.data_range = float(data_range)
+        ctx.consts = (taps, C1, C2)
         ctx.save_for_backward(*xs, *ys)
         return means
 
     @staticmethod
     def backward(ctx, g):
+        need_x, need_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         saved = ctx.saved_tensors
         levels = len(saved) // 2
         xs, ys = saved[:levels], saved[levels:]
         g = g.contiguous()
         L = _L()
-        dnext = None
+        dnx = dny = None
         for s in reversed(range(levels)):
             xc, yc = xs[s], ys[s]
             B, Cc, h, w = xc.shape
-            nbytes = L.clc_ssim_workspace_bytes(B, h, w, Cc)
+            d = _ssim_desc(xc, yc, *ctx.consts)
+            dx = new_act(B, Cc, h, w, xc) if need_x else None
+            dy = new_act(B, Cc, h, w, xc) if need_y else None
+            if dx is not None:
+                d.dx, d.lddx, d.dnext_x = dx.data_ptr(), Cc, dnx.data_ptr() if dnx is not None else None
+            if dy is not None:
+                d.dy, d.lddy, d.dnext_y = dy.data_ptr(), Cc, dny.data_ptr() if dny is not None else None
+            nbytes = L.clc_ssim_desc_workspace_bytes(C.byref(d))
             ws = torch.empty((nbytes + 3) // 4, device=xc.device, dtype=torch.float32)
-            dx = new_act(B, Cc, h, w, xc)
-            _lib.check(L.clc_ssim_scale_bwd(xc.data_ptr(), Cc, yc.data_ptr(), Cc, B, h, w, Cc, ctx.data_range, g[s].data_ptr(),
-                                            dnext.data_ptr() if dnext is not None else None, dx.data_ptr(), Cc, ws.data_ptr(), nbytes, _stream()), "clc_ssim_scale_bwd")
-            dnext = dx
-        return dnext, None, None, None
+            _lib.check(L.clc_ssim_desc_bwd(C.byref(d), g[s].data_ptr(), ws.data_ptr(), nbytes, _stream()), "clc_ssim_desc_bwd")
+            dnx, dny = dx, dy
+        return dnx, dny, None, None, None, None
 
 
-def ms_ssim(x, y, data_range=1.0, weights=(0.0448, 0.2856, 0.3001, 0.2363, 0.1333)):
-    """pytorch_msssim.ms_ssim(X, Y, data_range, size_average=True) — the windowed statistics run in HIP, the final
-    [5, B, C] product of powers is a handful of scalar-sized torch ops."""
+def ssim_stats(x, y, levels, taps, data_range, K=(0.01, 0.03)):
+    """[levels, B, C, 2]: per scale, image and channel the (mean cs, mean ssim) of x against y, differentiable in both."""
+    if x.dim() != 4 or x.shape != y.shape:
+        raise ValueError(f"ssim: x {tuple(x.shape)} and y {tuple(y.shape)} must be 4-D tensors of one shape")
+    _require_gpu(x, "ssim")
+    _require_gpu(y, "ssim")
     B, Cc = x.shape[0], x.shape[1]
-    means = _MsSsimMeansFn.apply(x, y, len(weights), float(data_range)).view(len(weights), B, Cc, 2)
+    C1, C2 = ssim_constants(data_range, K)
+    return _SsimMeansFn.apply(x, y, levels, tuple(taps), C1, C2).view(levels, B, Cc, 2)
+
+
+def ms_ssim_combine(means, weights, size_average=True):
+    """pytorch_msssim's product over scales of relu(cs) ** w (relu(ssim) ** w at the coarsest), averaged over channels (and
+    images when size_average)."""
     # exponents are host scalars: no host->device tensor is built here, so the loss can be captured into a hipGraph
     # (TrainEngine(loss_type='ms_ssim') = the reference's --type ms-ssim mode)
     L = len(weights)
@@ -2411,4 +2482,13 @@ def ms_ssim(x, y, data_range=1.0, weights=(0.0448, 0.2856, 0.3001, 0.2363, 0.133
     for s in range(L):
         v = torch.relu(means[s, :, :, 0 if s + 1 < L else 1]) ** float(weights[s])
         out = v if out is None else out * v
-    return out.mean()
+    return out.mean() if size_average else out.mean(1)
+
+
+def ms_ssim(x, y, data_range=1.0, weights=MS_SSIM_WEIGHTS, size_average=True, win_size=11, win_sigma=1.5, win=None, K=(0.01, 0.03)):
+    """pytorch_msssim.ms_ssim(X, Y, ...) — the windowed statistics and the pooling run in HIP, the final [levels, B, C] product of
+    powers is a handful of small torch ops.  data_range defaults to 1.0 here (pytorch_msssim: 255); weights=None means the
+    5-scale default.  Unlike clc_amd.ssim.ms_ssim there is no minimum-size rule beyond each scale holding one window."""
+    weights = MS_SSIM_WEIGHTS if weights is None else weights
+    taps = ssim_window_taps(win_size, win_sigma, win)
+    return ms_ssim_combine(ssim_stats(x, y, len(weights), taps, data_range, K), weights, size_average)

@@ -33,9 +33,11 @@ from . import ops
 FUSED_RD_LOSS = os.environ.get("CLC_FUSED_RD_LOSS", "1") != "0"
 
 
-def ms_ssim(X, Y, data_range=1.0):
-    """pytorch_msssim.ms_ssim semantics (train_CLC.py:33-34) on the HIP MS-SSIM kernels (clc_ssim_scale_fwd/bwd)."""
-    return ops.ms_ssim(X, Y.float().contiguous(memory_format=ops.CL), data_range=data_range)
+def ms_ssim(X, Y, data_range=1.0, size_average=True, win_size=11, win_sigma=1.5, win=None, weights=None, K=(0.01, 0.03)):
+    """pytorch_msssim.ms_ssim semantics (train_CLC.py:33-34) on the HIP SSIM kernels (clc_ssim_desc_fwd/bwd); the keywords are
+    pytorch_msssim's, but data_range defaults to 1.0 (pytorch_msssim: 255), the value every call of the reference passes."""
+    return ops.ms_ssim(X, Y.float().contiguous(memory_format=ops.CL), data_range=data_range, weights=weights, size_average=size_average,
+                       win_size=win_size, win_sigma=win_sigma, win=win, K=K)
 
 
 class RateDistortionLoss(nn.Module):

@@ -421,6 +421,37 @@ int clc_ssim_scale_bwd(const float* x, int ldx, const float* y, int ldy, int B, 
                        clc_stream_t stream);
 int clc_avgpool2(const float* x, int ldx, float* out, int B, int H, int W, int C, clc_stream_t stream);
 
+/* ---- SSIM / MS-SSIM, descriptor form (pytorch_msssim.ssim / ms_ssim on any image size, window and input gradient) ---- *
+ * The window travels by value in the descriptor (no init call, no __constant__ upload: capturable as it stands).
+ * One scale at a time, same means layout as clc_ssim_scale_fwd: means[bc][0] = mean cs, means[bc][1] = mean ssim over the
+ * (H - win_size + 1) x (W - win_size + 1) valid windows.  bwd writes dx and / or dy (a NULL output is not computed):
+ * d(sum_bc g_means[bc][0]*mean_cs + g_means[bc][1]*mean_ssim)/d{x,y} + 0.25 * the gradient arriving through the 2x2 average pool
+ * from the next coarser scale (dnext_x / dnext_y, or NULL): input row i reads coarse row (i + pad_h) / 2, columns likewise.
+ * With the 11-tap sigma-1.5 window of clc_ssim_window, C1 / C2 as clc_ssim_scale_fwd forms them, and dy == NULL, the results
+ * equal clc_ssim_scale_fwd / clc_ssim_scale_bwd bit for bit.
+ * clc_avgpool2_pad: F.avg_pool2d(x, 2, padding=(pad_h, pad_w)) with zero padding counted (divisor 4); out is dense
+ * [B, (H + pad_h) / 2, (W + pad_w) / 2, C].  pad_h / pad_w must be H % 2 / W % 2 (pytorch_msssim's padding) here and in the descriptor.
+ * clc_ssim_window (HOST, no GPU): pytorch_msssim's _fspecial_gauss_1d(win_size, sigma) in fp32. */
+#define CLC_SSIM_MAX_WIN 15
+typedef struct {
+  const float* x; int ldx;
+  const float* y; int ldy;
+  int B, H, W, C;
+  int win_size;                  /* odd, 3 .. CLC_SSIM_MAX_WIN */
+  float win[CLC_SSIM_MAX_WIN];   /* taps [0, win_size), applied along both axes */
+  float C1, C2;                  /* (K1 * data_range)^2, (K2 * data_range)^2 */
+  int pad_h, pad_w;              /* pooling pads toward the next coarser scale */
+  float* dx; int lddx;           /* bwd outputs (NULL: not wanted; at least one is set) */
+  float* dy; int lddy;
+  const float* dnext_x;          /* bwd: dense [B, (H + pad_h) / 2, (W + pad_w) / 2, C] or NULL */
+  const float* dnext_y;
+} clc_ssim_desc;
+int clc_ssim_window(int win_size, float sigma, float* taps);
+size_t clc_ssim_desc_workspace_bytes(const clc_ssim_desc* d);
+int clc_ssim_desc_fwd(const clc_ssim_desc* d, float* means, void* ws, size_t ws_bytes, clc_stream_t stream);
+int clc_ssim_desc_bwd(const clc_ssim_desc* d, const float* g_means, void* ws, size_t ws_bytes, clc_stream_t stream);
+int clc_avgpool2_pad(const float* x, int ldx, float* out, int B, int H, int W, int C, int pad_h, int pad_w, clc_stream_t stream);
+
 /* ---- optimizer ------------------------------------------------------------------------ *
  * Multi-tensor AdamW + grad-norm clip + nan_to_num (train_CLC.py:164-179) over a flat
  * table of (param, grad, m, v, numel) entries resident on the device. */
