@@ -151,3 +151,72 @@ def test_reference_surface_single_image_codec_rides_on_captured_graphs(dev, kind
         assert a3["strings"] == a2["strings"]
     finally:
         mclc.CODEC_GRAPH = old
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,R,H,W,batches", [("clc", 1, 384, 384, (1, 2, 3)), ("tcm", 0, 384, 384, (1, 2, 3)), ("clc", 1, 384, 640, (1, 2))])
+def test_codec_batch_invariance_across_the_slice_route_flip(dev, kind, R, H, W, batches, monkeypatch):
+    """An image's bits do not depend on its batch, also where the batch decides the slice nets' route: they pair only when B * h * w of the
+    latent is a multiple of 128 (models/clc.py `_slice_params`), so at 384x384 (576 latent rows per image) B = 1 and 3 run them unpaired and
+    B = 2 paired; 384x640 (960 rows) flips between B = 1 and 2.  Streams encoded at any B are byte-identical to the eager single-image ones;
+    the batch-2 streams decode on one image through model.decompress, the single-image ones at batch 2 through the engine, and every
+    decoded image equals the encoder-side reconstruction bit for bit."""
+    from clc_amd import codec, ops
+    from clc_amd import models as pm
+    from clc_amd.recipe import apply_weight_recipe, synthetic_image
+
+    paired = [0]
+    real = ops.whole_and_first_half
+
+    def counted(x):   # (only the paired slice route calls it, once per slice)
+        paired[0] += 1
+        return real(x)
+
+    monkeypatch.setattr(ops, "whole_and_first_half", counted)
+    m = pm.CLC(N=64, num_ref_frames=R) if kind == "clc" else pm.TCM(N=64)
+    apply_weight_recipe(m, 0)
+    m = m.to(dev).eval()
+    m.update(force=True)
+    n = max(batches)
+    x = torch.cat([synthetic_image(1, H, W, 300 + 7 * i, smooth=True) for i in range(n)]).to(dev)
+    refs = [torch.cat([synthetic_image(1, H, W, 400 + 7 * i + j, smooth=True) for i in range(n)]).to(dev) for j in range(R)]
+    pairs_at = lambda B: B * (H // 16) * (W // 16) % 128 == 0
+    assert not pairs_at(1) and pairs_at(2) and (3 not in batches or not pairs_at(3))
+    ref_of = lambda idx: [r[idx] for r in refs] if R else None
+    want, recon = [], []
+    for i in range(n):
+        want.append(m._compress_eager(x[i:i + 1], ref_of(slice(i, i + 1))))
+        with torch.no_grad():
+            recon.append(m(x[i:i + 1], ref_of(slice(i, i + 1)))["x_hat"].clamp(0, 1))
+    assert paired[0] == 0, "expected the unpaired slice route for one image"
+    eng = codec.CodecEngine(m, threads=2, use_graph=True)
+    enc2 = {}
+    for B in batches:
+        paired[0] = 0
+        for s in range(0, n, B):
+            idx = [(s + k) % n for k in range(B)]
+            outs = eng.compress(x[idx], ref_of(idx))
+            for k, i in enumerate(idx):
+                assert outs[k]["strings"][0] == want[i]["strings"][0], f"B={B}: image {i}'s y stream differs from the single-image one"
+                assert outs[k]["strings"][1] == want[i]["strings"][1], f"B={B}: image {i}'s z stream differs from the single-image one"
+                assert tuple(outs[k]["shape"]) == tuple(want[i]["shape"])
+                if B == 2:
+                    enc2[i] = outs[k]
+        # (the slice nets run in Python while the plan is captured, and not at all when it replays)
+        assert (paired[0] > 0 and paired[0] % 5 == 0) if pairs_at(B) else paired[0] == 0, (B, paired[0])
+    assert sorted(enc2) == list(range(n))
+    # batch-2 streams, decoded one image at a time (unpaired)
+    paired[0] = 0
+    for i in range(n):
+        o = enc2[i]
+        dec = m.decompress(o["strings"], o["shape"], ref_of(slice(i, i + 1))) if R else m.decompress(o["strings"], o["shape"])
+        assert torch.equal(dec["x_hat"], recon[i]), f"image {i}: batch-2 stream decoded alone != encoder-side reconstruction"
+    assert paired[0] == 0
+    # single-image streams, decoded at batch 2 (paired)
+    for s in range(0, n, 2):
+        idx = [(s + k) % n for k in range(2)]
+        x_hat = eng.decompress([want[i] for i in idx], ref_of(idx))
+        for k, i in enumerate(idx):
+            assert torch.equal(x_hat[k:k + 1], recon[i]), f"image {i}: single-image stream decoded at batch 2 != encoder-side reconstruction"
+    assert paired[0] > 0 and paired[0] % 5 == 0, paired[0]
+    eng.close()

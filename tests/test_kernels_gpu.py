@@ -165,7 +165,9 @@ def test_conv_fwd_bwd(dev, case, act):
         _close(xd.grad, xr.grad, 1e-4, "conv dgrad")
 
 
-@pytest.mark.parametrize("case", [(8, 64, 16, 16, 64, 3), (8, 128, 16, 16, 64, 1), (2, 448, 16, 16, 224, 3), (2, 64, 64, 64, 128, 3), (4, 64, 32, 32, 64, 1)])
+# (4, 320, 24, 24, 224, 3): the first layer of the paired slice nets of a 384x384 image at batch 2 (1152-row halves on the 64x64 tiles)
+@pytest.mark.parametrize("case", [(8, 64, 16, 16, 64, 3), (8, 128, 16, 16, 64, 1), (2, 448, 16, 16, 224, 3), (2, 64, 64, 64, 128, 3), (4, 64, 32, 32, 64, 1),
+                                  (4, 320, 24, 24, 224, 3)])
 def test_conv_paired_filters(dev, case, request):
     """w2/bias2: the second half of the batch on a second filter set in the same launch == two separate launches, bit
     for bit (forward, data gradient, both filter gradients), for both kernel families."""
@@ -397,6 +399,96 @@ def test_window_attention(dev, cfg, shift):
     y.backward(_dev(gy, dev))
     _close(qd.grad, qkv.grad, 1e-4, "attn dqkv")
     _close(rd.grad, rb.grad, 1e-4, "attn drelbias")
+
+
+
+# 3x3 window grids (the per-image maps of a 384x384 / 384x640 image, which a 128-multiple pad with an odd block count gives) at batch 1 and 3:
+# (C, heads, ws, H, W) = slice SWAtten (inter_dim 128, head_dim 16; the NH-per-workgroup forward kernel), the hyper ConvTransBlocks at N = 64
+# and N = 128, and the 24x40 latent of 384x640
+@pytest.mark.parametrize("cfg", [(128, 8, 8, 24, 24), (64, 2, 4, 12, 12), (128, 4, 4, 12, 12), (128, 8, 8, 24, 40)])
+@pytest.mark.parametrize("N", [1, 3])
+@pytest.mark.parametrize("shift", [False, True])
+def test_window_attention_odd_grids_vs_fp64(dev, cfg, N, shift):
+    from clc_amd import ops
+
+    C, heads, ws, H, W = cfg
+    qkv = _rand((N, 3 * C, H, W), 21 + N)
+    rb = _rand((heads, 2 * ws - 1, 2 * ws - 1), 22, 0.5)
+    gy = _rand((N, C, H, W), 23)
+    qr, rr = qkv.double().requires_grad_(), rb.double().requires_grad_()
+    ref = _ref_wmsa_core(qr, rr, heads, ws, shift)
+    ref.backward(gy.double())
+    qd, rd = _dev(qkv, dev, grad=True), _dev(rb, dev, grad=True)
+    y = ops.window_attention(qd, rd, heads, ws, shift)
+    _close(y, ref, 2e-5, "attn fwd")
+    y.backward(_dev(gy, dev))
+    _close(qd.grad, qr.grad, 1e-4, "attn dqkv")
+    _close(rd.grad, rr.grad, 1e-4, "attn drelbias")
+
+
+def _is_64x64_tile(v):
+    """kernel-variant id of clc_conv2d's 64x64 tiles on 4 waves (conv_igemm_kernel / conv_igemm_dma2_kernel<64, 64, 2, 2, ...>)"""
+    return (v >> 20) in (1, 4) and (v & 0xFFFFF) == (2 << 16) | (2 << 12) | (64 << 3) | (64 >> 5)
+
+
+@pytest.mark.parametrize("cin", [320, 576])
+@pytest.mark.parametrize("act", [0, 3])
+def test_unpaired_slice_net_convs_at_24x24_vs_fp64(dev, cin, act):
+    """The slice nets' 3x3 layers (cin -> 224 -> 128 -> 64) as the unpaired route launches them for one 384x384 image: a 24x24 map, 576 rows
+    (not a multiple of 128, so no filter-set pairing), above the split-K family's 256-pixel threshold.  Forward, data and filter gradients
+    against fp64.  An eval (no_grad) forward must take the 64x64 tiles — or, for the few-channel layers that tuning keys 4 / 5 route there
+    by the per-image map, the split-K family; a recorded one may take the Winograd kernel only where wino_ok says so, and otherwise gives
+    the eval forward's bits."""
+    from clc_amd import ops
+
+    H = W = 24
+    L = ops._L()
+    splitk_pix, splitk_maxc = max(L.clc_get_tuning(4), 256), L.clc_get_tuning(5)
+
+    def family_ok(v, cout):   # clc_conv2d's rule for a per-image map of 257..1024 pixels (csrc/conv_igemm.hip)
+        if H * W <= splitk_pix and cout <= splitk_maxc:
+            return v >> 20 == 3
+        return _is_64x64_tile(v)
+
+    for li, (ci, co) in enumerate(((cin, 224), (224, 128), (128, 64))):
+        seed = 100 * li + cin + act
+        x = _rand((1, ci, H, W), seed)
+        w = _rand((co, ci, 3, 3), seed + 1, (1.0 / (ci * 9)) ** 0.5)
+        b = _rand((co,), seed + 2, 0.1)
+        gy = _rand((1, co, H, W), seed + 3)
+        xr, wr, br = (t.double().requires_grad_() for t in (x, w, b))
+        ref = F.conv2d(xr, wr, br, padding=1)
+        ref = F.gelu(ref) if act == 3 else ref
+        ref.backward(gy.double())
+        xd, wd, bd = _dev(x, dev, grad=True), _dev(w, dev, grad=True), _dev(b, dev, grad=True)
+        ops.PROFILE = []
+        try:
+            with torch.no_grad():
+                y_eval = ops.conv2d(xd, wd, bd, act=act)
+            y = ops.conv2d(xd, wd, bd, act=act)
+            n_fwd = len(ops.PROFILE)
+            y.backward(_dev(gy, dev))
+            ops.flush_wgrads()
+            torch.cuda.synchronize()
+            recs = list(ops.PROFILE)
+        finally:
+            ops.PROFILE = None
+        what = f"{ci}->{co} act {act}"
+        fwd = [r.variant for r in recs[:n_fwd] if r.fam == "conv_igemm"]
+        dgrad = [r.variant for r in recs[n_fwd:] if r.fam == "conv_igemm"]
+        assert len(fwd) == 2 and len(dgrad) == 1, (what, [(r.fam, hex(r.variant)) for r in recs])
+        assert family_ok(fwd[0], co), (what, "eval forward", hex(fwd[0]))
+        if ops.wino_ok(1, H, W, ci, co, 3, 1):
+            assert fwd[1] >> 20 == 13, (what, "recorded forward", hex(fwd[1]))
+        else:
+            assert family_ok(fwd[1], co), (what, "recorded forward", hex(fwd[1]))
+            assert torch.equal(y.detach(), y_eval), what
+        assert family_ok(dgrad[0], ci), (what, "data gradient", hex(dgrad[0]))
+        _close(y_eval, ref, 2e-5, f"{what} eval fwd")
+        _close(y, ref, 2e-5, f"{what} fwd")
+        _close(xd.grad, xr.grad, 1e-4, f"{what} dgrad")
+        _close(wd.grad, wr.grad, 1e-4, f"{what} wgrad")
+        _close(bd.grad, br.grad, 1e-4, f"{what} bgrad")
 
 
 def test_gate(dev):

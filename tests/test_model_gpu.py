@@ -31,10 +31,28 @@ def _pair(kind, R, dev, seed=0):
     return o.eval(), p.to(dev).eval()
 
 
-def _inputs(B, R, smooth=True, size=256):
+def _inputs(B, R, smooth=True, size=256, seed=100):
+    """size: the side of a square image, or (h, w)"""
     from oracle.recipe import synthetic_image
 
-    return synthetic_image(B, size, size, 100, smooth=smooth), [synthetic_image(B, size, size, 101 + i, smooth=smooth) for i in range(R)]
+    h, w = (size, size) if isinstance(size, int) else size
+    return synthetic_image(B, h, w, seed, smooth=smooth), [synthetic_image(B, h, w, seed + 1 + i, smooth=smooth) for i in range(R)]
+
+
+def _count_paired_slices(monkeypatch):
+    """-> a one-element list counting the calls of ops.whole_and_first_half, which only the paired slice route of
+    models/clc.py `_slice_params` makes (once per slice): 0 on the unpaired route, 5 per forward on the paired one"""
+    from clc_amd import ops
+
+    n = [0]
+    real = ops.whole_and_first_half
+
+    def counted(x):
+        n[0] += 1
+        return real(x)
+
+    monkeypatch.setattr(ops, "whole_and_first_half", counted)
+    return n
 
 
 @pytest.mark.parametrize("kind,R", [("clc", 1), ("clc", 3), ("tcm", 0)])
@@ -180,6 +198,97 @@ def test_backward_parity(dev, kind, R, B):
         assert abs(lo[k].item() - lp[k].item()) <= 2e-4 * max(1.0, abs(lo[k].item())), (k, lo[k].item(), lp[k].item())
     checked, worst = _grad_parity(o, p)
     print(kind, R, "checked", checked, "worst rel err", worst)
+
+
+# 384x384: a 24x24 latent, 576 rows per image.  The slice nets pair only when B * 576 is a multiple of 128, so one image takes the
+# unpaired route (models/clc.py `_slice_params`, the `else` body) — the route of every odd-block image that eval.py pads at batch 1.
+@pytest.mark.parametrize("kind,R", [("clc", 1), ("tcm", 0)])
+def test_forward_parity_unpaired_slices_384(dev, kind, R, monkeypatch):
+    from oracle.loss import compute_bpp
+
+    paired = _count_paired_slices(monkeypatch)
+    o, p = _pair(kind, R, dev)
+    x, refs = _inputs(1, R, size=384)
+    with torch.no_grad():
+        a = o(x, refs) if kind == "clc" else o(x)
+        b = p(x.to(dev), [r.to(dev) for r in refs]) if kind == "clc" else p(x.to(dev))
+    assert paired[0] == 0, "expected the unpaired slice route"
+    assert b["likelihoods"]["y"].shape == (1, 320, 24, 24) and b["likelihoods"]["z"].shape == (1, 192, 6, 6)
+    y_err = (b["para"]["y"].cpu() - a["para"]["y"]).abs().max().item() / a["para"]["y"].abs().max().item()
+    assert y_err < 5e-5, f"y rel err {y_err}"
+    bpp_o, bpp_p = compute_bpp(a), compute_bpp({"x_hat": b["x_hat"].cpu(), "likelihoods": {k: v.cpu() for k, v in b["likelihoods"].items()}})
+    assert abs(bpp_o - bpp_p) <= 1e-4, (bpp_o, bpp_p)
+    psnr_o, psnr_p = _psnr(a["x_hat"], x), _psnr(b["x_hat"].cpu(), x)
+    assert abs(psnr_o - psnr_p) <= 0.01, (psnr_o, psnr_p)
+    d = (b["x_hat"].cpu() - a["x_hat"]).abs()
+    frac_bad = (d > 1e-3 * a["x_hat"].abs().max()).float().mean().item()
+    assert frac_bad < 5e-3, frac_bad
+
+
+@pytest.mark.parametrize("B", [1, 2])
+def test_backward_parity_384(dev, B, monkeypatch):
+    """CLC R = 1 at 384x384, loss terms and every parameter gradient vs the oracle.  B = 1: the unpaired slice nets; B = 2: the paired
+    ones with 1152-row halves on the 64x64 tiles (the 16x16-map cases of test_backward_parity run on the split-K family)."""
+    from clc_amd.train import RateDistortionLoss as PRD
+    from oracle.loss import RateDistortionLoss as ORD
+
+    paired = _count_paired_slices(monkeypatch)
+    o, p = _pair("clc", 1, dev)
+    x, refs = _inputs(B, 1, size=384)
+    oo = o(x, refs)
+    lo = ORD(0.0067)(oo, x)
+    lo["loss"].backward()
+    xd, rd = x.to(dev), [r.to(dev) for r in refs]
+    po = p(xd, rd)
+    assert paired[0] == (5 if B == 2 else 0), (B, paired[0])
+    lp = PRD(0.0067)(po, xd)
+    lp["loss"].backward()
+    assert _symbol_flips(oo, po) == 0
+    for k in ("loss", "bpp_loss", "mse_loss"):
+        assert abs(lo[k].item() - lp[k].item()) <= 2e-4 * max(1.0, abs(lo[k].item())), (k, lo[k].item(), lp[k].item())
+    checked, worst = _grad_parity(o, p)
+    print("384x384 B", B, "checked", checked, "worst rel err", worst)
+
+
+def test_paired_and_unpaired_slices_agree(dev, monkeypatch):
+    """The same 256x256 batch of 2 through the paired slice nets and, with ops.PAIR_SLICES = 0, the unpaired ones.  A filter-set launch gives
+    each half the bits of a separate launch (test_conv_paired_filters), so the eval forward is bit-identical; the gradients agree up to fp32
+    accumulation order (the bar of test_slice_loop_launch_merging_keeps_the_bits)."""
+    from clc_amd import ops
+    from clc_amd.train import RateDistortionLoss as PRD
+
+    paired = _count_paired_slices(monkeypatch)
+    _, p = _pair("clc", 1, dev)
+    x, refs = _inputs(2, 1)
+    xd, rd = x.to(dev), [r.to(dev) for r in refs]
+
+    def run():
+        paired[0] = 0
+        with torch.no_grad():
+            ev = p(xd, rd)
+        n_eval = paired[0]
+        p.zero_grad(set_to_none=True)
+        PRD(0.0067)(p(xd, rd), xd)["loss"].backward()
+        ops.flush_wgrads()
+        torch.cuda.synchronize()
+        return ev, {n: q.grad.clone() for n, q in p.named_parameters() if q.grad is not None}, (n_eval, paired[0] - n_eval)
+
+    ev1, g1, n1 = run()
+    monkeypatch.setattr(ops, "PAIR_SLICES", 0)
+    ev0, g0, n0 = run()
+    assert n1 == (5, 5) and n0 == (0, 0), (n1, n0)
+    assert torch.equal(ev1["x_hat"], ev0["x_hat"]), "x_hat"
+    for k in ("y", "z"):
+        assert torch.equal(ev1["likelihoods"][k], ev0["likelihoods"][k]), k
+    for k in ("means", "scales", "y"):
+        assert torch.equal(ev1["para"][k], ev0["para"][k]), k
+    assert g1.keys() == g0.keys()
+    worst = 0.0
+    for n in g1:
+        d = g0[n].abs().max().item()
+        if d > 1e-12:
+            worst = max(worst, (g1[n] - g0[n]).abs().max().item() / d)
+    assert worst < 2e-4, worst
 
 
 def test_slice_loop_launch_merging_keeps_the_bits(dev, monkeypatch):
