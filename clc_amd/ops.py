@@ -20,7 +20,7 @@ import torch
 from torch.autograd import Function
 
 from . import lib as _lib
-from .lib import (ACT_GELU, ACT_HALFTANH, ACT_LRELU, ACT_NONE, ACT_RELU, ACT_SAVED_DERIV, IN_NONE, IN_SQUARE, NORM_GDN,
+from .lib import (ACT_GELU, ACT_HALFTANH, ACT_LRELU, ACT_NONE, ACT_RELU, ACT_SAVED_DERIV, ACT_SIGMOID, IN_NONE, IN_SQUARE, NORM_GDN,
                   NORM_IGDN, NORM_MUL2, NORM_NONE)
 
 CL = torch.channels_last
@@ -889,6 +889,9 @@ class _ConvFn(Function):
         wk2 = to_kernel_weight(w2) if w2 is not None else None
         wkx = ((to_kernel_weight(w3), b3), (to_kernel_weight(w4), b4)) if w3 is not None else None
         need_grad = _recording(ctx)
+        if need_grad and act == ACT_SIGMOID:
+            # (forward-only epilogue: no gradient kernel knows sigmoid's derivative, and nothing is saved for it)
+            raise _lib.ClcError("conv2d: act=ACT_SIGMOID has no backward; run it without recording a graph (torch.no_grad())")
         # the activation derivative needs the pre-activation whenever the output does not determine it
         save_pre = need_grad and (act == ACT_GELU or (act in (ACT_LRELU, ACT_RELU, ACT_HALFTANH) and res is not None and not res_first))
         N, _, H, W = x.shape
