@@ -5,17 +5,21 @@ One "step" = one full training step of the reference loop (/root/reference/train
 synthetic batch already resident in HBM: forward (CLC N=64, lambda=0.0067, n_refs=1) + RD loss + backward +
 clip_grad_norm_(1.0) + nan_to_num_ + AdamW + aux-loss step, fp32, through the HIP kernels of libclc_hip.so.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 K timed steps after W warm-up steps; `ms_per_step` is the wall time of the K timed steps / K.  --dump-outputs writes what the last
 timed step returned, and the parameters it left, as DIR/<name>.npy (dump_outputs(); inputs and weights are seeded, so two builds
 run with the same arguments can be compared file for file).
 For N > 1 the driver launches it under torch.distributed.run (one rank per GPU, RCCL): every rank draws its
 own synthetic shard (weak scaling), gradients are averaged with all-reduce over the flat gradient arena.
-Rank 0 prints ONE JSON line (contract in the task description) with the extra objects
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.
+--full also runs every other leg after the timed steps (each can still be dropped with its --no-* option) and adds their objects:
   "roofline"      dominant kernel's algorithmic FLOP / measured duration (HIP events on the launch stream) vs the
                   f32-MFMA peak of gfx950 (157.3 TFLOP/s, /opt/skills/guides/MI355X_MICROARCH.md)
   "cpu_baseline"  the CPU oracle (plain PyTorch restatement of the reference graph) timed on the host cores on
                   a bounded sample of the same workload.
+  "parity", "codec", "reduced_precision", "reference_loop"   (one GPU): the HIP forward against the oracle on seeded images and the
+                  codec's timings; the opt-in bf16-MFMA mode's step rate and gradient error; the reference's literal (eager) loop body
+  "config.exposed_comm_ms"   (N > 1 or a forced one-rank group): the exposed gradient-exchange time of 5 extra steps
 """
 from __future__ import annotations
 
@@ -802,6 +806,8 @@ def main():
     ap.add_argument("--loss", choices=("mse", "ms_ssim"), default="mse", help="distortion term (train_CLC.py:52-57); configs[4] uses ms_ssim")
     ap.add_argument("--N", type=int, default=64, help="transform width: 64 (eval_CLC.py:264, the headline) or 128 (train_CLC.py:356 default)")
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every other leg: roofline (+ transforms), parity + codec, "
+                    "reduced precision, reference loop, CPU baseline and (multi-rank) exposed communication; the --no-* options drop single legs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--cpu-sample-batch", type=int, default=0, help="CPU-baseline batch (default: the GPU batch, BASELINE.md §3)")
@@ -912,7 +918,7 @@ def main():
     loss = float(out["loss"].item())
     # (before anything below runs another step: the roofline leg's eager step and exposed_comm_ms() update the parameters again)
     dumped = dump_outputs(args.dump_outputs, out, model) if (args.dump_outputs and rank == 0) else None
-    exposed_comm = engine.exposed_comm_ms(x, refs) if (use_dist and not args.no_graph) else None
+    exposed_comm = engine.exposed_comm_ms(x, refs) if (args.full and use_dist and not args.no_graph) else None
 
     result = {
         "metric": "images/sec fwd+bwd @256x256 bs8; bpp+PSNR parity vs ref",
@@ -945,7 +951,8 @@ def main():
         result["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "files": dumped}
     if trace is not None:
         result["config"]["loss_trace"] = [float(t.item()) for t in trace]
-    if not args.no_roofline:  # every rank runs it (the eager step contains the gradient all-reduce); rank 0 reports
+    # everything below the headline is --full only: a plain run prints its line now
+    if args.full and not args.no_roofline:  # every rank runs it (the eager step contains the gradient all-reduce); rank 0 reports
         result["roofline"] = roofline_leg(engine, x, refs)
         if rank == 0 and world == 1:
             result["roofline"]["transforms"] = transforms_leg(model, x, refs, engine)
@@ -960,17 +967,17 @@ def main():
             rl["in_step_transforms_frac"] = rl["in_step_by_owner"].get("transforms", {}).get("frac_of_f32_mfma_peak")
     if rank == 0:
         reduced_parity = None
-        if world == 1 and not args.no_parity:
+        if args.full and world == 1 and not args.no_parity:
             result["parity"], result["codec"], reduced_parity = parity_and_codec(dev)
-        if world == 1 and not args.no_reduced:
+        if args.full and world == 1 and not args.no_reduced:
             result["reduced_precision"] = reduced_precision_leg(args, dev, x, refs)
             if reduced_parity:
                 result["reduced_precision"].update(reduced_parity)
             result["reduced_precision"]["vs_f32_value"] = result["reduced_precision"]["value"] / result["value"]
-        if world == 1 and not use_dist and not args.no_reference_loop:
+        if args.full and world == 1 and not use_dist and not args.no_reference_loop:
             result["reference_loop"] = reference_loop_leg(args, dev, x, refs)
             result["reference_loop"]["vs_engine_value"] = round(result["reference_loop"]["value"] / result["value"], 4)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(args.n_refs, args.cpu_sample_batch or args.batch, args.size, N=args.N, lmbda=args.lmbda, loss=args.loss)
         print(json.dumps(result), flush=True)
     if use_dist:

@@ -42,3 +42,19 @@ def test_bench_dump_outputs_are_the_last_timed_step_and_reproducible(dev, tmp_pa
     assert ra["config"]["loss_trace"] == rb["config"]["loss_trace"]
     for f in names:
         assert np.array_equal(arrs[f], np.load(os.path.join(b, f))), f"{f} differs between two runs with the same arguments"
+
+
+def test_plain_run_prints_the_headline_and_runs_no_other_leg(dev):
+    """Without --full the run stops after the timed steps: the headline fields and `config`, none of the legs' objects."""
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "CLC_FORCE_COLLECTIVES", "CLC_FORCE_SPLIT_GRAPHS", "CLC_BENCH_EVAL_ROUNDING", "CLC_BENCH_LOSS_TRACE"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4"],
+                       capture_output=True, text=True, timeout=360, env=env, cwd=ROOT)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    rep = json.loads(lines[0])
+    assert rep["unit"] == "images/sec" and rep["higher_is_better"] is True and rep["dtype"] == "f32" and rep["steps"] == 2
+    assert rep["ms_per_step"] > 0 and abs(rep["value"] * rep["ms_per_step"] - 4 * 1e3) <= 1e-6 * 4e3
+    assert not {"roofline", "parity", "codec", "reduced_precision", "reference_loop", "cpu_baseline"} & set(rep), sorted(rep)

@@ -37,7 +37,7 @@ def test_rccl_one_rank_three_graph_step_is_bit_identical_to_no_group(dev, tmp_pa
 
 def _bench(env):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4",
-                        "--no-roofline", "--no-parity", "--no-reduced", "--no-cpu-baseline"], capture_output=True, text=True, timeout=360, env=env, cwd=ROOT)
+                        "--full", "--no-roofline", "--no-parity", "--no-reduced", "--no-cpu-baseline"], capture_output=True, text=True, timeout=360, env=env, cwd=ROOT)
     if r.returncode != 0:   # keep the whole child output where a gpurun call brings it home
         os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
         with open(os.path.join(ROOT, "gpurun_out", "rccl_bench_child_failure.txt"), "w") as fh:

@@ -6,16 +6,17 @@ set -u -o pipefail
 R=${GRAFT_REPO_ROOT:?set GRAFT_REPO_ROOT}
 cd $R
 N=$1; shift
-mkdir -p gpurun_out/ab
-extra="--no-cpu-baseline --no-reduced --no-parity --no-reference-loop"
+O=${OUT_DIR:-out}
+mkdir -p $O/ab
+extra="--full --no-cpu-baseline --no-reduced --no-parity --no-reference-loop"
 [ "${TR:-1}" = "0" ] && extra="$extra --no-roofline"
 for i in $(seq 1 $N); do
   for v in "$@"; do
     envs=""; [ "$v" != "-" ] && envs=$(echo "$v" | tr ',' ' ')
-    env $envs timeout -k 10 300 python bench.py --steps ${STEPS:-30} --warmup 5 $extra ${BENCH_ARGS:-} > gpurun_out/ab/step.json 2> gpurun_out/ab/step.err || { tail -20 gpurun_out/ab/step.err; exit 1; }
-    python - "$v" "$i" <<'PY'
+    env $envs timeout -k 10 300 python bench.py --steps ${STEPS:-30} --warmup 5 $extra ${BENCH_ARGS:-} > $O/ab/step.json 2> $O/ab/step.err || { tail -20 $O/ab/step.err; exit 1; }
+    python - "$v" "$i" "$O/ab/step.json" <<'PY'
 import json, sys
-d = json.loads(open("gpurun_out/ab/step.json").read().strip().splitlines()[-1])
+d = json.loads(open(sys.argv[3]).read().strip().splitlines()[-1])
 line = f"[{sys.argv[1]}] round {sys.argv[2]}: {d['value']:.2f} img/s {d['ms_per_step']:.3f} ms"
 t = d.get("roofline", {}).get("transforms")
 if t:
