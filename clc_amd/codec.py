@@ -31,6 +31,7 @@ import torch
 
 from . import ans, ops
 from .ops import CL
+from .refbank import BankMismatch  # noqa: F401  (raised by CodecEngine.decompress(items, bank=...))
 
 MAGIC = b"CLC1"
 
@@ -59,18 +60,31 @@ def kernel_config():
     return int(L.clc_kernel_config_tag()), int(L.clc_kernel_config_hash()) & 0xFFFFFFFF
 
 
-def pack(strings, shape, image_hw, n_refs: int = 0, model_id: int = 0, kernel_config_=None) -> bytes:
+def pack(strings, shape, image_hw, n_refs: int = 0, model_id: int = 0, kernel_config_=None, bank_id=None, ref_ids=None) -> bytes:
     """One image: header + z stream + y stream.
     header (little endian): magic 'CLC1' | u8 version | u8 model_id | u8 n_refs | u8 kernel-config tag | u16 H | u16 W (original image) |
-    u16 zh | u16 zw (hyper-latent shape = `shape`) | u32 len(y) | u32 len(z) [| u32 kernel-config hash: version 2].
+    u16 zh | u16 zw (hyper-latent shape = `shape`) | u32 len(y) | u32 len(z) [| u32 kernel-config hash: versions 2, 3]
+    [| u32 bank_id | n_refs x u32 ref ids: version 3].
     The tag records which generation of context-model kernels encoded the image: the slice loop is autoregressive through the
     arithmetic decoder, so the decoder only stays in sync when it reproduces the encoder's means / scales bit for bit (the
     reference has the same property across devices and library versions; it records nothing).  Version 1 (24-byte header) under the
     build's default kernel state; version 2 (28 bytes) when an order-affecting tuning key was off its default at ENCODE time: the tag
     then holds 7 bits of a hash and the full 32 bits follow.  kernel_config_: the `kernel_config` entry of compress()'s result
-    (default: the state at the time of this call)."""
+    (default: the state at the time of this call).
+    Version 3 (ref_ids given: the references of a clc_amd.refbank.ReferenceBank): the version-2 header, the hash always present, then
+    the bank's id and one index into bank.keys per reference; H x W is the size the bank prepared the references at, so the file
+    decodes with the bank alone (CodecEngine.decompress(items, bank=...))."""
     y, z = strings[0][0], strings[1][0]
     tag, h = kernel_config_ if kernel_config_ is not None else kernel_config()
+    if ref_ids is not None:
+        ids = [int(i) for i in ref_ids]
+        if bank_id is None or not 0 <= int(bank_id) < 1 << 32 or not 0 < len(ids) < 256 or any(not 0 <= i < 1 << 32 for i in ids):
+            raise ValueError(f"pack: version 3 needs a u32 bank_id and 1..255 u32 reference ids (got {bank_id}, {len(ids)} ids)")
+        if n_refs not in (0, len(ids)):
+            raise ValueError(f"pack: n_refs={n_refs} but {len(ids)} reference ids")
+        head = MAGIC + struct.pack("<BBBBHHHHII", 3, model_id, len(ids), tag, image_hw[0], image_hw[1], int(shape[0]), int(shape[1]), len(y), len(z))
+        head += struct.pack("<II", h, int(bank_id)) + struct.pack(f"<{len(ids)}I", *ids)
+        return head + z + y
     ver = 2 if tag >= 128 else 1
     head = MAGIC + struct.pack("<BBBBHHHHII", ver, model_id, n_refs, tag, image_hw[0], image_hw[1], int(shape[0]), int(shape[1]), len(y), len(z))
     if ver == 2:
@@ -78,9 +92,20 @@ def pack(strings, shape, image_hw, n_refs: int = 0, model_id: int = 0, kernel_co
     return head + z + y
 
 
-def pack_item(item: dict, image_hw, n_refs: int = 0, model_id: int = 0) -> bytes:
-    """pack() of one compress() result, under the kernel state that result was ENCODED with."""
-    return pack(item["strings"], item["shape"], image_hw, n_refs, model_id, item.get("kernel_config"))
+def pack_item(item: dict, image_hw=None, n_refs=None, model_id: int = 0) -> bytes:
+    """pack() of one compress() result, under the kernel state that result was ENCODED with.  A result of the bank path (it carries
+    `ref_ids`, `bank_id`, `image_hw`) is written as version 3; image_hw then defaults to the item's and must equal it."""
+    ids = item.get("ref_ids")
+    if ids is None:
+        if image_hw is None:
+            raise ValueError("pack_item: image_hw is required for an item without reference ids")
+        return pack(item["strings"], item["shape"], image_hw, n_refs or 0, model_id, item.get("kernel_config"))
+    ihw = item.get("image_hw")
+    if image_hw is None:
+        image_hw = ihw
+    if image_hw is None or (ihw is not None and tuple(int(v) for v in image_hw) != tuple(int(v) for v in ihw)):
+        raise ValueError(f"pack_item: image_hw {image_hw} is not the size {ihw} the bank prepared this item's references at")
+    return pack(item["strings"], item["shape"], image_hw, n_refs or 0, model_id, item.get("kernel_config"), item["bank_id"], ids)
 
 
 def check_kernel_config(meta, what="container"):
@@ -99,21 +124,27 @@ def check_kernel_config(meta, what="container"):
 
 def unpack(blob: bytes, strict: bool = True):
     """-> (strings, shape, meta) as decompress() takes them.  strict (default): refuse a container whose kernel-config tag is not this
-    build's (KernelConfigMismatch); strict=False returns it with meta["same_kernel_config"] = False for inspection."""
+    build's (KernelConfigMismatch); strict=False returns it with meta["same_kernel_config"] = False for inspection.  Version 3 adds
+    meta["bank_id"] and meta["ref_ids"]."""
     if len(blob) < 24 or blob[:4] != MAGIC:
         raise ValueError("not a CLC1 container (shorter than its 24-byte header, or wrong magic)")
     ver, model_id, n_refs, tag, H, W, zh, zw, ny, nz = struct.unpack("<BBBBHHHHII", blob[4:24])
-    if ver not in (1, 2):
+    if ver not in (1, 2, 3):
         raise ValueError(f"unsupported container version {ver}")
-    hl = 24 if ver == 1 else 28
+    hl = {1: 24, 2: 28, 3: 32 + 4 * n_refs}[ver]
+    if ver == 3 and n_refs == 0:
+        raise ValueError("version-3 container without reference ids")
     if len(blob) != hl + ny + nz:
         raise ValueError("truncated / oversized container")
     z, y = blob[hl:hl + nz], blob[hl + nz:hl + nz + ny]
     now, now_h = kernel_config()
     meta = {"image_hw": (H, W), "n_refs": n_refs, "model_id": model_id, "kernel_config_tag": tag, "same_kernel_config": tag == now}
-    if ver == 2:
+    if ver >= 2:
         meta["kernel_config_hash"] = struct.unpack("<I", blob[24:28])[0]
         meta["same_kernel_config"] = tag == now and meta["kernel_config_hash"] == now_h
+    if ver == 3:
+        meta["bank_id"] = struct.unpack("<I", blob[28:32])[0]
+        meta["ref_ids"] = list(struct.unpack(f"<{n_refs}I", blob[32:hl]))
     if strict:
         check_kernel_config(meta)
     return [[y], [z]], torch.Size([zh, zw]), meta
@@ -125,8 +156,8 @@ def unpack_item(blob: bytes, strict: bool = True) -> dict:
     return {"strings": strings, "shape": shape, "meta": meta}
 
 
-def write_file(path, strings, shape, image_hw, n_refs=0, model_id=0):
-    blob = pack(strings, shape, image_hw, n_refs, model_id)
+def write_file(path, strings, shape, image_hw, n_refs=0, model_id=0, kernel_config_=None, bank_id=None, ref_ids=None):
+    blob = pack(strings, shape, image_hw, n_refs, model_id, kernel_config_, bank_id, ref_ids)
     with open(path, "wb") as f:
         f.write(blob)
     return len(blob)
@@ -215,19 +246,39 @@ class CodecEngine:
         return g, out
 
     # ---------------------------------------------------------------- encoder
-    def _build_encoder(self, x, refs):
+    def _bank_slots(self, pl, arena, slots):
+        """bank plans: the arena the graphs gather from and the slot table they read (device memory, refreshed per call from pinned memory)."""
+        pl.arena = arena
+        pl.slot_idx = torch.tensor(slots, dtype=torch.int32).to(arena.device)
+        pl.slot_host = torch.empty(pl.slot_idx.shape, dtype=torch.int32).pin_memory()
+        pl.R = len(slots[0])
+
+    def _set_slots(self, pl, arena, slots):
+        if pl.arena is not arena:   # (arenas are never reallocated: a plan only ever meets the one it was captured with)
+            raise RuntimeError("CodecEngine: the bank's arena moved under a captured plan")
+        pl.slot_host.numpy()[...] = slots
+        pl.slot_idx.copy_(pl.slot_host, non_blocking=True)
+
+    def _bank_features(self, pl):
+        """reference features of a bank plan: the gathered latents [R*B, M, h, w] into the unchanged tail of CLC._ref."""
+        B = pl.slot_idx.shape[0]
+        return self.model._ref_from_latents(ops.gather_slots(pl.arena, pl.slot_idx, B, pl.R), pl.R)
+
+    def _build_encoder(self, x, refs, bank=None):
         m = self.model
         pl = _Plan()
         pl.kernel_config = kernel_config()
         pl.x = x.clone()
         pl.refs = [r.clone() for r in refs] if refs is not None else None
+        if bank is not None:
+            self._bank_slots(pl, *bank)
         B = x.shape[0]
         S = m.num_slices
 
         @torch.no_grad()
         def run():
             xx = m._prep(pl.x)
-            ref_features = m._ref(pl.refs)
+            ref_features = self._bank_features(pl) if bank is not None else m._ref(pl.refs)
             y = m.g_a(xx)
             y_shape = y.shape[2:]
             z = m._fuse_z(m.h_a(y))
@@ -258,14 +309,49 @@ class CodecEngine:
         pl.zidx = np.ascontiguousarray(np.broadcast_to(np.arange(C, dtype=np.int32).reshape(C, 1, 1), (C,) + pl.zshape)).reshape(-1)
         return pl
 
+    def _bank_model(self, bank):
+        m = self.model
+        if not getattr(m, "use_ref", True) or not hasattr(m, "ref_encoder"):
+            raise ValueError("CodecEngine: a reference bank needs a model that codes with references (CLC, use_ref=True)")
+        if bank.model.ref_encoder is not m.ref_encoder:
+            raise ValueError("CodecEngine: the bank was built for another model")
+
     @torch.no_grad()
-    def compress(self, x, ref_frames: Optional[Sequence[torch.Tensor]] = None) -> List[dict]:
-        """x [B,3,H,W] (H, W multiples of 128 after eval.pad) -> one {"strings": [[y], [z]], "shape"} per image."""
+    def compress(self, x, ref_frames: Optional[Sequence[torch.Tensor]] = None, *, ref_keys=None, bank=None, image_hw=None) -> List[dict]:
+        """x [B,3,H,W] (H, W multiples of 128 after eval.pad) -> one {"strings": [[y], [z]], "shape"} per image.
+        Bank path (clc_amd.refbank.ReferenceBank): ref_keys = one list of R bank keys per image, image_hw = the size the references are
+        resized to before padding (default: x's); the latents come from the bank's cache and the results carry `ref_ids` (indexes into
+        bank.keys), `bank_id` and `image_hw` besides, which pack_item() writes as a version-3 container."""
+        if bank is not None or ref_keys is not None:
+            return self._compress_bank(x, ref_frames, ref_keys, bank, image_hw)
         refs = list(ref_frames) if ref_frames else None
         if not getattr(self.model, "use_ref", True) or not hasattr(self.model, "ref_encoder"):
             refs = None
         sig = self._sig(x, refs)
         pl = self._plan(self._enc, sig, lambda: self._build_encoder(x, refs))
+        return self._run_encoder(pl, x, refs)
+
+    def _compress_bank(self, x, ref_frames, ref_keys, bank, image_hw):
+        if bank is None or ref_keys is None or ref_frames:
+            raise ValueError("CodecEngine.compress: the bank path takes ref_keys AND bank, and no ref_frames")
+        self._bank_model(bank)
+        B = x.shape[0]
+        rows = [list(r) for r in ref_keys]
+        if len(rows) != B or len({len(r) for r in rows}) != 1:
+            raise ValueError(f"CodecEngine.compress: ref_keys must hold one list of R keys per image ({B} images), got {[len(r) for r in rows]}")
+        hw = tuple(int(v) for v in (image_hw if image_hw is not None else x.shape[-2:]))
+        if ((hw[0] + 127) // 128 * 128, (hw[1] + 127) // 128 * 128) != tuple(x.shape[-2:]):
+            raise ValueError(f"CodecEngine.compress: image_hw {hw} does not pad to the input's size {tuple(x.shape[-2:])}")
+        arena, slots = bank.lookup(rows, hw)
+        sig = (tuple(x.shape), len(rows[0]), bank, kernel_config())
+        pl = self._plan(self._enc, sig, lambda: self._build_encoder(x, None, (arena, slots)))
+        self._set_slots(pl, arena, slots)
+        outs = self._run_encoder(pl, x, None)
+        for o, r in zip(outs, rows):
+            o.update(ref_ids=[bank.index[k] for k in r], bank_id=bank.bank_id, image_hw=hw)
+        return outs
+
+    def _run_encoder(self, pl, x, refs):
         t0 = time.perf_counter()
         pl.x.copy_(x, non_blocking=True)
         if refs is not None:
@@ -293,11 +379,13 @@ class CodecEngine:
         return [{"strings": [[ys], [zs]], "shape": torch.Size(pl.zshape), "kernel_config": pl.kernel_config} for ys, zs in streams]
 
     # ---------------------------------------------------------------- decoder
-    def _build_decoder(self, B, zshape, refs, dev):
+    def _build_decoder(self, B, zshape, refs, dev, bank=None):
         m = self.model
         S = m.num_slices
         pl = _Plan()
         pl.refs = [r.clone() for r in refs] if refs is not None else None
+        if bank is not None:
+            self._bank_slots(pl, *bank)
         pl.z_in = torch.zeros((B, self.zc) + tuple(zshape), dtype=torch.int32, device=dev)
         yh, yw = zshape[0] * 4, zshape[1] * 4
         Cs = m.M // S
@@ -324,7 +412,7 @@ class CodecEngine:
 
         @torch.no_grad()
         def seg_first():
-            st["ref"] = m._ref(pl.refs)
+            st["ref"] = self._bank_features(pl) if bank is not None else m._ref(pl.refs)
             med = m.entropy_bottleneck._get_medians().reshape(1, -1, 1, 1)
             z_hat = (pl.z_in.float() + med).contiguous(memory_format=CL)
             st["ls"] = m.h_scale_s(z_hat)
@@ -348,23 +436,61 @@ class CodecEngine:
             pl.segs.append((g, fn, out))
         return pl
 
+    def _bank_rows(self, items, bank, zshape):
+        """(key rows, image_hw) of bank items (compress() results of the bank path or unpack_item()ed version-3 containers)."""
+        rows, hws = [], set()
+        for k, it in enumerate(items):
+            meta = it.get("meta") or {}
+            ids = it.get("ref_ids", meta.get("ref_ids"))
+            bid = it.get("bank_id", meta.get("bank_id"))
+            hw = it.get("image_hw", meta.get("image_hw"))
+            if ids is None or bid is None or hw is None:
+                raise ValueError(f"item {k} names no bank references (encode with compress(..., ref_keys=, bank=) / a version-3 container)")
+            if int(bid) != bank.bank_id:
+                raise BankMismatch(f"item {k} was encoded against bank {int(bid):08x}, this bank is {bank.bank_id:08x} ({len(bank.keys)} keys): "
+                                   "its reference ids would name other images")
+            bad = [i for i in ids if not 0 <= int(i) < len(bank.keys)]
+            if bad:
+                raise ValueError(f"item {k}: reference ids {bad} are outside the bank's {len(bank.keys)} keys")
+            rows.append([bank.keys[int(i)] for i in ids])
+            hws.add((int(hw[0]), int(hw[1])))
+        if len(hws) != 1 or len({len(r) for r in rows}) != 1:
+            raise ValueError(f"decompress: the items of one call share one image size and one reference count, got {sorted(hws)}")
+        hw = hws.pop()
+        if ((hw[0] + 127) // 128 * 128, (hw[1] + 127) // 128 * 128) != (zshape[0] * 64, zshape[1] * 64):
+            raise ValueError(f"decompress: image size {hw} does not pad to the streams' {zshape[0] * 64}x{zshape[1] * 64}")
+        return rows, hw
+
     @torch.no_grad()
-    def decompress(self, items: Sequence[dict], ref_frames: Optional[Sequence[torch.Tensor]] = None) -> torch.Tensor:
-        """items: outputs of compress() (or unpack_item()ed containers, whose kernel-config tag is checked here) for B images of one shape -> x_hat [B,3,H,W] clamped to [0,1]."""
+    def decompress(self, items: Sequence[dict], ref_frames: Optional[Sequence[torch.Tensor]] = None, *, bank=None) -> torch.Tensor:
+        """items: outputs of compress() (or unpack_item()ed containers, whose kernel-config tag is checked here) for B images of one shape -> x_hat [B,3,H,W] clamped to [0,1].
+        bank: decode items of the bank path without reference tensors: their ref ids name the bank's keys (BankMismatch for another
+        bank's id), the bank prepares and encodes (or finds cached) the references itself."""
         m = self.model
         for k, it in enumerate(items):      # items that came out of a container carry its header: refuse another kernel generation's
             if it.get("meta") is not None:
                 check_kernel_config(it["meta"], f"item {k}")
             elif it.get("kernel_config") is not None and tuple(it["kernel_config"]) != kernel_config():
                 raise KernelConfigMismatch(f"item {k} was encoded under kernel state {tuple(it['kernel_config'])}, this process now decodes under {kernel_config()}")
-        refs = list(ref_frames) if ref_frames else None
-        if not getattr(m, "use_ref", True) or not hasattr(m, "ref_encoder"):
-            refs = None
         B = len(items)
         zshape = tuple(int(v) for v in items[0]["shape"])
         dev = next(m.parameters()).device
-        sig = (B, zshape, None if refs is None else tuple(tuple(r.shape) for r in refs), kernel_config())
-        pl = self._plan(self._dec, sig, lambda: self._build_decoder(B, zshape, refs, dev))
+        if bank is not None:
+            if ref_frames:
+                raise ValueError("CodecEngine.decompress: pass ref_frames or bank, not both")
+            self._bank_model(bank)
+            rows, hw = self._bank_rows(items, bank, zshape)
+            arena, slots = bank.lookup(rows, hw)
+            sig = (B, zshape, len(rows[0]), bank, kernel_config())
+            pl = self._plan(self._dec, sig, lambda: self._build_decoder(B, zshape, None, dev, (arena, slots)))
+            self._set_slots(pl, arena, slots)
+            refs = None
+        else:
+            refs = list(ref_frames) if ref_frames else None
+            if not getattr(m, "use_ref", True) or not hasattr(m, "ref_encoder"):
+                refs = None
+            sig = (B, zshape, None if refs is None else tuple(tuple(r.shape) for r in refs), kernel_config())
+            pl = self._plan(self._dec, sig, lambda: self._build_decoder(B, zshape, refs, dev))
         if refs is not None:
             for d, r in zip(pl.refs, refs):
                 d.copy_(r, non_blocking=True)

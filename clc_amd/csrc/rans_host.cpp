@@ -56,7 +56,8 @@ extern "C" int clc_get_tuning(int key) {
 // The slice loop is autoregressive through the arithmetic decoder, so a decoder only stays in sync with an encoder that produced the
 // same float means / scales bit for bit.  kGeneration is bumped by hand whenever a kernel the codec path launches changes the order
 // in which it sums; the tuning keys that select between kernels of DIFFERENT order (kernel family limits, the reduced-precision mode,
-// the forward halves of the attention tiling) are folded in when they are off their defaults.
+// the forward halves of the attention tiling) are folded in when they are off their defaults.  clc_ref_prepare (refbank.hip) counts as
+// such a kernel: the reference bank's prepared images feed the reference encoder, so a change to its arithmetic bumps kGeneration too.
 // (key 11 — K split of under-filled data gradients, with a threshold value — reaches TRANSPOSED launches only, i.e. backward passes: not an
 //  order key of the codec path.)
 static uint32_t clc_order_hash(bool* dflt_out) {

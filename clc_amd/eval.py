@@ -46,16 +46,43 @@ def compute_bpp(out_net) -> float:
 
 
 @torch.no_grad()
-def evaluate(net, samples: Iterable[Tuple[torch.Tensor, Sequence[torch.Tensor]]], p: int = 128, device="cuda", engine=None, ms_ssim=False):
+def evaluate(net, samples: Iterable[Tuple[torch.Tensor, Sequence[torch.Tensor]]], p: int = 128, device="cuda", engine=None, ms_ssim=False,
+             bank=None):
     """samples: iterable of (image [3,h,w] in [0,1], [reference images]). Returns per-image rows and averages.
     engine: a clc_amd.codec.CodecEngine over `net` (graph-captured codec, same bitstreams); default: net.compress / net.decompress.
     ms_ssim: also score each cropped reconstruction (outside the timed region): rows gain "ms_ssim" and "ms_ssim_db"
-    (compute_msssim), the result "avg_ms_ssim_db"."""
+    (compute_msssim), the result "avg_ms_ssim_db".
+    bank: a clc_amd.refbank.ReferenceBank over `net`: a sample's references are KEYS of the bank, prepared by the bank (the same recipe
+    on clc_ref_prepare) and coded through `engine` (default: one CodecEngine for this call) with cached reference latents."""
     net.eval()
     net.update()
+    own = None
+    if bank is not None and engine is None:
+        from .codec import CodecEngine
+
+        engine = own = CodecEngine(net, threads=1)
+    try:
+        return _evaluate(net, samples, p, device, engine, ms_ssim, bank)
+    finally:
+        if own is not None:
+            own.close()
+
+
+def _evaluate(net, samples, p, device, engine, ms_ssim, bank):
     rows, t_total = [], 0.0
     for x, refs in samples:
         x = x.unsqueeze(0).to(device)
+        if bank is not None:
+            keys = list(refs)
+            x_p, padding = pad(x, p)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            enc = engine.compress(x_p, ref_keys=[keys], bank=bank, image_hw=tuple(x.shape[-2:]))[0]
+            dec = {"x_hat": engine.decompress([enc], bank=bank)}
+            torch.cuda.synchronize()
+            t_total += time.perf_counter() - t0
+            rows.append(_score(x, enc, dec, padding, ms_ssim))
+            continue
         refs = [r.unsqueeze(0).to(device) for r in refs]
         refs = [F.interpolate(r, size=x.shape[-2:], mode="bilinear", align_corners=False) if r.shape[-2:] != x.shape[-2:] else r for r in refs]
         x_p, padding = pad(x, p)
@@ -70,18 +97,23 @@ def evaluate(net, samples: Iterable[Tuple[torch.Tensor, Sequence[torch.Tensor]]]
             dec = net.decompress(enc["strings"], enc["shape"], refs_p)
         torch.cuda.synchronize()
         t_total += time.perf_counter() - t0
-        x_hat = crop(dec["x_hat"], padding)
-        num_pixels = x.size(0) * x.size(2) * x.size(3)
-        bitrate = sum(len(s[0]) for s in enc["strings"]) * 8.0 / num_pixels
-        rows.append({"bpp": bitrate, "psnr": compute_psnr(x, x_hat)})
-        if ms_ssim:
-            v = ssim.ms_ssim(x.float(), x_hat.float(), data_range=1.0).item()
-            rows[-1].update(ms_ssim=v, ms_ssim_db=-10 * math.log10(1 - v))
+        rows.append(_score(x, enc, dec, padding, ms_ssim))
     n = max(1, len(rows))
     res = {"rows": rows, "avg_bpp": sum(r["bpp"] for r in rows) / n, "avg_psnr": sum(r["psnr"] for r in rows) / n, "avg_time_s": t_total / n}
     if ms_ssim:
         res["avg_ms_ssim_db"] = sum(r["ms_ssim_db"] for r in rows) / n
     return res
+
+
+def _score(x, enc, dec, padding, ms_ssim):
+    x_hat = crop(dec["x_hat"], padding)
+    num_pixels = x.size(0) * x.size(2) * x.size(3)
+    bitrate = sum(len(s[0]) for s in enc["strings"]) * 8.0 / num_pixels
+    row = {"bpp": bitrate, "psnr": compute_psnr(x, x_hat)}
+    if ms_ssim:
+        v = ssim.ms_ssim(x.float(), x_hat.float(), data_range=1.0).item()
+        row.update(ms_ssim=v, ms_ssim_db=-10 * math.log10(1 - v))
+    return row
 
 
 # ----------------------------------------------------------------------------------------------- checkpoints / RD sweep (§8(f)-3)

@@ -98,6 +98,14 @@ class SsimDesc(C.Structure):
                 ("dx", fp), ("lddx", C.c_int), ("dy", fp), ("lddy", C.c_int), ("dnext_x", fp), ("dnext_y", fp)]
 
 
+class RefSrc(C.Structure):
+    _fields_ = [("src", fp), ("h", C.c_int), ("w", C.c_int)]
+
+
+class FpEntry(C.Structure):
+    _fields_ = [("ptr", fp), ("nbytes", C.c_uint64), ("word_offset", C.c_int64)]
+
+
 class ParamEntry(C.Structure):
     _fields_ = [("p", fp), ("g", fp), ("m", fp), ("v", fp), ("n", C.c_long)]
 
@@ -214,6 +222,9 @@ SIGNATURES = {
     "clc_rans_decoder_decode": (_l, [fp, fp, _l, fp, _i, fp, fp, fp]),
     "clc_rans_decoder_destroy": (None, [fp]),
     "clc_pmf_to_quantized_cdf": (_i, [fp, _i, _i, fp]),
+    "clc_ref_prepare": (_i, [fp, _i, _i, _i, fp, fp]),
+    "clc_gather_slots": (_i, [fp, _l, _i, fp, _i, _i, fp, fp]),
+    "clc_fingerprint": (_i, [fp, _i, fp, _i, fp, fp]),
 }
 
 

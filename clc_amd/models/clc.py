@@ -475,8 +475,19 @@ class CLC(_SliceCodec):
         R = len(ref_frames)
         if R != self.num_ref_frames:
             raise ValueError(f"expected {self.num_ref_frames} reference frames, got {R}")
+        return self._ref_from_latents(self._ref_encode(ref_frames), R)
+
+    def _ref_encode(self, ref_frames):
+        """R reference frames [B, 3, H, W] -> their latents [R*B, M, H/16, W/16], reference-major: one batched ref_encoder pass."""
+        R = len(ref_frames)
         refs = self._prep(torch.cat(list(ref_frames), dim=0)) if R > 1 else self._prep(ref_frames[0])
-        feats = self.ref_encoder(refs)                      # one batched pass over all R references
+        return self.ref_encoder(refs)
+
+    def _ref_from_latents(self, feats, R):
+        """reference latents [R*B, M, h, w] (reference-major, from _ref_encode or gathered from a clc_amd.refbank.ReferenceBank) -> the
+        reference features every slice reads."""
+        if R != self.num_ref_frames:
+            raise ValueError(f"expected {self.num_ref_frames} reference frames, got {R}")
         self._ref_latents = feats if self.wire_clm else None   # [R*B, M, h, w], reference-major
         if R > 1:
             feats = torch.cat(feats.chunk(R, dim=0), dim=1)  # [B, R*M, h, w] in reference order

@@ -2495,3 +2495,77 @@ def ms_ssim(x, y, data_range=1.0, weights=MS_SSIM_WEIGHTS, size_average=True, wi
     weights = MS_SSIM_WEIGHTS if weights is None else weights
     taps = ssim_window_taps(win_size, win_sigma, win)
     return ms_ssim_combine(ssim_stats(x, y, len(weights), taps, data_range, K), weights, size_average)
+
+
+# ------------------------------------------------------------------------------- reference bank of the codec (clc_amd/refbank.py)
+
+
+def _device_table(entries, ctype, dev):
+    """ctypes structs -> a device copy of their array (pinned staging + a stream-ordered copy: no host synchronisation)."""
+    arr = (ctype * len(entries))(*entries)
+    host = torch.empty(C.sizeof(arr), dtype=torch.uint8, pin_memory=True)
+    C.memmove(host.data_ptr(), C.addressof(arr), C.sizeof(arr))
+    return host.to(dev, non_blocking=True)
+
+
+def ref_prepare(images, image_hw):
+    """clc_ref_prepare: reference images [3, h_n, w_n] (fp32 in [0, 1], each its own size; [1, 3, h, w] accepted) -> channels_last
+    [N, 3, H, W] = eval.pad(F.interpolate(r, image_hw, mode="bilinear", align_corners=False), 128) in ONE launch; an image that already
+    has size image_hw is copied exactly."""
+    h, w = int(image_hw[0]), int(image_hw[1])
+    if not images or h < 1 or w < 1:
+        raise ValueError(f"ref_prepare: {len(images)} images, size {image_hw}")
+    srcs, keep = [], []
+    for r in images:
+        _require_gpu(r, "ref_prepare")
+        if r.dim() == 4 and r.shape[0] == 1:
+            r = r[0]
+        if r.dim() != 3 or r.shape[0] != 3:
+            raise ValueError(f"ref_prepare: an image must be [3, h, w], got {tuple(r.shape)}")
+        r = r.contiguous()
+        keep.append(r)
+        srcs.append(_lib.RefSrc(r.data_ptr(), r.shape[1], r.shape[2]))
+    dev = keep[0].device
+    H, W = (h + 127) // 128 * 128, (w + 127) // 128 * 128
+    out = torch.empty((len(keep), 3, H, W), device=dev, memory_format=CL)
+    table = _device_table(srcs, _lib.RefSrc, dev)
+    _lib.check(_L().clc_ref_prepare(table.data_ptr(), len(keep), h, w, out.data_ptr(), _stream()), "clc_ref_prepare")
+    return out
+
+
+def gather_slots(arena, idx, B: int, R: int, out=None):
+    """clc_gather_slots: arena [S, M, h, w] (channels_last slots), idx int32 [B, R] on the device -> [R*B, M, h, w] channels_last with
+    out[r*B + b] = arena[idx[b, r]] (reference-major, like ref_encoder(cat(refs)))."""
+    _require_gpu(arena, "gather_slots")
+    if arena.dim() != 4 or not arena.is_contiguous(memory_format=CL) or idx.dtype != torch.int32 or not idx.is_contiguous() or idx.numel() != B * R:
+        raise ValueError("gather_slots: arena must be a channels_last [S, M, h, w] tensor and idx a contiguous int32 [B, R] tensor")
+    if out is None:
+        out = torch.empty((R * B,) + tuple(arena.shape[1:]), device=arena.device, memory_format=CL)
+    slot = arena[0].numel()
+    _lib.check(_L().clc_gather_slots(arena.data_ptr(), slot, arena.shape[0], idx.data_ptr(), B, R, out.data_ptr(), _stream()), "clc_gather_slots")
+    return out
+
+
+def fingerprint(tensors, n_partials: int = 256):
+    """clc_fingerprint over the tensors' bytes (in this order) -> int64 device tensor [1] holding the 64-bit content hash.  Independent of
+    where the tensors live: equal content at other addresses gives the same value."""
+    ents, keep, off = [], [], 0
+    for t in tensors:
+        if t.numel() == 0:
+            continue
+        if not t.is_cuda:
+            raise _lib.ClcError("fingerprint: tensors live on the GPU only (no CPU fallback by design)")
+        if not (t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=CL))) or t.data_ptr() % 4:
+            t = t.contiguous().clone()
+        keep.append(t)
+        nb = t.numel() * t.element_size()
+        ents.append(_lib.FpEntry(t.data_ptr(), nb, off))
+        off += (nb + 3) // 4
+    if not ents:
+        raise ValueError("fingerprint: no data")
+    dev = keep[0].device
+    table = _device_table(ents, _lib.FpEntry, dev)
+    partials = torch.empty(n_partials, dtype=torch.int64, device=dev)
+    out = torch.empty(1, dtype=torch.int64, device=dev)
+    _lib.check(_L().clc_fingerprint(table.data_ptr(), len(ents), partials.data_ptr(), n_partials, out.data_ptr(), _stream()), "clc_fingerprint")
+    return out

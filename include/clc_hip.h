@@ -592,6 +592,28 @@ int clc_gdn_bwd_fused(const float* dy, const float* x, const float* v, const flo
 int clc_maxpool2d(const float* x, int ldx, float* y, int ldy, int N, int H, int W, int C, int ks, int stride, int pad, int OH, int OW, clc_stream_t stream);
 int clc_adaptive_pool2d(const float* x, int ldx, float* out, int N, int H, int W, int C, int L, int is_max, clc_stream_t stream);
 
+/* ---- reference bank of the codec (clc_amd/refbank.py; the reference prepares its references in eval_CLC.py:246-257, 306-315) ---- *
+ * clc_ref_prepare: N reference images, table[n] = {planar NCHW fp32 [3, h_n, w_n] in [0, 1], h_n, w_n} (the TABLE lives in device memory)
+ *   -> out channels_last [N, 3, H, W] = pad(F.interpolate(r, (h, w), mode="bilinear", align_corners=False), 128), H / W = h / w rounded up
+ *   to 128, the image centred (clc_amd.eval.pad).  ATen's source-index rule; index, weights and blend in double, rounded once to fp32; an
+ *   image that already has size (h, w) is copied exactly.  One launch for every image of the table.  Its bits feed the reference encoder,
+ *   i.e. the context model: a change to its arithmetic needs a new kernel generation (clc_kernel_config_tag).
+ * clc_gather_slots: channels_last latents, one slot = slot_elems floats (a multiple of 4, 16-byte aligned):
+ *   out[r*B + b] = arena[idx[b*R + r]] (reference-major, the layout ref_encoder(cat(refs)) returns).  idx [B, R] lives in device memory,
+ *   so a captured graph replays the gather with new slots after one small host-to-device copy; an index outside [0, n_slots) yields NaN.
+ * clc_fingerprint: out[0] = sum over every 32-bit word of every buffer of mix((global word index << 32) | word) mod 2^64 (a tail of 1-3
+ *   bytes zero-extended; word_offset = the buffer's first global word index).  Independent of the grid; partials = n_partials words of
+ *   caller scratch (1..4096). */
+typedef struct {
+  const float* src; int h; int w;
+} clc_ref_src;
+typedef struct {
+  const void* ptr; uint64_t nbytes; int64_t word_offset;
+} clc_fp_entry;
+int clc_ref_prepare(const clc_ref_src* table, int N, int h, int w, float* out, clc_stream_t stream);
+int clc_gather_slots(const float* arena, long slot_elems, int n_slots, const int32_t* idx, int B, int R, float* out, clc_stream_t stream);
+int clc_fingerprint(const clc_fp_entry* table, int n, uint64_t* partials, int n_partials, uint64_t* out, clc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
