@@ -129,8 +129,7 @@ def kernel_state():
 
 def _ops_state():
     """the Python-side switches of clc_amd.ops that change which launches a forward / backward issues"""
-    return (ops.WGRAD_DEFER, ops.DEFER_REDUCTIONS, ops.BRANCH_STREAMS, ops.PAIR_SLICES, ops.PAIR_HYPER, ops.SUPPORT_BUFFER,
-            ops.PROFILE is not None)
+    return (ops.WGRAD_DEFER, ops.DEFER_REDUCTIONS, ops.PAIR_SLICES, ops.SUPPORT_BUFFER, ops.PROFILE is not None)
 
 
 def signature(model, x, refs, kstate=None):

@@ -439,12 +439,6 @@ class SWAtten(AttentionBlock):
                 x = self.in_conv(x, pair=pair.in_conv, fold_in=in_fold, grad_slot=in_slot, out=u_buf[: x.shape[0]] if u_buf is not None else None)
             else:
                 assert in_fold is None and in_slot is None
-            def branch_a():
-                a = x
-                for m, q in zip(self.conv_a, pair.conv_a):
-                    a = m(a, pair=q)
-                return a
-
             if quad:
                 # conv_a's three ResidualUnits (on x) and conv_b's (on the Swin output) are same-shaped layers on different data: stacked
                 # along the batch they run as ONE chain of 9 launches with four filter sets (this net's a, the pair's a, this net's b,
@@ -465,29 +459,17 @@ class SWAtten(AttentionBlock):
                 b = self.conv_b[3](b, pair=pair.conv_b[3], grad_slot=(bs, 0, 1) if bs is not None else None)
                 out = ops.gate(a, b, x, a_slot=(bs, 0) if bs is not None else None)
                 return self.out_conv(out, pair=pair.out_conv) if self.out_conv is not None else out
-            fork_a = ops.BRANCH_STREAMS and ops.PROFILE is None and "swatten_a" in ops.BRANCH_SLOTS
-            if fork_a:   # conv_a(x) is independent of the Swin -> conv_b branch: run it on a forked stream
-                with ops.fork("swatten_a", [x]) as f:
-                    a = branch_a()
             b = self.non_local_block(x, pair=pair.non_local_block)
             for m, q in zip(self.conv_b, pair.conv_b):
                 b = m(b, pair=q)
-            if fork_a:
-                f.join(a)
-            else:
-                a = branch_a()
+            a = x
+            for m, q in zip(self.conv_a, pair.conv_a):
+                a = m(a, pair=q)
             out = ops.gate(a, b, x)
             return self.out_conv(out, pair=pair.out_conv) if self.out_conv is not None else out
         if self.in_conv is not None:
             x = self.in_conv(x)
-        if ops.BRANCH_STREAMS and ops.PROFILE is None and "swatten_a" in ops.BRANCH_SLOTS and "scale" not in ops.BRANCH_SLOTS:
-            # (not inside the forked scale branch: nested forks crash hipGraph capture_end on ROCm 7.2)
-            with ops.fork("swatten_a", [x]) as f:       # conv_a(x) is independent of the Swin -> conv_b branch
-                a = self.conv_a(x)
-            b = self.conv_b(self.non_local_block(x))
-            f.join(a)
-        else:
-            a = self.conv_a(x)
-            b = self.conv_b(self.non_local_block(x))
+        a = self.conv_a(x)
+        b = self.conv_b(self.non_local_block(x))
         out = ops.gate(a, b, x)
         return self.out_conv(out) if self.out_conv is not None else out

@@ -255,8 +255,6 @@ def load():
         if L.clc_set_tuning(int(k), int(v)) < 0:
             msg = L.clc_last_error()
             raise ClcError(f"CLC_TUNING={item}: {msg.decode() if msg else 'rejected'}")
-    if os.environ.get("CLC_WINO"):   # Winograd F(2x2, 3x3) for the 3x3 layers of the transforms (tuning key 23): bit 0 forward, bit 1 data gradients, bit 2 the 64-wide kernel
-        L.clc_set_tuning(23, int(os.environ["CLC_WINO"]))
     _lib = L
     return L
 

@@ -190,25 +190,16 @@ class _SliceCodec(CompressionModel):
                 mu, scale = mu[:, :, : y_shape[0], : y_shape[1]], scale[:, :, : y_shape[0], : y_shape[1]]
             return mean_support, mu, scale
 
-        def scale_branch():
-            ss = self.atten_scale[i](torch.cat([latent_scales] + support, dim=1))
-            if ref_features is not None:
-                return self.ref_cc_scale_transforms[i](torch.cat([ss, ref_features], dim=1))
-            return self.cc_scale_transforms[i](ss)
-
-        branch = ops.BRANCH_STREAMS and ops.PROFILE is None and "scale" in ops.BRANCH_SLOTS
-        if branch:   # the scale-parameter net is independent of the mean-parameter net: run it on a forked stream
-            with ops.fork("scale", [latent_scales, ref_features] + list(support)) as f:
-                scale = scale_branch()
         mean_support = self.atten_mean[i](torch.cat([latent_means] + support, dim=1))
         if ref_features is not None:
             mu = self.ref_cc_mean_transforms[i](torch.cat([mean_support, ref_features], dim=1))
         else:
             mu = self.cc_mean_transforms[i](mean_support)
-        if branch:
-            f.join(scale)
+        ss = self.atten_scale[i](torch.cat([latent_scales] + support, dim=1))
+        if ref_features is not None:
+            scale = self.ref_cc_scale_transforms[i](torch.cat([ss, ref_features], dim=1))
         else:
-            scale = scale_branch()
+            scale = self.cc_scale_transforms[i](ss)
         if mu.shape[2] != y_shape[0] or mu.shape[3] != y_shape[1]:
             mu, scale = mu[:, :, : y_shape[0], : y_shape[1]], scale[:, :, : y_shape[0], : y_shape[1]]
         return mean_support, mu, scale
@@ -224,7 +215,7 @@ class _SliceCodec(CompressionModel):
         architecture on the same input — stacked along the batch they run as ONE launch per layer.
         stacked: return the stacked result [means; scales] itself (ops.SliceSupport takes it whole)."""
         rows = z_hat.shape[0] * z_hat.shape[2] * z_hat.shape[3]
-        if ops.PAIR_SLICES and ops.PAIR_HYPER and rows % 128 == 0 and z_hat.shape[0] % 2 == 0:
+        if ops.PAIR_SLICES and rows % 128 == 0 and z_hat.shape[0] % 2 == 0:
             both = torch.cat((z_hat, z_hat), dim=0)
             for m, q in zip(self.h_mean_s, self.h_scale_s):
                 both = m(both, pair=q)
@@ -268,7 +259,7 @@ class _SliceCodec(CompressionModel):
         S = y.shape[1] // self.num_slices
         sup = y_buf = lik_buf = None
         rows = z_hat.shape[0] * z_hat.shape[2] * z_hat.shape[3]
-        if (ops.SUPPORT_BUFFER and ops.PAIR_SLICES and ops.PAIR_HYPER and rows % 128 == 0 and z_hat.shape[0] % 2 == 0
+        if (ops.SUPPORT_BUFFER and ops.PAIR_SLICES and rows % 128 == 0 and z_hat.shape[0] % 2 == 0
                 and (y.shape[0] * y.shape[2] * y.shape[3]) % 128 == 0
                 # (the shared gradient buffer relies on the slices running backward strictly last-to-first, which autograd's dependencies
                 #  only enforce when every slice reads its predecessor: ops.SliceSupport)
@@ -312,7 +303,7 @@ class _SliceCodec(CompressionModel):
         y_hat = ops.gather_channels(y_buf, y_hat_slices) if y_buf is not None else torch.cat(y_hat_slices, dim=1)
         if prof:
             ops.set_owner("g_s")
-        x_hat = self.g_s(ops.flush_point(y_hat))
+        x_hat = self.g_s(y_hat)
         if prof:
             ops.set_owner("other")
         y_likelihoods = ops.gather_channels(lik_buf, y_lik) if lik_buf is not None else torch.cat(y_lik, dim=1)

@@ -14,7 +14,6 @@ from __future__ import annotations
 import ctypes as C
 import functools
 import math
-import os
 
 import torch
 from torch.autograd import Function
@@ -27,11 +26,9 @@ CL = torch.channels_last
 
 # Filter gradients are only needed by the optimizer, so they are DEFERRED: queued per layer and launched WGRAD_GROUP at a
 # time through clc_conv2d_wgrad_batched (one grid per tile shape + one slab reduce for the whole group) instead of 2-3
-# launch-bound kernels per layer.  Where they run:
-#   * in line on the launching stream (default).  Under hipGraph replay on ROCm 7.2 a graph with parallel branches pays
-#     ~4.4 us of cross-queue marker latency in front of EVERY kernel that follows an event record, and the branches barely
-#     overlap (tools/graph_fork_probe.py; bench: 1 graph queue 216 img/s vs 4 queues 210) — a linear graph is faster;
-#   * on a side stream (CLC_WGRAD_STREAM=1), concurrent with the data-gradient chain: the better choice for eager execution.
+# launch-bound kernels per layer.  They run in line on the launching stream: under hipGraph replay on ROCm 7.2 a graph with
+# parallel branches pays ~4.4 us of cross-queue marker latency in front of EVERY kernel that follows an event record, and the
+# branches barely overlap (tools/graph_fork_probe.py; bench: 1 graph queue 216 img/s vs 4 queues 210) — a linear graph is faster.
 # Tensors a deferred launch still reads are kept alive in the device state's `keepalive` until join_side_streams().
 WGRAD_DEFER = False
 
@@ -46,7 +43,7 @@ class _DeviceState:
     the engine's device thread while join_side_streams() is called from the caller's.)"""
 
     __slots__ = ("pending", "pending_flop", "pending_streams", "pending_post", "last_defer_vid", "pending_reduce", "keepalive",
-                 "branch_pool", "wgrad_stream", "group_ws")
+                 "group_ws")
 
     def __init__(self):
         self.pending = {}            # kernel-family id -> [(descriptor, keep-alive tuple)]
@@ -56,8 +53,6 @@ class _DeviceState:
         self.last_defer_vid = 0      # family of the problem queued last (a post hook registers itself under it)
         self.pending_reduce = []
         self.keepalive = []          # tensors a deferred / cross-stream launch still reads, until join_side_streams()
-        self.branch_pool = {}
-        self.wgrad_stream = None     # side stream of the filter gradients (CLC_WGRAD_STREAM=1), else None
         self.group_ws = {}           # None / "capture" -> [stream-K partial-tile workspace (642 MiB), stream that used it last]
 
 
@@ -78,21 +73,20 @@ def _S() -> _DeviceState:
     return st
 
 
-def enable_wgrad_stream(enable=True):
-    """Turn on deferred, grouped filter gradients (and the side stream when CLC_WGRAD_STREAM=1) — the TrainEngine's mode."""
+def enable_deferred_wgrads(enable=True):
+    """Turn on deferred, grouped filter gradients — the TrainEngine's mode."""
     global WGRAD_DEFER
     WGRAD_DEFER = bool(enable)
-    _S().wgrad_stream = torch.cuda.Stream() if (enable and os.environ.get("CLC_WGRAD_STREAM", "0") == "1") else None
 
 
-WGRAD_GROUP = int(os.environ.get("CLC_WGRAD_GROUP", "64"))             # problems per grouped launch (library cap: 64)
+WGRAD_GROUP = 64             # problems per grouped launch (library cap: 64)
 # ... or as soon as this much work is queued.  Default: effectively never (flush by count).
-WGRAD_FLUSH_GFLOP = float(os.environ.get("CLC_WGRAD_FLUSH_GFLOP", "1000"))
+WGRAD_FLUSH_GFLOP = 1000.0
 
 
 def _group_ws():
     """(ptr, bytes) of this device's stream-K workspace.  Launches on one stream are ordered; when the launching stream changes
-    (warm-up stream -> training stream, main stream <-> filter-gradient side stream) the new stream first waits for the old one.
+    (warm-up stream -> training stream) the new stream first waits for the old one.
     The buffer is allocated OUTSIDE hipGraph capture (TrainEngine's eager warm-up steps come first); a capture that meets no
     buffer gets a private one that lives in the graph's pool, under its own key, and is never handed to eager launches."""
     tab = _S().group_ws
@@ -123,7 +117,7 @@ def _is_capturing(stream):
 
 
 def release_workspaces():
-    """Teardown hook: drop the stream-K workspaces, branch-stream pools and queues of every device of this process (re-created on
+    """Teardown hook: drop the stream-K workspaces and queues of every device of this process (re-created on
     demand).  Call it only between steps: queued filter gradients are dropped with their queues."""
     _STATES.clear()
 
@@ -170,8 +164,7 @@ def _flush_family(vid, target):
 
 def _flush_target():
     S = _S()
-    cur = torch.cuda.current_stream()
-    target = S.wgrad_stream if S.wgrad_stream is not None else cur
+    target = torch.cuda.current_stream()
     for sid, st in S.pending_streams.items():   # the operands were produced on these streams
         if sid != target.cuda_stream:
             target.wait_stream(st)
@@ -223,62 +216,15 @@ def flush_reductions():
 
 def join_side_streams():
     flush_wgrads()
-    S = _S()
-    if S.wgrad_stream is not None:
-        torch.cuda.current_stream().wait_stream(S.wgrad_stream)
     flush_reductions()
-    S.keepalive.clear()
+    _S().keepalive.clear()
 
 
-# Branch streams: independent sub-graphs of the latency-bound 16x16 slice loop (mean vs scale parameter nets, the
-# conv_a vs Swin->conv_b branches of SWAtten) run on forked HIP streams and join again, so the ~10 us kernels of different
-# branches overlap on the 256 CUs; under hipGraph capture the fork/join becomes parallel graph branches. Autograd runs
-# each op's backward on the stream of its forward, so the backward overlaps the same way.
-BRANCH_STREAMS = False
-# Paired layers: the mean- and scale-parameter nets of a slice run as one launch per layer over a stacked batch (CLC_PAIR=0:
-# two launches, optionally on forked streams).
-PAIR_SLICES = int(os.environ.get("CLC_PAIR", "1"))   # default on: half the launches of the slice loop, no reliance on hipGraph branch concurrency
-SUPPORT_BUFFER = int(os.environ.get("CLC_SUPPORT_BUFFER", "1"))   # slice loop: one support buffer + one gradient buffer instead of per-slice concatenations (SliceSupport)
-MATERIALIZE_DZ = int(os.environ.get("CLC_MATERIALIZE_DZ", "32768"))   # rows from which a 3x3 layer's activation backward is its own pass (0: always fused into the gradient kernels' loaders)
-QUAD_UNITS = int(os.environ.get("CLC_QUAD_UNITS", "1"))   # paired SWAttens: the ResidualUnits of conv_a and conv_b of both nets in one chain (4 filter sets)
-PAIR_HYPER = int(os.environ.get("CLC_PAIR_HYPER", "1"))   # also pair the mean / scale hyper-synthesis nets (h_mean_s, h_scale_s)
-BRANCH_SLOTS = set(os.environ.get("CLC_BRANCH", "scale").split(","))   # which forks are taken (debug knob)
-
-
-def enable_branch_streams(enable=True):
-    global BRANCH_STREAMS
-    BRANCH_STREAMS = bool(enable)
-
-
-class fork:
-    """with ops.fork(slot, inputs) as f: out = branch(...);  f.join(out) afterwards on the parent stream."""
-
-    def __init__(self, slot, inputs):
-        self.parent = torch.cuda.current_stream()
-        key = (self.parent.cuda_stream, slot)
-        pool = _S().branch_pool
-        if key not in pool:
-            pool[key] = torch.cuda.Stream()
-        self.stream = pool[key]
-        self.inputs = [t for t in inputs if t is not None]
-
-    def __enter__(self):
-        self.stream.wait_stream(self.parent)
-        # tensors crossing streams are kept alive until the end of the step (ops.join_side_streams) instead of
-        # record_stream(): every later use of a branch stream starts with wait_stream(parent), which orders any reuse of
-        # their memory after the consumers — and record_stream's deferred events crash hipGraph capture_end (ROCm 7.2)
-        _S().keepalive.append(self.inputs)
-        self.ctx = torch.cuda.stream(self.stream)
-        self.ctx.__enter__()
-        return self
-
-    def __exit__(self, *exc):
-        self.ctx.__exit__(*exc)
-        return False
-
-    def join(self, *outputs):
-        self.parent.wait_stream(self.stream)
-        _S().keepalive.append(outputs)
+# Paired layers: the mean- and scale-parameter nets of a slice run as one launch per layer over a stacked batch (0: two launches).
+PAIR_SLICES = 1   # half the launches of the slice loop, no reliance on hipGraph branch concurrency
+SUPPORT_BUFFER = 1   # slice loop: one support buffer + one gradient buffer instead of per-slice concatenations (SliceSupport)
+MATERIALIZE_DZ = 32768   # rows from which a 3x3 layer's activation backward is its own pass (0: always fused into the gradient kernels' loaders)
+QUAD_UNITS = 1   # paired SWAttens: the ResidualUnits of conv_a and conv_b of both nets in one chain (4 filter sets)
 
 
 class GradFold:
@@ -312,9 +258,6 @@ class GradFold:
         g, s, gate = self.pending, self.scale, self.gate
         self.pending = self.gate = None
         return g, s, gate
-
-
-ACT_GATES = int(os.environ.get("CLC_ACT_GATE", "1"))   # 0: every layer applies its own activation derivative (A/B knob)
 
 
 class ActGate:
@@ -550,16 +493,15 @@ def to_kernel_weight(w: torch.Tensor) -> torch.Tensor:
 #     that `w.data.copy_(...)` or a kernel writing through a raw pointer changed the weights (neither moves a version counter), and a stale
 #     image would be silently wrong results.  Inside a captured graph (CodecEngine) the pack launch is part of the graph, so a replay
 #     always packs the weights of the moment.
-HALO = os.environ.get("CLC_HALO", "1") != "0"
 WEIGHTS_EPOCH = 0   # bumped by TrainEngine per step (its kernels update the arena through raw pointers); informational
 
 
 def halo_ok(N, H, W, Cin, rows, ks, stride):
     """input-channel count (128 / 64) if a [rows][3][3][Cin] filter on an N x H x W map may take the halo kernel, else 0 (the C side re-checks
     everything and falls through to the tiled kernels)"""
-    if not (HALO and ks == 3 and stride == 1 and Cin in (128, 64) and rows % Cin == 0 and H % 8 == 0 and W % 16 == 0):
+    if not (ks == 3 and stride == 1 and Cin in (128, 64) and rows % Cin == 0 and H % 8 == 0 and W % 16 == 0):
         return 0
-    if not (_L().clc_get_tuning(22) & (1 if Cin == 128 else 2)):   # tuning key 22: bit 0 = 128-channel layers, bit 1 = 64-channel layers (off by default)
+    if not (_L().clc_get_tuning(22) & (1 if Cin == 128 else 2)):   # tuning key 22: bit 0 = 128-channel layers (default), bit 1 = 64-channel layers
         return 0
     return Cin if N * (H // 8) * (W // 16) * (rows // Cin) >= 128 else 0
 
@@ -587,7 +529,7 @@ def halo_packed(w, transposed_image=None):
 
 # ---- Winograd F(2x2, 3x3) kernel (csrc/conv_wino.hip): needs the TRANSFORMED filter U = G g G^T in fragment order.  Same provenance rules as the
 # halo kernel's image: per-step batched launch inside a TrainEngine step (clc_amd.train.WinoPacker -> w._clc_wu / w._clc_wu_t), per use elsewhere.
-# (switched by tuning key 23 / the CLC_WINO environment variable: bit 0 = forward launches of a recorded (training) pass, bit 1 = data gradients.
+# (switched by tuning key 23, e.g. through CLC_TUNING: bit 0 = forward launches of a recorded (training) pass, bit 1 = data gradients.
 #  Never taken without autograd recording: eval forwards, the parity measurement and the codec keep the direct kernels and their bits.)
 
 
@@ -782,7 +724,7 @@ def wgrad_raw(x, dy, *, ks, stride, pad, Cout, Cin, want_bias, in_op=IN_NONE, dw
               dys_pre=False, defer=False, _collect=False, accumulate=None):
     """Returns (dw [Cout, ks*ks*Cin] flat kernel layout, dbias or None).  With dw_out / db_out (persistent gradient
     buffers in kernel layout) the result is ACCUMULATED into them and (None, None) is returned.  defer=True (direct mode
-    on the side stream only) queues the problem for the next grouped launch (flush_wgrads)."""
+    only) queues the problem for the next grouped launch (flush_wgrads)."""
     x, xp, N, H, W, _, ldx = nhwc(x)
     dy, dp, _, OH, OW, _, lddy = nhwc(dy)
     direct = dw_out is not None
@@ -915,7 +857,7 @@ class _ConvFn(Function):
         saved_act = y_pre if save_pre else (y if act in (ACT_LRELU, ACT_RELU, ACT_HALFTANH) else None)
         ctx.use_pre = save_pre
         ctx.gates = (gate_in, gate_out)
-        if gate_out is not None and ACT_GATES and need_grad and act in (ACT_LRELU, ACT_RELU, ACT_GELU) and res is None:
+        if gate_out is not None and need_grad and act in (ACT_LRELU, ACT_RELU, ACT_GELU) and res is None:
             # what the consumer's data-gradient epilogue needs to apply this layer's activation derivative.  detach(): a plain alias
             # without grad_fn — the gate must not close a reference cycle y -> grad_fn -> ctx -> gate -> y (the activations would
             # then live until a garbage-collection pass instead of until the backward pass has used them)
@@ -935,18 +877,7 @@ class _ConvFn(Function):
         gw, gb = _direct_grad(w), (_direct_grad(bias_ref) if has_b else None)
         if gw is not None and (gb is not None or not has_b) and to_kernel_weight(w) is w:
             # write straight into the persistent gradient arena (accumulate) — no temporary, no autograd add kernel
-            if WGRAD_DEFER and (PROFILE is None or WGRAD_GROUP > 1):
-                side = _S().wgrad_stream
-                if WGRAD_GROUP > 1 or side is None:
-                    wgrad_raw(x, dz, ks=ks, stride=stride, pad=pad, Cout=Cout, Cin=Cin, want_bias=has_b, dw_out=gw, db_out=gb, defer=True, **fw)
-                else:
-                    cur = torch.cuda.current_stream()
-                    side.wait_stream(cur)
-                    _S().keepalive.append((x, dz, fw.get("dys")))
-                    with torch.cuda.stream(side):
-                        wgrad_raw(x, dz, ks=ks, stride=stride, pad=pad, Cout=Cout, Cin=Cin, want_bias=has_b, dw_out=gw, db_out=gb, **fw)
-            else:
-                wgrad_raw(x, dz, ks=ks, stride=stride, pad=pad, Cout=Cout, Cin=Cin, want_bias=has_b, dw_out=gw, db_out=gb, **fw)
+            wgrad_raw(x, dz, ks=ks, stride=stride, pad=pad, Cout=Cout, Cin=Cin, want_bias=has_b, dw_out=gw, db_out=gb, defer=WGRAD_DEFER, **fw)
             return None, None
         dwf, db = wgrad_raw(x, dz, ks=ks, stride=stride, pad=pad, Cout=Cout, Cin=Cin, want_bias=need_b, **fw)
         return (_dw_to_param_layout(dwf, w) if need_w else None), db
@@ -1077,7 +1008,7 @@ def _recording(ctx) -> bool:
 # running (or capturing) the forward/backward of a step — a plain autograd backward on the same model afterwards transposes on the fly.
 WT_CACHE_VALID = False
 
-FUSED_RU = int(os.environ.get("CLC_FUSED_RU", "1"))   # ResidualUnits on 16x16 maps with 128 channels: one launch forward, one for the data gradient
+FUSED_RU = 1   # ResidualUnits on 16x16 maps with 128 channels: one launch forward, one for the data gradient
 
 
 def residual_unit_fusable(x, sets) -> bool:
@@ -1174,12 +1105,12 @@ def residual_unit(x, units):
 
 # ----------------------------------------------------------------------------- fused Swin-block MLP (csrc/fused_mlp.hip)
 
-FUSED_MLP = int(os.environ.get("CLC_FUSED_MLP", "1"))              # 0: fc1 + GELU and fc2 as two clc_conv2d launches (A/B knob; same bits)
-FUSED_MLP_MIN_PIX = int(os.environ.get("CLC_FUSED_MLP_MIN", "32768"))   # pixels from which the persistent fused kernel pays (one workgroup per CU)
-FUSED_MLP_LN = int(os.environ.get("CLC_FUSED_MLP_LN", "1"))        # 1: the LayerNorm in front (Block.ln2) inside the fused kernels too (same bits; not with MLP_SAVE_H)
-MLP_SAVE_H = int(os.environ.get("CLC_MLP_SAVE_H", "0"))            # training: 0 = nothing stored, the backward kernel recomputes fc1 from the LayerNorm output;
-                                                                   # 1 = the forward pass stores fc1's pre-activation and the backward kernel reads it (same bits;
-                                                                   #     111 vs 133 us per launch at 8x128x128, and the same step time: the 134 MB it writes cost as much)
+FUSED_MLP = 1              # 0: fc1 + GELU and fc2 as two clc_conv2d launches (same bits)
+FUSED_MLP_MIN_PIX = 32768  # pixels from which the persistent fused kernel pays (one workgroup per CU)
+FUSED_MLP_LN = 1           # 1: the LayerNorm in front (Block.ln2) inside the fused kernels too (same bits; not with MLP_SAVE_H)
+MLP_SAVE_H = 0             # training: 0 = nothing stored, the backward kernel recomputes fc1 from the LayerNorm output;
+                           # 1 = the forward pass stores fc1's pre-activation and the backward kernel reads it (same bits;
+                           #     111 vs 133 us per launch at 8x128x128, and the same step time: the 134 MB it writes cost as much)
 
 
 def mlp_fusable(x, w1, w2, pair=None) -> bool:
@@ -1332,8 +1263,8 @@ def mlp_ln(x, ln_g, ln_b, w1, b1, w2, b2, *, out=None):
 
 # ------------------------------------------------------------------ LayerNorm + Linear: ln1 and the attention's embedding (csrc/fused_mlp.hip)
 
-FUSED_GDN_BWD = int(os.environ.get("CLC_FUSED_GDN_BWD", "1"))   # 0: clc_gdn_bwd_elem + a transposed 1x1 clc_conv2d (A/B knob; same bits)
-FUSED_LNLIN = int(os.environ.get("CLC_FUSED_LNLIN", "1"))   # 0: clc_layernorm_fwd + a 1x1 clc_conv2d launch (A/B knob; same bits)
+FUSED_GDN_BWD = 1   # 0: clc_gdn_bwd_elem + a transposed 1x1 clc_conv2d (same bits)
+FUSED_LNLIN = 1   # 0: clc_layernorm_fwd + a 1x1 clc_conv2d launch (same bits)
 
 
 def lnlin_fusable(x, w, pair=None) -> bool:
@@ -1473,12 +1404,9 @@ class _FanOutFn(Function):
         return out, None
 
 
-FANOUT = int(os.environ.get("CLC_FANOUT", "1"))   # 0: leave multi-consumer gradients to autograd's pairwise accumulation (A/B knob)
-
-
 def fanout(x, n):
     """n aliases of x for n consumers (see _FanOutFn); a tensor that needs no gradient is handed out as it is"""
-    if n <= 1 or not FANOUT or not (torch.is_grad_enabled() and x.requires_grad):
+    if n <= 1 or not (torch.is_grad_enabled() and x.requires_grad):
         return (x,) * max(n, 1)
     return _FanOutFn.apply(x, n)
 
@@ -1523,24 +1451,6 @@ class _CutFn(Function):
 
 def cut(x):
     return _CutFn.apply(x) if x is not None and x.requires_grad else x
-
-
-class _FlushPointFn(Function):
-    """Identity whose backward launches the filter gradients queued so far (the synthesis transform's, when placed at its input):
-    on the side stream (CLC_WGRAD_STREAM=1) these MFMA-bound grids then run beside the latency-bound backward of the slice loop."""
-
-    @staticmethod
-    def forward(ctx, x):
-        return x.view_as(x)
-
-    @staticmethod
-    def backward(ctx, g):
-        flush_wgrads()
-        return g
-
-
-def flush_point(x):
-    return _FlushPointFn.apply(x) if (WGRAD_DEFER and x.is_cuda and _S().wgrad_stream is not None and x.requires_grad) else x
 
 
 # ----------------------------------------------------------------------------------- split / chunk

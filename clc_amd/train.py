@@ -30,7 +30,6 @@ from . import ops
 
 
 # ------------------------------------------------------------------------------------------ loss
-FUSED_RD_LOSS = os.environ.get("CLC_FUSED_RD_LOSS", "1") != "0"
 
 
 def ms_ssim(X, Y, data_range=1.0, size_average=True, win_size=11, win_sigma=1.5, win=None, weights=None, K=(0.01, 0.03)):
@@ -52,7 +51,7 @@ class RateDistortionLoss(nn.Module):
         num_pixels = N * H * W
         out = {}
         liks = output["likelihoods"]
-        if self.type == "mse" and FUSED_RD_LOSS and isinstance(liks, dict) and list(liks.keys()) == ["y", "z"] and output["x_hat"].is_cuda:
+        if self.type == "mse" and isinstance(liks, dict) and list(liks.keys()) == ["y", "z"] and output["x_hat"].is_cuda:
             # the whole scalar tail (three sums, the divisions, lmbda * 255^2 * mse + bpp) in one launch; same bits as the expressions below
             tgt = target.float().contiguous(memory_format=ops.CL)
             out["bpp_loss"], out["mse_loss"], out["loss"] = ops.rd_loss_mse(liks["y"], liks["z"], output["x_hat"], tgt, self.lmbda, num_pixels)
@@ -416,7 +415,7 @@ class TrainEngine:
         self.lr, self.aux_lr, self.clip = lr, aux_lr, clip_max_norm
         self.use_graph, self.with_optimizer = use_graph, with_optimizer
         self.train_mode = train_mode   # False: deterministic rounding instead of noise (tests)
-        self.side_stream = side_stream # filter gradients on a second stream, concurrent with the data-gradient chain
+        self.side_stream = side_stream # deferred, grouped filter gradients (ops.enable_deferred_wgrads)
         self.opt: Optional[FusedAdamW] = None
         self.aux_opt: Optional[FusedAdamW] = None
         self.sync: Optional[GradSync] = None
@@ -442,8 +441,7 @@ class TrainEngine:
         live = late + early
         aux = [p for n, p in self.model.named_parameters() if n.endswith(".quantiles")]
         if self.side_stream:
-            ops.enable_wgrad_stream(True)
-            ops.enable_branch_streams(True)
+            ops.enable_deferred_wgrads(True)
         ops.enable_deferred_reductions(True)
         self.opt = self._make_opt(live, self.lr, self.clip)
         self.aux_opt = self._make_opt(aux, self.aux_lr, 0.0)
@@ -491,7 +489,7 @@ class TrainEngine:
             out["loss"].backward(self._one_like(out["loss"]))   # (a cached 1: no ones_like fill launch per step)
         finally:
             ops.WT_CACHE_VALID = False
-        ops.join_side_streams()   # filter gradients computed on the side stream are complete from here on
+        ops.join_side_streams()   # the deferred filter gradients and reductions are launched from here on
         return out
 
     # -- the same pass cut in two at the outputs of the analysis transform / reference branch (multi-GPU overlap)

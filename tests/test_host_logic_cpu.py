@@ -277,3 +277,27 @@ def test_clc_tuning_env_rejects_unknown_and_retired_settings():
     assert retired.startswith("raised:") and "retired" in retired, retired
     assert unknown.startswith("raised:") and "out of range" in unknown, unknown
     assert run("0:2,13:0") == "loaded"          # a retired key at its default, a live key at any value
+
+
+def test_retired_environment_switches_are_not_read():
+    """The host layer's retired CLC_* switches, each set away from its default, change none of the constants that took their place nor the
+    Winograd tuning key: a child interpreter with them prints what one without them prints."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    names = ("PAIR_SLICES", "SUPPORT_BUFFER", "QUAD_UNITS", "MATERIALIZE_DZ", "FUSED_RU", "FUSED_MLP", "FUSED_MLP_MIN_PIX", "FUSED_MLP_LN",
+             "MLP_SAVE_H", "FUSED_GDN_BWD", "FUSED_LNLIN", "WGRAD_GROUP", "WGRAD_FLUSH_GFLOP")
+    code = f"from clc_amd import lib, ops, train\nprint([getattr(ops, n) for n in {names!r}], lib.load().clc_get_tuning(23))\n"
+    retired = dict(CLC_PAIR="0", CLC_SUPPORT_BUFFER="0", CLC_QUAD_UNITS="0", CLC_MATERIALIZE_DZ="0", CLC_FUSED_RU="0", CLC_FUSED_MLP="0",
+                   CLC_FUSED_MLP_MIN="1", CLC_FUSED_MLP_LN="0", CLC_MLP_SAVE_H="1", CLC_FUSED_GDN_BWD="0", CLC_FUSED_LNLIN="0",
+                   CLC_WGRAD_GROUP="1", CLC_WGRAD_FLUSH_GFLOP="0", CLC_WINO="0", CLC_BRANCH="scale,swatten_a", CLC_WGRAD_STREAM="1",
+                   CLC_ACT_GATE="0", CLC_FANOUT="0", CLC_HALO="0", CLC_PAIR_HYPER="0", CLC_FUSED_RD_LOSS="0")
+
+    def run(extra):
+        env = {k: v for k, v in os.environ.items() if k not in retired and k != "CLC_TUNING"}
+        out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120, cwd=root, env=dict(env, **extra))
+        assert out.returncode == 0, out.stderr[-2000:]
+        return out.stdout.strip()
+
+    assert run(retired) == run({})

@@ -250,6 +250,43 @@ def test_backward_parity_384(dev, B, monkeypatch):
     print("384x384 B", B, "checked", checked, "worst rel err", worst)
 
 
+def test_unpaired_slices_stay_on_one_stream_after_a_train_engine(dev, monkeypatch):
+    """A TrainEngine in the process leaves other models' launches alone: a plain forward and backward at 384x384, batch 1 (the unpaired
+    slice route), issues every C-ABI launch on one stream — the scale-parameter net is not moved to a stream of its own."""
+    from clc_amd import models as pm
+    from clc_amd import ops
+    from clc_amd.recipe import apply_weight_recipe
+    from clc_amd.train import RateDistortionLoss, TrainEngine
+
+    x, refs = _inputs(2, 1)
+    m = pm.CLC(N=64, num_ref_frames=1).to(dev)
+    apply_weight_recipe(m, 0)
+    TrainEngine(m, lmbda=0.0067, use_graph=False, train_mode=False).step(x.to(dev), [r.to(dev) for r in refs])
+    torch.cuda.synchronize()
+
+    paired = _count_paired_slices(monkeypatch)
+    p = pm.CLC(N=64, num_ref_frames=1).to(dev).eval()
+    apply_weight_recipe(p, 0)
+    x, refs = _inputs(1, 1, size=384)
+    xd, rd = x.to(dev), [r.to(dev) for r in refs]
+    streams, real = [], ops._stream
+
+    def recorded():
+        s = real()
+        streams.append(s)
+        return s
+
+    monkeypatch.setattr(ops, "_stream", recorded)
+    out = p(xd, rd)
+    n_fwd = len(streams)
+    RateDistortionLoss(0.0067)(out, xd)["loss"].backward()
+    torch.cuda.synchronize()
+    assert paired[0] == 0, "expected the unpaired slice route"
+    assert 0 < n_fwd < len(streams)
+    assert set(streams[:n_fwd]) == {torch.cuda.current_stream().cuda_stream}, "forward"
+    assert set(streams[n_fwd:]) == {torch.cuda.current_stream().cuda_stream}, "backward"
+
+
 def test_paired_and_unpaired_slices_agree(dev, monkeypatch):
     """The same 256x256 batch of 2 through the paired slice nets and, with ops.PAIR_SLICES = 0, the unpaired ones.  A filter-set launch gives
     each half the bits of a separate launch (test_conv_paired_filters), so the eval forward is bit-identical; the gradients agree up to fp32
@@ -292,8 +329,8 @@ def test_paired_and_unpaired_slices_agree(dev, monkeypatch):
 
 
 def test_slice_loop_launch_merging_keeps_the_bits(dev, monkeypatch):
-    """The slice loop's launch-count reductions — four filter sets per launch (CLC_QUAD_UNITS), the support / gradient buffers
-    (CLC_SUPPORT_BUFFER), the separate activation-backward pass of large 3x3 layers (CLC_MATERIALIZE_DZ) — only regroup work: the
+    """The slice loop's launch-count reductions — four filter sets per launch (ops.QUAD_UNITS), the support / gradient buffers
+    (ops.SUPPORT_BUFFER), the separate activation-backward pass of large 3x3 layers (ops.MATERIALIZE_DZ) — only regroup work: the
     forward results are bit-identical with and without them, the gradients equal up to fp32 accumulation order."""
     from clc_amd import ops
     from clc_amd.train import RateDistortionLoss as PRD
