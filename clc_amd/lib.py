@@ -185,6 +185,14 @@ SIGNATURES = {
     "clc_clm_scale_rows": (_i, [fp, _i, fp, fp, _i, _l, _i, fp]),
     "clc_clm_deform": (_i, [fp, _i, fp, _i, fp, _i, fp, _i, _i, _i, _i, _i, fp]),
     "clc_clm_fuse": (_i, [_pp, _pp, _i, _i, _i, fp, _i, fp, _i, _l, _i, _i, fp]),
+    "clc_clm_sim_colsum_train": (_i, [fp, _i, fp, _i, _i, _i, _i, _f, fp, fp, fp, fp]),
+    "clc_clm_sim_colsum_bwd_workspace_bytes": (_sz, [_i, _i]),
+    "clc_clm_sim_colsum_bwd": (_i, [fp, _i, fp, _i, fp, fp, fp, _i, _i, _i, _f, fp, _i, fp, _i, fp, _sz, fp]),
+    "clc_clm_sigmoid": (_i, [fp, _i, fp, _i, _l, _i, fp]),
+    "clc_clm_scale_rows_bwd": (_i, [fp, _i, fp, _i, fp, fp, fp, _i, _l, _i, fp]),
+    "clc_clm_deform_bwd_workspace_bytes": (_sz, [_i, _i, _i]),
+    "clc_clm_deform_bwd": (_i, [fp, _i, fp, _i, fp, _i, fp, _i, fp, _i, fp, _i, fp, _i, _i, _i, _i, _i, fp, _sz, fp]),
+    "clc_clm_fuse_bwd": (_i, [_pp, _pp, _i, _i, _i, fp, _i, _pp, _i, _pp, _i, _l, _i, _i, fp]),
     "clc_pm_prep": (_i, [fp, fp, _i, _i, _i, _f, fp]),
     "clc_pm_gauss_mask": (_i, [fp, _i, _i, _i, _i, fp]),
     "clc_pm_pearson_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),

@@ -376,7 +376,7 @@ int clc_rd_grad_scalars(const float* g_bpp, const float* g_mse, const float* g_l
 int clc_sqdiff_partials(const float* a, const float* b, long n, float* partials, int n_partials, clc_stream_t stream);
 
 /* ---- Conditional Latent Matching ops (standalone module /root/reference/models/CLM.py) ---- *
- * All tensors NHWC fp32. Forward only (the reference module is an orphan that is never trained).
+ * All tensors NHWC fp32.  The first four are the inference forward; the recorded forward and the backward follow below.
  * clc_clm_sim_colsum: colsum[b][q] = sum_p softmax_q( yt[b,p,:].yrt[b,q,:] / temperature )   (CLM.py:107-109,14-20)
  * clc_clm_scale_rows: out[r][c] = w[r] * x[r][c]                                             (CLM.py:16-22)
  * clc_clm_deform:     9-tap modulated bilinear sampling, zero outside the map               (CLM.py:35-60)
@@ -390,6 +390,41 @@ int clc_clm_deform(const float* x, int ldx, const float* offset, int ldo, const 
                    int ldy, int B, int H, int W, int C, clc_stream_t stream);
 int clc_clm_fuse(const float* const* feats, const float* const* atts, int M, int ldf, int lda, const float* y, int ldy,
                  float* out, int ldo, long rows, int C, int gate, clc_stream_t stream);
+
+/* Recorded forward and backward of the CLM ops (csrc/clm_train.hip).  Stream-ordered, no allocation, no synchronisation, no
+ * floating-point atomics: the same bits on every run.  s[p][q] = yt[p].yrt[q] / temperature, S = softmax_q(s).
+ * clc_clm_sim_colsum_train: colsum as clc_clm_sim_colsum, on v_mfma_f32_32x32x2_f32, plus the row statistics the backward
+ *                           recomputes S from: m[b][p] = max_q s, l[b][p] = sum_q exp(s - m)                (CLM.py:107-109,14-20)
+ *                           Needs C % 4 == 0, C <= 384, HW <= 4096, 16-byte aligned rows.
+ * clc_clm_sim_colsum_bwd:   g = d/d colsum;  D[p] = sum_q S[p][q] g[q],  ds = S (g[q] - D[p]),
+ *                           dyt[p][:] = 1/temperature sum_q ds[p][q] yrt[q][:],  dyrt[q][:] = 1/temperature sum_p ds[p][q] yt[p][:]
+ *                           (differentiates CLM.py:107-109 and the sum of :16-20).  dyt / dyrt NULL: that sweep does not run.
+ * clc_clm_sigmoid:          out = sigmoid(x), the modulation of CLM.py:29 kept for the backward
+ * clc_clm_scale_rows_bwd:   dw[r] = sum_c d[r][c] x[r][c];  dx[r][c] += w[r] d[r][c]  (CLM.py:16-22; dw / dx NULL: not wanted)
+ * clc_clm_deform_bwd:       of out[p][c] = sum_k mod[p][k] valid[p][k] bilinear(x, p + off[p][k])[c]  (CLM.py:35-60), da = d/d out:
+ *                           doff[p][2k+{0,1}] (slope of the bilinear weights inside the cell, cell index constant), dlogit[p][k] =
+ *                           d_mod[p][k] mod (1 - mod) (gradient of the modulation's PRE-sigmoid value; channels 18.. / 9.. of a padded
+ *                           row are zeroed), dx = the scatter, bucketed by destination pixel and summed in source order.
+ *                           doff + dlogit NULL or dx NULL: that part does not run.
+ * clc_clm_fuse_bwd:         of clc_clm_fuse (CLM.py:118-125, SimpleCLM :166-179): wts = softmax_m(att), F_m = feat_m (* sigmoid(att_m)),
+ *                           t_m = sum_c dout[c] F_m[c]:  dfeat_m = wts_m dout (* sigmoid(att_m)),
+ *                           datt_m = wts_m (t_m - sum_m' wts_m' t_m') (+ wts_m (1 - sigmoid(att_m)) t_m);  dy = dout.
+ *                           Columns 1.. of a padded datt row are zeroed. */
+int clc_clm_sim_colsum_train(const float* yt, int ldy, const float* yrt, int ldr, int B, int HW, int C, float temperature,
+                             float* colsum, float* m, float* l, clc_stream_t stream);
+size_t clc_clm_sim_colsum_bwd_workspace_bytes(int B, int HW);
+int clc_clm_sim_colsum_bwd(const float* yt, int ldy, const float* yrt, int ldr, const float* m, const float* l, const float* g,
+                           int B, int HW, int C, float temperature, float* dyt, int lddyt, float* dyrt, int lddyr, void* ws,
+                           size_t ws_bytes, clc_stream_t stream);
+int clc_clm_sigmoid(const float* x, int ldx, float* out, int ldo, long rows, int C, clc_stream_t stream);
+int clc_clm_scale_rows_bwd(const float* d, int ldd, const float* x, int ldx, const float* w, float* dw, float* dx, int lddx,
+                           long rows, int C, clc_stream_t stream);
+size_t clc_clm_deform_bwd_workspace_bytes(int B, int H, int W);
+int clc_clm_deform_bwd(const float* x, int ldx, const float* offset, int ldo, const float* modulation, int ldm, const float* da,
+                       int lda, float* doff, int lddo, float* dlogit, int lddl, float* dx, int lddx, int B, int H, int W, int C,
+                       void* ws, size_t ws_bytes, clc_stream_t stream);
+int clc_clm_fuse_bwd(const float* const* feats, const float* const* atts, int M, int ldf, int lda, const float* dout, int lddo,
+                     float* const* dfeats, int lddf, float* const* datts, int ldda, long rows, int C, int gate, clc_stream_t stream);
 
 /* ---- patch-matching side information (numeric core of /root/reference/models/Patch_Matching.py) ---- *
  * Planar NCHW fp32 (3-channel images), forward only.
