@@ -233,6 +233,11 @@ SIGNATURES = {
     "clc_ref_prepare": (_i, [fp, _i, _i, _i, fp, fp]),
     "clc_gather_slots": (_i, [fp, _l, _i, fp, _i, _i, fp, fp]),
     "clc_fingerprint": (_i, [fp, _i, fp, _i, fp, fp]),
+    "clc_kmeans_assign": (_i, [fp, _i, _i, _i, fp, _i, _i, fp, fp, fp, fp]),
+    "clc_kmeans_update_workspace_bytes": (_sz, [_i, _i, _i]),
+    "clc_kmeans_update": (_i, [fp, _i, _i, _i, fp, fp, _i, fp, _i, fp, _i, fp, fp, _sz, fp]),
+    "clc_kmeans_representatives_workspace_bytes": (_sz, [_i]),
+    "clc_kmeans_representatives": (_i, [fp, _i, _i, _i, fp, fp, fp, _i, _i, fp, fp, _sz, fp]),
 }
 
 

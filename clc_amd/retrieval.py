@@ -10,7 +10,8 @@ Here the bank lives in HBM and a whole batch of queries is answered by one GEMM 
 (scores = 2 q.r - |r|^2, the 1x1-convolution path of libclc_hip.so) plus the tie-stable top-k kernel of the patch-matching
 module (clc_pm_topk: equal scores -> lowest index, like a stable sort of the distances).  Clustering itself stays the
 reference's own sklearn call (same estimator, same random_state) so that the representatives are the reference's; the
-member-closest-to-centre step runs on the device.
+member-closest-to-centre step runs on the device.  `method="device"` is the opt-in alternative that never leaves the GPU: full-batch
+Lloyd k-means on the kernels of clc_amd.kmeans (its representatives are NOT the reference's).
 """
 from __future__ import annotations
 
@@ -26,9 +27,9 @@ from .ops import _L, _stream
 
 class ReferenceIndex:
     def __init__(self, ref_features, feature_to_key: Optional[Dict[int, str]] = None, n_clusters: Optional[int] = None, n_refs: int = 1,
-                 device="cuda", extractor: Optional[Callable] = None):
+                 device="cuda", extractor: Optional[Callable] = None, cluster_method: str = "sklearn"):
         """ref_features [N, D] (numpy / tensor), feature_to_key {row -> key} as the reference's pickle holds them
-        (dataloader_ref_cluster.py:89-104)."""
+        (dataloader_ref_cluster.py:89-104).  cluster_method: how n_clusters thins the bank (cluster_features' `method`)."""
         if not 1 <= n_refs <= 8:
             raise ValueError("n_refs must be in 1..8")
         self.device = torch.device(device)
@@ -40,15 +41,34 @@ class ReferenceIndex:
         self.feature_to_key = dict(feature_to_key) if feature_to_key is not None else {i: i for i in range(feats.shape[0])}
         self._set_bank(feats.to(self.device))
         if n_clusters:
-            self.cluster_features(int(n_clusters))
+            self.cluster_features(int(n_clusters), method=cluster_method)
 
     def _set_bank(self, feats):
         self.ref_features = feats.contiguous()
         self.sqnorm = (self.ref_features.double() ** 2).sum(1).float()     # |r|^2 once per bank (double: exact to fp32 rounding)
 
     # ---- thinning: MiniBatchKMeans representatives (dataloader_ref_cluster.py:106-144)
-    def cluster_features(self, n_clusters: int, labels=None, centers=None):
-        """labels / centers: precomputed clustering (tests); default: the reference's estimator on the host."""
+    def cluster_features(self, n_clusters: int, labels=None, centers=None, method: str = "sklearn", **kmeans_kw):
+        """labels / centers: precomputed clustering (tests); default: the reference's estimator on the host.
+
+        method="sklearn" (default): MiniBatchKMeans(random_state=42, batch_size=1000) on a host copy of the bank, as the reference does.
+        method="device": clc_amd.kmeans.DeviceKMeans(n_clusters, **kmeans_kw) on the resident bank, then kmeans_representatives: nothing
+        leaves the GPU but the list of representatives.  These are NOT the reference's representatives: the algorithm (full-batch Lloyd
+        instead of mini-batch) and the initialisation (sampled rows instead of k-means++) both differ.  Empty clusters are skipped and
+        representatives stay in cluster order, as in the default path."""
+        if method not in ("sklearn", "device"):
+            raise ValueError(f"method must be 'sklearn' or 'device', got {method!r}")
+        if method == "device":
+            if labels is not None or centers is not None:
+                raise ValueError("method='device' computes its own clustering: labels / centers cannot be given")
+            from .kmeans import DeviceKMeans, kmeans_representatives
+
+            km = self.kmeans_ = DeviceKMeans(n_clusters, **kmeans_kw).fit(self.ref_features)   # kept for inspection (labels_, counts_, ...)
+            rep = kmeans_representatives(self.ref_features, km.labels_, km.cluster_centers_).cpu().tolist()
+            self._set_representatives([j for j in rep if j >= 0])
+            return
+        if kmeans_kw:
+            raise TypeError(f"method='sklearn' takes no estimator arguments, got {sorted(kmeans_kw)}")
         if labels is None:
             from sklearn.cluster import MiniBatchKMeans
 
@@ -72,6 +92,13 @@ class ReferenceIndex:
         self.representatives = reps
         self.feature_to_key = keys
         self._set_bank(self.ref_features[torch.as_tensor(reps, device=self.device)])
+
+    def _set_representatives(self, reps):
+        """Thin the bank to the rows `reps` (in this order) and renumber the keys.  The sklearn path above ends in the same three steps
+        inline (its loop builds the keys as it goes); keep the two in step."""
+        self.feature_to_key = {n: self.feature_to_key[j] for n, j in enumerate(reps)}
+        self.representatives = list(reps)
+        self._set_bank(self.ref_features[torch.as_tensor(reps, device=self.device, dtype=torch.long)])
 
     # ---- search
     def _scores(self, q, bank, bank_sqnorm):

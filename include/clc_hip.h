@@ -649,6 +649,26 @@ int clc_ref_prepare(const clc_ref_src* table, int N, int h, int w, float* out, c
 int clc_gather_slots(const float* arena, long slot_elems, int n_slots, const int32_t* idx, int B, int R, float* out, clc_stream_t stream);
 int clc_fingerprint(const clc_fp_entry* table, int n, uint64_t* partials, int n_partials, uint64_t* out, clc_stream_t stream);
 
+/* ---- full-batch Lloyd k-means for the reference-retrieval dictionary (clc_amd/kmeans.py, kmeans.hip) ----
+ * x [N][D] f32 rows (ldx), c [K][D] centres (ldc): rows 16-byte aligned, ld >= D and a multiple of 4, D >= 4 a multiple of 4 (no upper
+ * bound: the D loop is chunked), 1 <= K <= N (clc_kmeans_assign: any K >= 1).  Stream-ordered, allocation-free, sync-free; every sum has a fixed order (same bits on every run).
+ * clc_kmeans_assign           label[i] = argmin_k (c_sqnorm[k] - 2 x_i.c_k) on v_mfma_f32_32x32x2_f32, equal scores -> lowest k (the tie rule of
+ *                             clc_pm_topk); score[i] = that minimum, so |x_i - c_label|^2 = |x_i|^2 + score[i].  [N][K] is never written.
+ * clc_kmeans_update           c_out[k] = mean of the rows with label k, counts[k] = their number; an empty cluster copies prev_c[k] bit for bit.
+ *                             order [N] = the row indices sorted by label, rows of one label ascending (a stable sort of label); lists longer than
+ *                             512 rows are summed in 512-row chunks by separate waves, the partials added in chunk order.  Labels must lie
+ *                             in [0, K) (anything else: unspecified centres, but no access outside the buffers).  ws: clc_kmeans_update_workspace_bytes(N, D, K), 16-byte aligned.
+ * clc_kmeans_representatives  rep[k] = the row with label k that minimises sum_d (x - c_k)^2 (f32, lanes over columns), the lowest row on a tie;
+ *                             -1 for an empty cluster.  ws: clc_kmeans_representatives_workspace_bytes(K). */
+int clc_kmeans_assign(const float* x, int ldx, int N, int D, const float* c, int ldc, int K, const float* c_sqnorm, int32_t* label, float* score,
+                      clc_stream_t stream);
+size_t clc_kmeans_update_workspace_bytes(int N, int D, int K);
+int clc_kmeans_update(const float* x, int ldx, int N, int D, const int32_t* label, const int32_t* order, int K, const float* prev_c, int ldp,
+                      float* c_out, int ldc, int32_t* counts, void* ws, size_t ws_bytes, clc_stream_t stream);
+size_t clc_kmeans_representatives_workspace_bytes(int K);
+int clc_kmeans_representatives(const float* x, int ldx, int N, int D, const int32_t* label, const int32_t* order, const float* c, int ldc, int K,
+                               int32_t* rep, void* ws, size_t ws_bytes, clc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
