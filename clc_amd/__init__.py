@@ -6,7 +6,7 @@ def set_precision(mode: str = "f32") -> str:
     16x16): "f32" (default: exact f32 MFMA — the mode every parity bar and the headline benchmark are stated in) or "bf16"
     (opt-in reduced precision, the counterpart of the reference's --use-mixed-precision branch, /root/reference/train_CLC.py:143-174:
     operands rounded to bf16 at fragment read, f32 accumulation, f32 tensors in HBM).  The entropy-parameter networks on the 16x16
-    latents, the likelihoods, the codec and the optimizer stay f32 in both modes.  Process-wide (one clc_set_tuning switch); set it
+    latents, the likelihoods, the codec, the optimizer and every 5x5 layer (csrc/conv5.hip has no bf16 instantiation) stay f32 in both modes.  Process-wide (one clc_set_tuning switch); set it
     BEFORE a TrainEngine captures its hipGraph.  Returns the previous mode."""
     from . import lib as _lib
 

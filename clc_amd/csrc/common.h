@@ -42,6 +42,10 @@ extern int clc_tuning[CLC_TUNE_COUNT];
 int clc_conv_halo_launch(const void* conv_params, const float* wpk, hipStream_t st);
 // conv_wino.hip: 0 = the launch does not qualify
 int clc_conv_wino_launch(const void* conv_params, const float* u, hipStream_t st);
+// conv5.hip: clc_conv2d / clc_conv2d_wgrad with ks == 5 (own validation; the filter gradient is launched in line, never grouped)
+int clc_conv5_launch(const clc_conv_desc* d, hipStream_t st);
+size_t clc_conv5_wgrad_workspace_bytes(const clc_wgrad_desc* d);
+int clc_conv5_wgrad_launch(const clc_wgrad_desc* d, hipStream_t st);
 int clc_lin_launch(const float* x, int ldx, const float* w, const float* bias, const float* res, int ldr, float res_scale, float* y, int ldy, long M, int Cin,
                    int Cout, hipStream_t st);
 

@@ -1124,7 +1124,7 @@ static void use_split(ConvParams& p, const clc_conv_desc* d, int classes) {
 // validates a descriptor and fills the kernel parameters (shared by clc_conv2d and clc_conv2d_workspace_bytes)
 static int fill_params(const clc_conv_desc* d, ConvParams& p, int& classes) {
   CLC_CHECK(d && d->x && d->w && d->y, "clc_conv2d: null pointer");
-  CLC_CHECK(d->ks == 1 || d->ks == 3, "clc_conv2d: ks must be 1 or 3 (got %d)", d->ks);
+  CLC_CHECK(d->ks == 1 || d->ks == 3, "clc_conv2d: ks must be 1, 3 or 5 (got %d)", d->ks);
   CLC_CHECK(d->stride == 1 || d->stride == 2, "clc_conv2d: stride must be 1 or 2 (got %d)", d->stride);
   CLC_CHECK(d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 && d->OH > 0 && d->OW > 0, "clc_conv2d: bad dims");
   CLC_CHECK(d->ldx >= d->Cin, "clc_conv2d: ldx < Cin");
@@ -1192,7 +1192,7 @@ static int fill_params(const clc_conv_desc* d, ConvParams& p, int& classes) {
 }
 
 extern "C" size_t clc_conv2d_workspace_bytes(const clc_conv_desc* d) {
-  if (!d) return 0;
+  if (!d || d->ks == 5) return 0;   // (the 5x5 kernels never split K)
   ConvParams p;
   int classes = 1;
   if (fill_params(d, p, classes) < 0) return 0;
@@ -1206,6 +1206,7 @@ extern "C" size_t clc_conv2d_workspace_bytes(const clc_conv_desc* d) {
 
 extern "C" int clc_conv2d(const clc_conv_desc* d, clc_stream_t stream) {
   hipStream_t st = (hipStream_t)stream;
+  if (d && d->ks == 5) return clc_conv5_launch(d, st);   // conv5.hip: a kernel family of its own, nothing below sees 25 taps
   ConvParams p;
   int classes = 1;
   if (fill_params(d, p, classes) < 0) return -1;

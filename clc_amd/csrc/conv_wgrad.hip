@@ -1128,6 +1128,7 @@ Plan make_plan(const clc_wgrad_desc* d) {
 
 extern "C" size_t clc_conv2d_wgrad_workspace_bytes(const clc_wgrad_desc* d) {
   if (!d) return 0;
+  if (d->ks == 5) return clc_conv5_wgrad_workspace_bytes(d);
   Plan pl = make_plan(d);
   const size_t wsz = (size_t)d->Cout * d->ks * d->ks * d->Cin;
   return ((size_t)pl.splits * (wsz + d->Cout) + 64) * sizeof(float);
@@ -1140,7 +1141,7 @@ namespace {
 // small-Cin split path)
 int prepare(const clc_wgrad_desc* d, Plan& pl, WgradParams& p, bool sk = false) {
   CLC_CHECK(d && d->x && d->dy && d->dw, "clc_conv2d_wgrad: null pointer");
-  CLC_CHECK(d->ks == 1 || d->ks == 3, "clc_conv2d_wgrad: ks must be 1 or 3");
+  CLC_CHECK(d->ks == 1 || d->ks == 3, "clc_conv2d_wgrad: ks must be 1 or 3 here (ks = 5 problems are launched in line by clc_conv2d_wgrad, never grouped)");
   CLC_CHECK(d->stride == 1 || d->stride == 2, "clc_conv2d_wgrad: stride must be 1 or 2");
   CLC_CHECK(d->OH == (d->H + 2 * d->pad - d->ks) / d->stride + 1 && d->OW == (d->W + 2 * d->pad - d->ks) / d->stride + 1,
             "clc_conv2d_wgrad: output dims inconsistent");
@@ -1438,6 +1439,7 @@ int variant_id(const Plan& pl) { return pl.small ? 1 : (pl.taps ? 64900 + pl.tap
 }  // namespace
 
 extern "C" int clc_conv2d_wgrad(const clc_wgrad_desc* d, clc_stream_t stream) {
+  if (d && d->ks == 5) return clc_conv5_wgrad_launch(d, (hipStream_t)stream);   // conv5.hip
   Pending e;
   e.d = d;
   int rc = prepare(d, e.pl, e.p);
@@ -1467,6 +1469,7 @@ extern "C" int clc_conv2d_wgrad_batched(const clc_wgrad_desc* descs, int count, 
 
 extern "C" int clc_conv2d_wgrad_variant(const clc_wgrad_desc* d) {
   if (!d) return -1;
+  if (d->ks == 5) return 5;   // conv5_wgrad_kernel: in line only (the grouped launches refuse it)
   return variant_id(make_plan(d));
 }
 
@@ -1474,6 +1477,7 @@ extern "C" size_t clc_conv2d_wgrad_group_workspace_bytes(void) { return sk_total
 
 extern "C" size_t clc_conv2d_wgrad_sk_workspace_bytes(const clc_wgrad_desc* d) {
   if (!d) return 0;
+  if (d->ks == 5) return clc_conv5_wgrad_workspace_bytes(d);
   if (clc_tuning[CLC_TUNE_WGRAD_STREAMK] && !make_plan(d).small) return 0;   // partial tiles go to the group workspace
   return clc_conv2d_wgrad_workspace_bytes(d);
 }

@@ -66,8 +66,9 @@ class Conv2d(nn.Conv2d):
 
     def __init__(self, in_ch, out_ch, kernel_size, stride=1, padding=None, bias=True):
         padding = kernel_size // 2 if padding is None else padding
-        if kernel_size not in (1, 3) or padding != kernel_size // 2 or stride not in (1, 2):
-            raise ValueError("clc_amd.layers.Conv2d supports 1x1 / 3x3 'same' convolutions with stride 1 or 2")
+        if kernel_size not in (1, 3, 5) or padding != kernel_size // 2 or stride not in (1, 2):
+            raise ValueError(f"clc_amd.layers.Conv2d supports 1x1 / 3x3 / 5x5 'same' convolutions with stride 1 or 2 (got kernel_size={kernel_size}, "
+                             f"padding={padding}, stride={stride})")
         super().__init__(in_ch, out_ch, kernel_size, stride=stride, padding=padding, bias=bias)
         self.weight.data = self.weight.data.contiguous(memory_format=CL)
         self.weight._clc_is_filter = True
@@ -76,6 +77,17 @@ class Conv2d(nn.Conv2d):
                 grad_slot=None, park_dx=None, gate_in=None, gate_out=None):
         """pair: a second Conv2d of the same shape applied to the second half of the batch in the same launch — or a tuple of three:
         this layer and they take one quarter of the batch each.  fold_in / fold_out: ops.GradFold of a residual block (see there)."""
+        if self.kernel_size[0] == 5 and self.in_channels % 4:
+            # few-channel input (the RGB head of the hyperprior analysis transforms): the aligned loaders of the 5x5 kernel need
+            # Cin % 4 == 0.  As the 3x3 stems do: patch rows (25 Cin values padded to a multiple of 4), then a 1x1 convolution over
+            # them on the MFMA kernel, whose own gradient kernels give dw / db.  The image itself gets no gradient.
+            if res is not None or shuffle or pair is not None or fold_in is not None or fold_out is not None or out is not None:
+                raise ValueError("clc_amd.layers.Conv2d: a 5x5 layer with Cin % 4 != 0 takes bias and activation only (no res / shuffle / pair / fold / out)")
+            if x.requires_grad:
+                raise ops._lib.ClcError("clc_amd.layers.Conv2d: a 5x5 layer with Cin % 4 != 0 (RGB head) has no input gradient; detach the image")
+            ldc = (25 * self.in_channels + 3) // 4 * 4
+            col = ops.im2col_small(x, 5, self.stride[0], ldc)
+            return ops.linear(col, ops.patch_filter(ops.to_kernel_weight(self.weight), ldc), self.bias, act=act)
         wx = None
         if isinstance(pair, (tuple, list)):
             pair, q3, q4 = pair
@@ -84,6 +96,37 @@ class Conv2d(nn.Conv2d):
                           res_first=res_first, shuffle=shuffle, w2=pair.weight if pair is not None else None,
                           b2=pair.bias if pair is not None else None, fold_in=fold_in, fold_out=fold_out, out=out, grad_slot=grad_slot,
                           park_dx=park_dx, gate_in=gate_in, gate_out=gate_out, wx=wx)
+
+
+class ConvTranspose2d(nn.ConvTranspose2d):
+    """nn.ConvTranspose2d(in, out, 5, stride=2, padding=2, output_padding=1) — CompressAI's ``deconv`` — with torch's parameter names and
+    [in, out, 5, 5] shape (kept channels_last = [in][kh][kw][out]); forward on the transposed 5x5 kernel (ops.conv_transpose5)."""
+
+    def __init__(self, in_ch, out_ch, kernel_size=5, stride=2, padding=2, output_padding=1, bias=True):
+        if (kernel_size, stride, padding, output_padding) != (5, 2, 2, 1):
+            raise ValueError("clc_amd.layers.ConvTranspose2d supports kernel_size=5, stride=2, padding=2, output_padding=1 only "
+                             f"(got kernel_size={kernel_size}, stride={stride}, padding={padding}, output_padding={output_padding})")
+        if in_ch % 4:
+            raise ValueError(f"clc_amd.layers.ConvTranspose2d: in_channels must be a multiple of 4 (got {in_ch})")
+        super().__init__(in_ch, out_ch, kernel_size, stride=stride, padding=padding, output_padding=output_padding, bias=bias)
+        self.weight.data = self.weight.data.contiguous(memory_format=CL)
+
+    def forward(self, x, act=ACT_NONE):
+        return ops.conv_transpose5(x, self.weight, self.bias, act=act)
+
+
+def conv(in_channels, out_channels, kernel_size=5, stride=2):
+    """CompressAI's ``conv`` helper: a 'same' convolution, 5x5 / stride 2 by default."""
+    return Conv2d(in_channels, out_channels, kernel_size, stride=stride, padding=kernel_size // 2)
+
+
+def deconv(in_channels, out_channels, kernel_size=5, stride=2):
+    """CompressAI's ``deconv`` helper: ConvTranspose2d(k, s, padding=k // 2, output_padding=s - 1); (3, 1) is the plain 3x3 layer
+    (a stride-1 'same' transposed convolution is a convolution with the flipped, channel-swapped filter: build that one yourself
+    if a checkpoint must load — here it is a fresh layer)."""
+    if (kernel_size, stride) == (3, 1):
+        return Conv2d(in_channels, out_channels, 3, stride=1)
+    return ConvTranspose2d(in_channels, out_channels, kernel_size, stride=stride, padding=kernel_size // 2, output_padding=stride - 1)
 
 
 class Linear(nn.Linear):

@@ -877,7 +877,8 @@ class _ConvFn(Function):
         gw, gb = _direct_grad(w), (_direct_grad(bias_ref) if has_b else None)
         if gw is not None and (gb is not None or not has_b) and to_kernel_weight(w) is w:
             # write straight into the persistent gradient arena (accumulate) — no temporary, no autograd add kernel
-            wgrad_raw(x, dz, ks=ks, stride=stride, pad=pad, Cout=Cout, Cin=Cin, want_bias=has_b, dw_out=gw, db_out=gb, defer=WGRAD_DEFER, **fw)
+            wgrad_raw(x, dz, ks=ks, stride=stride, pad=pad, Cout=Cout, Cin=Cin, want_bias=has_b, dw_out=gw, db_out=gb,
+                      defer=WGRAD_DEFER and ks != 5, **fw)   # (5x5 problems are launched in line: the grouped launches refuse them)
             return None, None
         dwf, db = wgrad_raw(x, dz, ks=ks, stride=stride, pad=pad, Cout=Cout, Cin=Cin, want_bias=need_b, **fw)
         return (_dw_to_param_layout(dwf, w) if need_w else None), db
@@ -902,6 +903,8 @@ class _ConvFn(Function):
         gate_park = (need_res and res_first and not shuffle and act in (ACT_LRELU, ACT_RELU) and fold_out is not None
                      and fold_out.gated and fold_out.can_park())
         fuse = act in (ACT_LRELU, ACT_RELU, ACT_SAVED_DERIV) and not shuffle and (not (need_res and res_first) or gate_park)
+        if ks == 5:
+            fuse = False   # the 5x5 kernels (csrc/conv5.hip) have no fused-derivative loaders: dz is materialised by the act_bwd pass
         # Large-map 3x3 layers whose derivative no consumer applied (ActGate): ONE elementwise pass dz = dy * act'(.) and then the
         # LDS-DMA data- and filter-gradient kernels beat the fused loaders of the register-staged ones (64 -> 64 @ 8x128x128:
         # 160 + 119 us fused vs 22 + 106 + 102 us)
@@ -984,6 +987,79 @@ def conv2d(x, w, b=None, *, stride=1, act=ACT_NONE, res=None, res_scale=1.0, shu
     _note_grad_mode()
     return _ConvFn.apply(x, w, b, res, ks, stride, act, float(res_scale), bool(shuffle), bool(res_first), w2, b2, fold_in, fold_out, out,
                          grad_slot, park_dx, gate_in, gate_out, w3, b3, w4, b4)
+
+
+def colsum(x):
+    """[C] column sums of a pixel-major [N,C,H,W] tensor over its pixels (clc_colsum: two-stage, fixed order)."""
+    x, xp, N, H, W, Cc, ld = nhwc(x)
+    nb = _L().clc_colsum_workspace_bytes(N * H * W, Cc)
+    ws = torch.empty((nb + 3) // 4, device=x.device, dtype=torch.float32)
+    out = torch.empty(Cc, device=x.device, dtype=torch.float32)
+    _lib.check(_L().clc_colsum(xp, ld, N * H * W, Cc, out.data_ptr(), 0, ws.data_ptr(), nb, _stream()), "clc_colsum")
+    return out
+
+
+def patch_filter(wk, ldc):
+    """kernel-layout filter [rows][5][5][c] -> the [rows][ldc] matrix of the patch-row formulation (columns 25 c .. ldc - 1 zero).
+    Plain tensor ops on the parameter, so autograd carries the matrix's gradient back to it."""
+    rows = wk.shape[0]
+    m = wk.permute(0, 2, 3, 1).reshape(rows, -1)
+    return torch.nn.functional.pad(m, (0, ldc - m.shape[1]))
+
+
+class _ConvTranspose5Fn(Function):
+    """y = act(conv_transpose2d(x, w, stride=2, padding=2, output_padding=1) + b), w = [in, out, 5, 5]: the DATA GRADIENT of the 5x5 /
+    stride-2 convolution whose OIHW filter w is (Cout = in, Cin = out), on the transposed 5x5 kernel (csrc/conv5.hip).
+    Backward: dx = that forward convolution of dz, dw = its filter gradient with the roles of input and output swapped, db = column
+    sums of dz.  Fewer than 4 (or not a multiple of 4) output channels — the RGB tail — cannot feed the aligned loaders: both
+    gradients then go through the patch rows of dz (clc_im2col_small, 25 out values padded to a multiple of 4) and the 1x1 kernels."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, act):
+        _own(ctx)
+        if x.dim() != 4 or x.shape[1] != w.shape[0]:
+            raise _lib.ClcError(f"conv_transpose2d: input {tuple(x.shape)} does not match the filter {tuple(w.shape)} (expected {w.shape[0]} input channels)")
+        cin, cout = w.shape[0], w.shape[1]
+        wk = to_kernel_weight(w)   # [in][5][5][out]
+        wt = filter_transpose(wk, cin, 25, cout)   # [out][25][in]
+        N, _, H, W = x.shape
+        y = conv_raw(x, wt, b, ks=5, stride=2, pad=2, transposed=True, out_hw=(2 * H, 2 * W), act=act)
+        ctx.act, ctx.has_b = act, b is not None
+        ctx.save_for_backward(x, w, y if (act != ACT_NONE and _recording(ctx)) else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        _reown(ctx)
+        x, w, y = ctx.saved_tensors
+        cin, cout = w.shape[0], w.shape[1]
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_b and ctx.needs_input_grad[2]
+        dz = dy if ctx.act == ACT_NONE else act_bwd(dy, y, False, ctx.act)
+        wk = to_kernel_weight(w)
+        dx = dw = db = None
+        if cout % 4 == 0:
+            if need_x:
+                dx = conv_raw(dz, wk, None, ks=5, stride=2, pad=2)
+            if need_w:
+                dwf, _ = wgrad_raw(dz, x, ks=5, stride=2, pad=2, Cout=cin, Cin=cout, want_bias=False)
+                dw = _dw_to_param_layout(dwf, w)
+        elif need_x or need_w:
+            ldc = (25 * cout + 3) // 4 * 4
+            col = im2col_small(dz.detach(), 5, 2, ldc)
+            if need_x:
+                dx = conv_raw(col, patch_filter(wk.detach(), ldc).contiguous(), None, ks=1)
+            if need_w:
+                dwf, _ = wgrad_raw(col, x, ks=1, stride=1, pad=0, Cout=cin, Cin=ldc, want_bias=False)
+                dw = dwf.view(cin, ldc)[:, : 25 * cout].reshape(cin, 5, 5, cout).permute(0, 3, 1, 2)
+        if need_b:
+            db = colsum(dz)
+        return dx, dw, db, None
+
+
+def conv_transpose5(x, w, b=None, *, act=ACT_NONE):
+    _require_gpu(x, "conv_transpose2d")
+    _note_grad_mode()
+    return _ConvTranspose5Fn.apply(x, w, b, act)
 
 
 # Inside Function.forward grad mode is always off and ctx.needs_input_grad only reflects the inputs' requires_grad flags — under

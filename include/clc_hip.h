@@ -78,7 +78,11 @@ typedef struct {
   const float* w;            /* [Cout][ks][ks][Cin] */
   const float* bias;         /* [Cout] or NULL */
   float* y; int OH, OW, Cout, ldy;
-  int ks, stride, pad;
+  int ks, stride, pad;       /* ks = 1 | 3 (pad = ks / 2 in every caller), or 5 with pad = 2: the 5x5 kernels of csrc/conv5.hip — forward and
+                              * transposed, stride 1 or 2, on the aligned path only (Cin % 4 == 0, ldx % 4 == 0, 16-byte aligned x / w; any Cout),
+                              * with bias, act = none / ReLU / LeakyReLU, ldx / ldy; every other optional field below is refused by name.
+                              * The K order of an output element depends on (Cin, map size) alone, as for the other kernels; no workspace;
+                              * f32 in the bf16 precision mode too. */
   int transposed;
   int in_op;
   int act;
@@ -159,7 +163,8 @@ typedef struct {
   const float* x; int N, H, W, Cin, ldx;
   const float* dy; int OH, OW, Cout, lddy;
   float* dw; float* dbias;
-  int ks, stride, pad;
+  int ks, stride, pad;       /* ks = 5 (pad 2): one single-pass launch per problem (csrc/conv5.hip), in clc_conv2d_wgrad only — the grouped
+                              * entry points refuse it, clc_conv2d_wgrad_variant returns 5; no dys / in_op; Cin % 4 == 0; workspace for dbias only */
   int in_op;
   int accumulate;
   void* workspace; size_t workspace_bytes;
