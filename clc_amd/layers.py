@@ -129,6 +129,27 @@ def deconv(in_channels, out_channels, kernel_size=5, stride=2):
     return ConvTranspose2d(in_channels, out_channels, kernel_size, stride=stride, padding=kernel_size // 2, output_padding=stride - 1)
 
 
+class MaskedConv2d(Conv2d):
+    """CompressAI's ``MaskedConv2d`` (the context model of the autoregressive priors): a 5x5 'same' convolution whose filter is multiplied
+    by a causal mask — type A keeps the two rows above the centre and the two taps left of it, 12 of 25.  Parameter names ``weight`` /
+    ``bias`` and a registered ``mask`` buffer of the weight's shape, so ``<name>.mask`` is a ``state_dict`` key as in published checkpoints.
+    As the published layer does, forward multiplies ``weight.data`` by the mask in place and then convolves with the (now masked) filter;
+    the masked taps' gradients are whatever the filter gradient of an unmasked layer gives.  Runs on the 5x5 stride-1 kernel."""
+
+    def __init__(self, in_ch, out_ch, kernel_size=5, padding=2, stride=1, mask_type="A", bias=True):
+        if mask_type != "A" or kernel_size != 5 or padding != 2 or stride != 1:
+            raise ValueError("clc_amd.layers.MaskedConv2d supports mask_type='A' with kernel_size=5, padding=2, stride=1 only "
+                             f"(got mask_type={mask_type!r}, kernel_size={kernel_size}, padding={padding}, stride={stride})")
+        super().__init__(in_ch, out_ch, 5, stride=1, padding=2, bias=bias)
+        self.register_buffer("mask", torch.ones_like(self.weight.data))
+        self.mask[:, :, 2, 2:] = 0
+        self.mask[:, :, 3:] = 0
+
+    def forward(self, x, act=ACT_NONE):
+        self.weight.data *= self.mask
+        return super().forward(x, act=act)
+
+
 class Linear(nn.Linear):
     """nn.Linear over the channel dim of a pixel-major [N,C,H,W] tensor (tokens are pixels)."""
 

@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("CLC_LIB_PATH") or os.path.join(_HERE, "libclc_hip.so"
 ACT_NONE, ACT_LRELU, ACT_RELU, ACT_GELU, ACT_HALFTANH, ACT_SIGMOID, ACT_SAVED_DERIV = 0, 1, 2, 3, 4, 5, 6
 IN_NONE, IN_SQUARE = 0, 1
 NORM_NONE, NORM_GDN, NORM_IGDN, NORM_MUL2 = 0, 1, 2, 3
+AR_SRC_DENSE, AR_SRC_PIXEL, AR_SRC_TAPS = 0, 1, 2
+AR_ENCODE, AR_DECODE = 0, 1
 
 fp = C.c_void_p  # device / host pointers are passed as integers (tensor.data_ptr())
 
@@ -104,6 +106,10 @@ class RefSrc(C.Structure):
 
 class FpEntry(C.Structure):
     _fields_ = [("ptr", fp), ("nbytes", C.c_uint64), ("word_offset", C.c_int64)]
+
+
+class ArSrc(C.Structure):
+    _fields_ = [("p", fp), ("ld", C.c_int), ("C", C.c_int), ("kind", C.c_int)]
 
 
 class ParamEntry(C.Structure):
@@ -238,6 +244,9 @@ SIGNATURES = {
     "clc_kmeans_update": (_i, [fp, _i, _i, _i, fp, fp, _i, fp, _i, fp, _i, fp, fp, _sz, fp]),
     "clc_kmeans_representatives_workspace_bytes": (_sz, [_i]),
     "clc_kmeans_representatives": (_i, [fp, _i, _i, _i, fp, fp, fp, _i, _i, fp, fp, _sz, fp]),
+    "clc_ar_linear": (_i, [C.POINTER(ArSrc), _i, fp, _i, _i, _i, _i, fp, fp, _i, _i, fp, _i, fp]),
+    "clc_ar_finish": (_i, [fp, _i, _i, fp, _i, _i, _i, _i, fp, _i, fp, _i, fp, _i, fp, fp, _i, fp]),
+    "clc_ar_commit": (_i, [fp, fp, _i, _i, fp, _i, _i, _i, _i, fp, _i, fp]),
 }
 
 

@@ -18,7 +18,7 @@ import torch.nn as nn
 
 from .. import ans, ops
 from ..entropy_models import EntropyBottleneck, GaussianConditional
-from ..layers import GDN, conv, deconv
+from ..layers import GDN, Conv2d, MaskedConv2d, conv, deconv
 from ..ops import ACT_LRELU, ACT_NONE, ACT_RELU, CL
 from .clc import CompressionModel, _resize_registered_buffers, get_scale_table
 
@@ -169,3 +169,176 @@ class MeanScaleHyperprior(ScaleHyperprior):
     def _params(self, z_hat):
         scales_hat, means_hat = self._hyper_synthesis(z_hat).chunk(2, 1)
         return scales_hat, means_hat
+
+
+def ar_schedule(H, W, order="wavefront"):
+    """The steps of the autoregressive pass over an H x W latent, each a list of (h, w).  Under mask A pixel (h, w) reads rows h - 2 and
+    h - 1 at columns w - 2 .. w + 2 and row h at columns w - 2 and w - 1, so all pixels of equal t = w + 3 h are independent:
+    ``"wavefront"`` returns the W + 3 (H - 1) steps t = 0, 1, ... (for W < 3 some are empty), ``"raster"`` one pixel per step."""
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"ar_schedule: H and W must be positive (got {H}, {W})")
+    if order == "raster":
+        return [[(h, w)] for h in range(H) for w in range(W)]
+    if order != "wavefront":
+        raise ValueError(f"ar_schedule: order must be 'wavefront' or 'raster' (got {order!r})")
+    steps = [[] for _ in range(W + 3 * (H - 1))]
+    for h in range(H):
+        for w in range(W):
+            steps[w + 3 * h].append((h, w))
+    return steps
+
+
+class JointAutoregressiveHierarchicalPriors(MeanScaleHyperprior):
+    """Minnen et al. 2018 with the context model (``mbt2018``): the mean-scale hyperprior plus a masked 5x5 convolution over the coded
+    latent and a three-layer 1x1 ``entropy_parameters`` net on cat((hyper parameters, context)).
+
+    forward runs the full-map kernels.  The coder is sequential in the latent: per pixel, gather the 12 live taps -> M -> 2M -> (with the
+    pixel's hyper parameters) 4M -> 10M/3 -> 8M/3 -> 2M -> quantise / index, on the row kernels of csrc/ar_context.hip, whose summation
+    order depends on K alone — an encoder step of many pixels and a decoder step of one give the same bits.  compress runs the
+    wavefront schedule (W + 3 (H - 1) steps) and serialises in CompressAI's raster-pixel, channel-inner order; decompress must follow the
+    stream, one raster pixel at a time for the whole batch."""
+
+    def __init__(self, N=192, M=192, **kwargs):
+        if M % 12:
+            raise ValueError(f"JointAutoregressiveHierarchicalPriors needs M % 12 == 0 (then 10M/3, 8M/3 and 3M/2 are whole and multiples of 4, the "
+                             f"kernels' aligned path); got M = {M}" + (": M = 320 (mbt2018 qualities 5-8) is not built" if M == 320 else ""))
+        super().__init__(N=N, M=M, **kwargs)
+        self.entropy_parameters = nn.Sequential(Conv2d(M * 4, M * 10 // 3, 1), nn.LeakyReLU(inplace=True),
+                                                Conv2d(M * 10 // 3, M * 8 // 3, 1), nn.LeakyReLU(inplace=True),
+                                                Conv2d(M * 8 // 3, M * 2, 1))
+        self.context_prediction = MaskedConv2d(M, 2 * M, kernel_size=5, padding=2, stride=1)
+
+    def _entropy_parameters(self, t):
+        ep = self.entropy_parameters
+        return ep[4](ep[2](ep[0](t, act=ACT_LRELU), act=ACT_LRELU))
+
+    def forward(self, x):
+        x = self._prep(x)
+        y = self._analysis(x)
+        z = self._hyper_analysis(y)
+        z_hat, z_likelihoods = self.entropy_bottleneck(z)
+        params = self._hyper_synthesis(z_hat)
+        # quantize(y, "noise" if training else "dequantize"): no means here — the context model must see what a decoder can know
+        if self.training:
+            y_hat = y + torch.empty_like(y, memory_format=CL).uniform_(-0.5, 0.5)
+        else:
+            y_hat = torch.round(y.detach())
+        ctx_params = self.context_prediction(y_hat)
+        gaussian_params = self._entropy_parameters(torch.cat((params, ctx_params), 1))
+        scales_hat, means_hat = gaussian_params.chunk(2, 1)
+        _, y_likelihoods = self.gaussian_conditional(y, scales_hat, means=means_hat)
+        x_hat = self._synthesis(y_hat)
+        return {"x_hat": x_hat, "likelihoods": {"y": y_likelihoods, "z": z_likelihoods}}
+
+    # ---- the sequential coder ----
+    def _ar_filters(self):
+        """[(filter [N, K] row-major, bias)] of the four layers of the chain.  The context layer's is the masked parameter's 12 live taps,
+        [2M][12][M]: the first 12 of the 25 (kh, kw) positions of the channels-last parameter."""
+        M = self.M
+        cp, ep = self.context_prediction, self.entropy_parameters
+        wc = cp.weight.detach().permute(0, 2, 3, 1).reshape(2 * M, 25, M)[:, :12].reshape(2 * M, 12 * M).contiguous()
+        out = [(wc, cp.bias.detach().contiguous())]
+        for i in (0, 2, 4):
+            w = ep[i].weight.detach()
+            out.append((w.reshape(w.shape[0], w.shape[1]).contiguous(), ep[i].bias.detach().contiguous()))
+        return out
+
+    def _ar_workspace(self, rows, dev):
+        M = self.M
+        mk = lambda c: torch.empty((rows, c), device=dev, dtype=torch.float32)
+        return {"ctx": mk(2 * M), "h1": mk(M * 10 // 3), "h2": mk(M * 8 // 3), "gp": mk(2 * M)}
+
+    def _ar_chain(self, px, B, H, W, y_hat, params, ws, filt):
+        """(scales | means) of the listed pixels of every image -> ws["gp"]; four launches"""
+        ops.ar_linear([("taps", y_hat)], px, B, H, W, filt[0][0], filt[0][1], ws["ctx"])
+        ops.ar_linear([("pixel", params), ("dense", ws["ctx"])], px, B, H, W, filt[1][0], filt[1][1], ws["h1"], act=ACT_LRELU)
+        ops.ar_linear([("dense", ws["h1"])], px, B, H, W, filt[2][0], filt[2][1], ws["h2"], act=ACT_LRELU)
+        ops.ar_linear([("dense", ws["h2"])], px, B, H, W, filt[3][0], filt[3][1], ws["gp"])
+
+    @staticmethod
+    def _ar_pixels(steps, dev):
+        steps = [s for s in steps if s]
+        return steps, torch.tensor([p for s in steps for p in s], dtype=torch.int32).reshape(-1, 2).to(dev)
+
+    @torch.no_grad()
+    def _ar_encode(self, y, params, order="wavefront"):
+        """The autoregressive pass of compress -> (symbols int32 [B, H*W, M], indexes int32 [B, H*W, M], y_hat): all launches on the current
+        stream, no host sync.  The schedule decides the order of computation only; the buffers are in raster order either way."""
+        ops._require_gpu(y, "mbt2018 compress")
+        B, M, H, W = y.shape
+        y = y.contiguous(memory_format=CL)
+        params = params.contiguous(memory_format=CL)
+        steps, pix = self._ar_pixels(ar_schedule(H, W, order), y.device)
+        ws = self._ar_workspace(B * max(len(s) for s in steps), y.device)
+        filt = self._ar_filters()
+        table = self.gaussian_conditional.scale_table
+        y_hat = torch.zeros_like(y, memory_format=CL)
+        sym = torch.empty((B, H * W, M), device=y.device, dtype=torch.int32)
+        idx = torch.empty((B, H * W, M), device=y.device, dtype=torch.int32)
+        off = 0
+        for s in steps:
+            px = pix[off:off + len(s)]
+            self._ar_chain(px, B, H, W, y_hat, params, ws, filt)
+            ops.ar_finish_encode(ws["gp"], M, px, y, y_hat, table, sym, idx)
+            off += len(s)
+        return sym, idx, y_hat
+
+    @torch.no_grad()
+    def _code_inputs(self, x):
+        """(y, hyper parameters from the coded z, z streams, z's map size): what the autoregressive pass starts from"""
+        x = self._prep(x)
+        y = self._analysis(x)
+        z = self._hyper_analysis(y)
+        z_strings = self.entropy_bottleneck.compress(z)
+        z_hat = self.entropy_bottleneck.decompress(z_strings, z.size()[-2:])
+        return y, self._hyper_synthesis(z_hat), z_strings, z.size()[-2:]
+
+    @torch.no_grad()
+    def compress(self, x, order="wavefront"):
+        y, params, z_strings, z_size = self._code_inputs(x)
+        cdf, ln, off = self.gaussian_conditional.host_tables()
+        sym, idx, _ = self._ar_encode(y, params, order)
+        both = torch.stack((sym, idx)).cpu().numpy()   # the one device -> host copy: [2, B, H*W, M], raster pixels, channels inner
+        y_strings = [ans.encode(both[0, i].reshape(-1), both[1, i].reshape(-1), cdf, ln, off) for i in range(both.shape[1])]
+        from ..codec import kernel_config
+
+        return {"strings": [y_strings, z_strings], "shape": z_size, "kernel_config": kernel_config()}
+
+    @torch.no_grad()
+    def decompress(self, strings, shape):
+        assert isinstance(strings, (list, tuple)) and len(strings) == 2
+        z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
+        params = self._hyper_synthesis(z_hat).contiguous(memory_format=CL)
+        dev = params.device
+        B, M, (H, W) = params.shape[0], self.M, params.shape[2:]
+        if len(strings[0]) != B:
+            raise ValueError(f"decompress: {len(strings[0])} y streams for {B} z streams")
+        cdf, ln, off = self.gaussian_conditional.host_tables()
+        table = self.gaussian_conditional.scale_table
+        steps, pix = self._ar_pixels(ar_schedule(H, W, "raster"), dev)
+        ws = self._ar_workspace(B, dev)
+        filt = self._ar_filters()
+        y_hat = torch.zeros((B, M, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
+        decoders = []
+        for s in strings[0]:
+            d = ans.RansDecoder()
+            d.set_stream(s)
+            decoders.append(d)
+        idx_dev = torch.empty((B, M), device=dev, dtype=torch.int32)
+        sym_dev = torch.empty((B, M), device=dev, dtype=torch.int32)
+        idx_host = torch.empty((B, M), dtype=torch.int32).pin_memory()
+        sym_host = torch.empty((B, M), dtype=torch.int32).pin_memory()
+        idx_np, sym_np = idx_host.numpy(), sym_host.numpy()
+        stream = torch.cuda.current_stream(dev)
+        for i in range(len(steps)):
+            px = pix[i:i + 1]
+            self._ar_chain(px, B, H, W, y_hat, params, ws, filt)
+            ops.ar_finish_decode(ws["gp"], M, px, B, H, W, table, idx_dev)
+            idx_host.copy_(idx_dev, non_blocking=True)
+            stream.synchronize()   # (also: the previous pixel's symbol upload has left sym_host)
+            for b, d in enumerate(decoders):
+                sym_np[b] = d.decode_stream(idx_np[b], cdf, ln, off)
+            sym_dev.copy_(sym_host, non_blocking=True)
+            ops.ar_commit(sym_dev, ws["gp"], M, px, y_hat)
+        return {"x_hat": self._synthesis(y_hat).clamp_(0, 1)}

@@ -2555,3 +2555,107 @@ def fingerprint(tensors, n_partials: int = 256):
     out = torch.empty(1, dtype=torch.int64, device=dev)
     _lib.check(_L().clc_fingerprint(table.data_ptr(), len(ents), partials.data_ptr(), n_partials, out.data_ptr(), _stream()), "clc_fingerprint")
     return out
+
+
+# ------------------------------------------------------------------- autoregressive context model (csrc/ar_context.hip)
+# Rows of a call are r = b * P + p over a pixel list pix (int32 [P, 2] of (h, w) on the device, usually a slice of an uploaded schedule).
+
+
+def _ar_map(t, what):
+    """(ptr, B, H, W, C, ld) of a pixel-major [B, C, H, W] map; never copies (the kernels write / re-read these maps in place)."""
+    _require_gpu(t, what)
+    tt, p, B, H, W, Cc, ld = nhwc(t)
+    if tt is not t:
+        raise ValueError(f"{what}: the map must be a channels_last [B, C, H, W] tensor (or a channel slice of one)")
+    return p, B, H, W, Cc, ld
+
+
+def _ar_pix(pix):
+    if pix.dtype != torch.int32 or pix.dim() != 2 or pix.shape[1] != 2 or not pix.is_contiguous() or not pix.is_cuda or pix.shape[0] < 1:
+        raise ValueError("ar ops: the pixel list must be a contiguous int32 [P, 2] tensor of (h, w) pairs on the device, P >= 1")
+    return pix.data_ptr(), int(pix.shape[0])
+
+
+def _ar_dense(t, rows, what, dtype=torch.float32):
+    if t.dim() != 2 or t.dtype != dtype or not t.is_cuda or t.stride(1) != 1 or t.shape[0] < rows:
+        raise ValueError(f"{what}: needs a row-major {dtype} [>= {rows} rows, C] device buffer (got {tuple(t.shape)}, {t.dtype}, strides {t.stride()})")
+    return t.data_ptr(), int(t.stride(0))
+
+
+AR_KINDS = {"dense": _lib.AR_SRC_DENSE, "pixel": _lib.AR_SRC_PIXEL, "taps": _lib.AR_SRC_TAPS}
+
+
+def ar_linear(srcs, pix, B, H, W, w, bias, out, act=ACT_NONE):
+    """clc_ar_linear: out[r, :N] = act(bias + sum_k in(r, k) w[n, k]) for the rows r = b * P + p of the pixel list.  srcs: one or two
+    (kind, tensor) ranges of the K axis — ("dense", [rows, C] buffer), ("pixel", map) or ("taps", map: the 12 live taps of mask A,
+    K = 12 C).  w [N, K] row-major.  Every element's summation order depends on the K of each range alone (see ar_context.hip)."""
+    pp, P = _ar_pix(pix)
+    rows = B * P
+    if not 1 <= len(srcs) <= 2:
+        raise ValueError(f"ar_linear: one or two K ranges (got {len(srcs)})")
+    arr, K = (_lib.ArSrc * 2)(), 0
+    for i, (kind, t) in enumerate(srcs):
+        if kind not in AR_KINDS:
+            raise ValueError(f"ar_linear: unknown source kind {kind!r} (dense, pixel or taps)")
+        if kind == "dense":
+            _require_gpu(t, "ar_linear")
+            p, ld = _ar_dense(t, rows, "ar_linear dense range")
+            Cc = int(t.shape[1])
+        else:
+            p, Bm, Hm, Wm, Cc, ld = _ar_map(t, "ar_linear")
+            if (Bm, Hm, Wm) != (B, H, W):
+                raise ValueError(f"ar_linear: map {tuple(t.shape)} does not match B, H, W = {B}, {H}, {W}")
+        arr[i] = _lib.ArSrc(p, ld, Cc, AR_KINDS[kind])
+        K += 12 * Cc if kind == "taps" else Cc
+    _require_gpu(w, "ar_linear")
+    if w.dim() != 2 or not w.is_contiguous() or w.shape[1] != K:
+        raise ValueError(f"ar_linear: the filter must be a contiguous [N, K = {K}] matrix (got {tuple(w.shape)})")
+    N = int(w.shape[0])
+    if bias is not None and (bias.numel() != N or not bias.is_contiguous() or bias.dtype != torch.float32 or not bias.is_cuda):
+        raise ValueError("ar_linear: bias must be a contiguous float32 [N] device tensor")
+    op, ldo = _ar_dense(out, rows, "ar_linear out")
+    if out.shape[1] < N:
+        raise ValueError(f"ar_linear: out has {out.shape[1]} columns, N = {N}")
+    _lib.check(_L().clc_ar_linear(arr, len(srcs), pp, P, B, H, W, w.data_ptr(), bias.data_ptr() if bias is not None else None, N, act, op, ldo,
+                                  _stream()), "clc_ar_linear")
+    return out
+
+
+def ar_finish_encode(gp, M, pix, y, y_hat, scale_table, symbols, indexes):
+    """clc_ar_finish, encode mode: gp [rows, >= 2M] (scales | means) -> y_hat map in place, symbols / indexes int32 [B, H*W, M] at the
+    pixels' raster places.  The arithmetic of quantize_build_indexes, bit for bit."""
+    pp, P = _ar_pix(pix)
+    yp, B, H, W, Cy, ldy = _ar_map(y, "ar_finish")
+    hp, Bh, Hh, Wh, Ch, ldh = _ar_map(y_hat, "ar_finish")
+    if (Bh, Hh, Wh, Ch) != (B, H, W, Cy) or Cy != M:
+        raise ValueError(f"ar_finish: y {tuple(y.shape)} and y_hat {tuple(y_hat.shape)} must be [B, M = {M}, H, W] maps of one shape")
+    gpp, ldg = _ar_dense(gp, B * P, "ar_finish gp")
+    for t in (symbols, indexes):
+        if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (B, H * W, M):
+            raise ValueError(f"ar_finish: symbols / indexes must be contiguous int32 [B, H*W, M] = {(B, H * W, M)} device tensors")
+    if gp.shape[1] < 2 * M:
+        raise ValueError(f"ar_finish: gp has {gp.shape[1]} columns, needs 2 M = {2 * M}")
+    _lib.check(_L().clc_ar_finish(gpp, ldg, M, pp, P, B, H, W, scale_table.data_ptr(), scale_table.numel(), yp, ldy, hp, ldh, symbols.data_ptr(),
+                                  indexes.data_ptr(), _lib.AR_ENCODE, _stream()), "clc_ar_finish")
+
+
+def ar_finish_decode(gp, M, pix, B, H, W, scale_table, indexes):
+    """clc_ar_finish, decode mode: indexes int32 [rows, M] (dense) from the scales of gp; gp keeps the means for ar_commit."""
+    pp, P = _ar_pix(pix)
+    gpp, ldg = _ar_dense(gp, B * P, "ar_finish gp")
+    ip, ldi = _ar_dense(indexes, B * P, "ar_finish indexes", torch.int32)
+    if gp.shape[1] < 2 * M or ldi != M:
+        raise ValueError(f"ar_finish: gp needs 2 M = {2 * M} columns and indexes must be a dense [rows, M = {M}] buffer")
+    _lib.check(_L().clc_ar_finish(gpp, ldg, M, pp, P, B, H, W, scale_table.data_ptr(), scale_table.numel(), None, 0, None, 0, None, ip,
+                                  _lib.AR_DECODE, _stream()), "clc_ar_finish")
+
+
+def ar_commit(symbols, gp, M, pix, y_hat):
+    """clc_ar_commit: y_hat[pixel] = symbols[r] + mean(gp[r]) from decoded symbols (dense int32 [rows, M])."""
+    pp, P = _ar_pix(pix)
+    hp, B, H, W, Ch, ldh = _ar_map(y_hat, "ar_commit")
+    gpp, ldg = _ar_dense(gp, B * P, "ar_commit gp")
+    sp, lds = _ar_dense(symbols, B * P, "ar_commit symbols", torch.int32)
+    if gp.shape[1] < 2 * M or lds != M or Ch != M:
+        raise ValueError(f"ar_commit: gp needs 2 M = {2 * M} columns, symbols a dense [rows, M = {M}] buffer, y_hat M channels")
+    _lib.check(_L().clc_ar_commit(sp, gpp, ldg, M, pp, P, B, H, W, hp, ldh, _stream()), "clc_ar_commit")

@@ -30,6 +30,8 @@ def apply_weight_recipe(model: torch.nn.Module, seed: int = 0) -> None:
         t = sd[name]
         if name.endswith(_SKIP_SUFFIX) or not t.is_floating_point() or t.numel() == 0:
             continue
+        if name.rsplit(".", 1)[-1] == "mask":  # the fixed causal mask of a MaskedConv2d: a buffer, not a weight
+            continue
         g = _gen(name, seed)
         shape = tuple(t.shape)
         leaf = name.rsplit(".", 1)[-1]

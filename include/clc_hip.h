@@ -674,6 +674,42 @@ size_t clc_kmeans_representatives_workspace_bytes(int K);
 int clc_kmeans_representatives(const float* x, int ldx, int N, int D, const int32_t* label, const int32_t* order, const float* c, int ldc, int K,
                                int32_t* rep, void* ws, size_t ws_bytes, clc_stream_t stream);
 
+/* ---- the sequential part of the autoregressive context model (mbt2018, JointAutoregressiveHierarchicalPriors; ar_context.hip) ----
+ * What they replace: the per-pixel body of CompressAI's `_compress_ar` / `_decompress_ar` loops — F.conv2d of a 5x5 crop with the
+ * masked filter, the three 1x1 layers of `entropy_parameters` on cat((params pixel, context)), `build_indexes`, `quantize(.., "symbols",
+ * means)` and the write-back `y_hat[h, w] = symbols + means` — which the published coder runs on the CPU, one pixel at a time.
+ *
+ * Rows of a call are r = b * P + p for image b < B and entry p of a PIXEL LIST: P pairs (h, w) of int32 in device memory (a whole
+ * schedule is uploaded once, a step is an offset into it).  A pair outside the H x W map is neither read nor written.
+ *
+ * clc_ar_linear   out[r][n] = act(bias[n] + sum_k in(r, k) * w[n][k]), out a dense [rows][ldo] workspace, act CLC_ACT_NONE or
+ *                 CLC_ACT_LRELU, w [N][K] row-major, N arbitrary.  The K axis is one or two consecutive ranges (clc_ar_src):
+ *                   CLC_AR_SRC_DENSE  row r of a dense [rows][ld] buffer, K = C;
+ *                   CLC_AR_SRC_PIXEL  the C channels of the row's own pixel of an NHWC [B][H][W][ld] map, K = C;
+ *                   CLC_AR_SRC_TAPS   the 12 live taps of mask A of an NHWC map in (kh, kw) ascending order — (0,0..4), (1,0..4), (2,0),
+ *                                     (2,1) of the 5x5 window centred on the pixel — C channels each, K = 12 C; taps outside the map are zeros.
+ *                 ORDER RULE: every output element is summed in an order fixed by the K of each range alone (lane l of a wave takes the
+ *                 16-byte chunks l, l + 64, ... of each range in turn into one accumulator, then the 64 lanes are added by an xor
+ *                 butterfly): not by P, B, the row's place in the list, the pixel's place in the map or the grid.  An encoder step of many
+ *                 rows and a decoder step of one therefore give the same bits.  Any row count.  Requires C % 4 == 0, ld % 4 == 0,
+ *                 16-byte aligned bases.
+ * clc_ar_finish   gp is a dense [rows][ldg] buffer, scales in columns [0, M), means in [M, 2M) (chunk(2, 1)).
+ *                   CLC_AR_ENCODE  sym = round(y - mean), y_hat = sym + mean, idx = build_indexes(scale): the arithmetic of
+ *                                  clc_quantize_build_indexes, bit for bit.  y_hat goes into the NHWC map (which may be y itself),
+ *                                  sym and idx to int32 [B][H*W][M] at the pixel's raster place.
+ *                   CLC_AR_DECODE  idx to a dense [rows][M] int32 buffer; gp keeps the means for clc_ar_commit.
+ * clc_ar_commit   y_hat[pixel] = symbols[r] + mean from decoded symbols (dense [rows][M] int32): the expression of CLC_AR_ENCODE.
+ * All three: stream-ordered, graph-capturable, allocation- and sync-free, no workgroup waits on another. */
+enum { CLC_AR_SRC_DENSE = 0, CLC_AR_SRC_PIXEL = 1, CLC_AR_SRC_TAPS = 2 };
+enum { CLC_AR_ENCODE = 0, CLC_AR_DECODE = 1 };
+typedef struct { const float* p; int ld; int C; int kind; } clc_ar_src;
+int clc_ar_linear(const clc_ar_src* srcs /* HOST */, int nsrc, const int32_t* pix, int P, int B, int H, int W, const float* w, const float* bias,
+                  int N, int act, float* out, int ldo, clc_stream_t stream);
+int clc_ar_finish(const float* gp, int ldg, int M, const int32_t* pix, int P, int B, int H, int W, const float* scale_table, int n_scales,
+                  const float* y, int ldy, float* y_hat, int ldh, int32_t* symbols, int32_t* indexes, int mode, clc_stream_t stream);
+int clc_ar_commit(const int32_t* symbols, const float* gp, int ldg, int M, const int32_t* pix, int P, int B, int H, int W, float* y_hat,
+                  int ldh, clc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
