@@ -38,6 +38,7 @@ import weakref
 import torch
 
 from . import ops
+from .train import StepImages
 
 ENV = "CLC_GRAPH_TRAIN"
 _TRUE, _FALSE = ("1", "true", "on", "yes"), ("", "0", "false", "off", "no")
@@ -161,39 +162,7 @@ def _unflatten(ts):
     return out
 
 
-# ------------------------------------------------------------------------------------------------ filter images
-_IMAGE_ATTRS = ("_clc_wt", "_clc_hpk", "_clc_hpk_t", "_clc_wu", "_clc_wu_t", "_clc_gdn_eff")
-
-
-class _ImageScope:
-    """The batched packers of clc_amd.train publish their images as attributes of the Parameters, where the ops find them while
-    ops.WT_CACHE_VALID is set.  The plan captures on stand-in leaves (_StandIns), which start with copies of the parameters' attributes:
-    inside this scope the image attributes on them are the plan's own (none inherited from another engine), and on exit they are put
-    back as they were.  The model's own Parameters never carry this plan's images.  The captured graphs keep the addresses they were
-    captured with."""
-
-    def __init__(self, params):
-        self.params = params
-
-    def __enter__(self):
-        self.saved = []
-        for p in self.params:
-            d = {a: p.__dict__[a] for a in _IMAGE_ATTRS if a in p.__dict__}
-            for a in d:
-                delattr(p, a)
-            self.saved.append((p, d))
-        return self
-
-    def __exit__(self, *exc):
-        for p, d in self.saved:
-            for a in _IMAGE_ATTRS:
-                if a in p.__dict__:
-                    delattr(p, a)
-            for a, v in d.items():
-                setattr(p, a, v)
-        return False
-
-
+# ------------------------------------------------------------------------------------------------ stand-in leaves
 class _StandIns:
     """During warm-up and capture every parameter of the model is swapped for a fresh leaf on the SAME storage (same attributes), and the
     captured graphs differentiate with respect to those leaves.
@@ -230,29 +199,6 @@ class _StandIns:
         return False
 
 
-class _Images:
-    """The four batched refresh launches (clc_amd.train: transposed filters, halo packs, Winograd packs, GDN re-parametrisation)."""
-
-    def __init__(self, model, live):
-        from .train import FilterTransposer, GDNReparamCache, HaloPacker, WinoPacker
-
-        self.parts = [FilterTransposer(live)]   # (first: the halo / Winograd images of the data gradients read its output)
-        self.parts += [HaloPacker(live), WinoPacker(live), GDNReparamCache(model, live)]
-
-    def refresh(self):
-        for p in self.parts:
-            p.refresh()
-
-
-class _valid_images:
-    def __enter__(self):
-        ops.WT_CACHE_VALID = True
-
-    def __exit__(self, *exc):
-        ops.WT_CACHE_VALID = False
-        return False
-
-
 # ------------------------------------------------------------------------------------------------ one captured signature
 class _Plan:
     def __init__(self, state, sig):
@@ -267,23 +213,25 @@ class _Plan:
         self.sx = cl(x)
         self.srefs = [cl(r) for r in refs] if refs is not None else None
         inputs = [p for p in st.params if p.requires_grad]
-        with _StandIns(model) as si, _ImageScope(si.leaves):
+        with _StandIns(model) as si:
             params = [si.of(p) for p in inputs]
-            # warm-up on a side stream (allocator, lazy kernel attributes, the halo / Winograd use marks the packers select by).  Gradients
+            # warm-up on a side stream (allocator, lazy kernel attributes, which filters take the halo / Winograd kernels).  Gradients
             # come back from autograd.grad: the user's p.grad is never touched.
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
-                outs = _flatten(model._forward_eager(self.sx, self.srefs))
-                diff = [o for o in outs if o.requires_grad]
-                grads = torch.autograd.grad(diff, params, grad_outputs=[torch.ones_like(o) for o in diff], allow_unused=True)
-                ops.join_side_streams()
+                with ops.collecting_uses() as uses:
+                    outs = _flatten(model._forward_eager(self.sx, self.srefs))
+                    diff = [o for o in outs if o.requires_grad]
+                    grads = torch.autograd.grad(diff, params, grad_outputs=[torch.ones_like(o) for o in diff], allow_unused=True)
+                    ops.join_side_streams()
                 live_idx = [i for i, g in enumerate(grads) if g is not None]
                 del outs, diff, grads
                 self.live = [params[i] for i in live_idx]
-                self.images = _Images(model, self.live)
+                # (the plan's own images, of its stand-in leaves: the model's Parameters and any other owner's images are not involved)
+                self.images = StepImages(model, self.live, uses)
                 self.images.refresh()
-                with _valid_images():
+                with self.images.valid():
                     outs = _flatten(model._forward_eager(self.sx, self.srefs))
                     diff = [o for o in outs if o.requires_grad]
                     torch.autograd.grad(diff, self.live, grad_outputs=[torch.ones_like(o) for o in diff], allow_unused=True)
@@ -299,13 +247,13 @@ class _Plan:
             # (the default CUDA generator is registered with the capture: each replay draws fresh noise for the training-mode proxy)
             with ops.capture_guard(), torch.cuda.graph(self.fwd, pool=st.pool, capture_error_mode=ops.graph_capture_mode()):
                 self.images.refresh()
-                with _valid_images():
+                with self.images.valid():
                     self.souts = _flatten(model._forward_eager(self.sx, self.srefs))
             self.diff_idx = [i for i, o in enumerate(self.souts) if o.requires_grad]
             self.sgos = [torch.zeros_like(self.souts[i]) for i in self.diff_idx]
             self.go_dirty = [False] * len(self.sgos)
             with ops.capture_guard(), torch.cuda.graph(self.bwd, pool=st.pool, capture_error_mode=ops.graph_capture_mode()):
-                with _valid_images():
+                with self.images.valid():
                     g = torch.autograd.grad([self.souts[i] for i in self.diff_idx], self.live, grad_outputs=self.sgos, allow_unused=True)
                     ops.join_side_streams()
             self.souts = [o.detach() for o in self.souts]   # (the autograd graph of the capture is not needed past this point)

@@ -11,6 +11,7 @@ There is no CPU path: a CPU tensor raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import functools
 import math
@@ -487,13 +488,31 @@ def to_kernel_weight(w: torch.Tensor) -> torch.Tensor:
 
 
 # ---- halo-resident 3x3 kernel (csrc/conv_halo.hip): the filter is ALSO needed in fragment order.  Where the packed image comes from:
-#   * inside a TrainEngine step (WT_CACHE_VALID): one batched launch per step packs every eligible filter and transposed filter
-#     (clc_amd.train.HaloPacker -> w._clc_hpk / w._clc_hpk_t), like the transposed images themselves;
+#   * while an owner's per-step images are valid (WT_CACHE_VALID, _image): one batched launch per step packs every filter and transposed
+#     filter that took this kernel in the owner's discovery pass (note_use -> clc_amd.train.StepImages), like the transposed images themselves;
 #   * anywhere else: packed PER USE (one 5-us launch in front of a >= 75-us convolution).  No cache across calls: nothing tells this module
 #     that `w.data.copy_(...)` or a kernel writing through a raw pointer changed the weights (neither moves a version counter), and a stale
 #     image would be silently wrong results.  Inside a captured graph (CodecEngine) the pack launch is part of the graph, so a replay
 #     always packs the weights of the moment.
-WEIGHTS_EPOCH = 0   # bumped by TrainEngine per step (its kernels update the arena through raw pointers); informational
+USES = None   # the set an owner's discovery pass collects (parameter identity, image kind) into, else None: nothing is recorded
+
+
+@contextlib.contextmanager
+def collecting_uses():
+    """Install a fresh collector for the enclosed forward / backward: which parameters' filters took the halo / Winograd kernels, forward
+    ("halo", "wino") or as data gradient ("halo_t", "wino_t").  The owner packs exactly those per step from then on; a use it did not see
+    (a later shape change) packs per use."""
+    global USES
+    prev, USES = USES, set()
+    try:
+        yield USES
+    finally:
+        USES = prev
+
+
+def note_use(w, kind):
+    if USES is not None:
+        USES.add((id(w), kind))
 
 
 def halo_ok(N, H, W, Cin, rows, ks, stride):
@@ -514,21 +533,20 @@ def halo_pack(wk, rows, K=128):
 
 
 def halo_packed(w, transposed_image=None):
-    """packed image of parameter `w`'s forward filter, or (transposed_image given: the [Cin][9][Cout] image of this step) of its transposed one.
-    The parameter is marked as a user (`_clc_halo_use` / `_clc_halo_use_t`): clc_amd.train.HaloPacker packs exactly the marked ones."""
+    """packed image of parameter `w`'s forward filter, or (transposed_image given: the [Cin][9][Cout] image of this step) of its transposed one"""
     tr = transposed_image is not None
-    setattr(w, "_clc_halo_use_t" if tr else "_clc_halo_use", True)
-    if WT_CACHE_VALID:
-        pk = getattr(w, "_clc_hpk_t" if tr else "_clc_hpk", None)
-        if pk is not None:
-            return pk
+    kind = "halo_t" if tr else "halo"
+    note_use(w, kind)
+    pk = _image(w, kind)
+    if pk is not None:
+        return pk
     if tr:
         return halo_pack(transposed_image, transposed_image.shape[0], w.shape[0])
     return halo_pack(to_kernel_weight(w), w.shape[0], w.shape[1])
 
 
 # ---- Winograd F(2x2, 3x3) kernel (csrc/conv_wino.hip): needs the TRANSFORMED filter U = G g G^T in fragment order.  Same provenance rules as the
-# halo kernel's image: per-step batched launch inside a TrainEngine step (clc_amd.train.WinoPacker -> w._clc_wu / w._clc_wu_t), per use elsewhere.
+# halo kernel's image: from the owner's per-step batched launch while its images are valid, per use elsewhere.
 # (switched by tuning key 23, e.g. through CLC_TUNING: bit 0 = forward launches of a recorded (training) pass, bit 1 = data gradients.
 #  Never taken without autograd recording: eval forwards, the parity measurement and the codec keep the direct kernels and their bits.)
 
@@ -555,11 +573,11 @@ def wino_pack(wk, rows, K, flip=False):
 
 def wino_packed(w, transposed_image=None):
     tr = transposed_image is not None
-    setattr(w, "_clc_wino_use_t" if tr else "_clc_wino_use", True)
-    if WT_CACHE_VALID:
-        u = getattr(w, "_clc_wu_t" if tr else "_clc_wu", None)
-        if u is not None:
-            return u
+    kind = "wino_t" if tr else "wino"
+    note_use(w, kind)
+    u = _image(w, kind)
+    if u is not None:
+        return u
     if tr:
         return wino_pack(transposed_image, transposed_image.shape[0], w.shape[0], flip=True)
     return wino_pack(to_kernel_weight(w), w.shape[0], w.shape[1])
@@ -951,11 +969,6 @@ class _ConvFn(Function):
                 dw, db = _ConvFn._wgrad(x[:h], dz[:h], w, ctx.bias_ref, has_b, need_w, need_b, ks, stride, pad, fw1)
                 dw2, db2 = _ConvFn._wgrad(x[h:], dz[h:], w2, b2, has_b, need_w, need_b, ks, stride, pad, fw2)
         if need_x:
-            def wt_of(wp):
-                wt = getattr(wp, "_clc_wt", None) if WT_CACHE_VALID else None   # refreshed once per step by the batched transpose (clc_amd.train)
-                if wt is None:
-                    wt = filter_transpose(to_kernel_weight(wp), Cout, ks * ks, Cin)
-                return wt.view(Cin, -1)
             extra, extra_scale, gate = fold_in.take() if fold_in is not None else (None, 1.0, None)
             gs = ctx.grad_slot
             dx_out = gs[0].view(x, gs[1], gs[2], x.shape[1]) if gs is not None else None
@@ -964,12 +977,12 @@ class _ConvFn(Function):
                 # this layer is the only consumer of the producer's activated output: hand it d(pre-activation)
                 og = (gate_in.saved, gate_in.act, gate_in.pre)
                 gate_in.done = True
-            wt1 = wt_of(w)
+            wt1 = _wt_of(w)
             # (data gradient of a 128 -> 128 layer: rows = Cin, K = 9 x Cout = 9 x 128)
             wwino = (wino_packed(w, wt1) if (w2 is None and not fa and wino_ok(dz.shape[0], dz.shape[2], dz.shape[3], Cout, Cin, ks, stride, transposed=True)) else None)
             wpk = (halo_packed(w, wt1) if (wwino is None and w2 is None and not fa and halo_ok(dz.shape[0], dz.shape[2], dz.shape[3], Cout, Cin, ks, stride)) else None)
             dx = conv_raw(dz, wt1, None, ks=ks, stride=stride, pad=pad, transposed=True, out_hw=(x.shape[2], x.shape[3]),
-                          w2=(wt_of(w2) if w2 is not None else None), wx=(((wt_of(w3), None), (wt_of(w4), None)) if w3 is not None else None),
+                          w2=(_wt_of(w2) if w2 is not None else None), wx=(((_wt_of(w3), None), (_wt_of(w4), None)) if w3 is not None else None),
                           res=extra, res_scale=extra_scale, res_gate=gate, out=dx_out, out_gate=og, wpk=wpk, wwino=wwino, **fa)
         elif fold_in is not None:
             fold_in.consumed = True
@@ -1079,10 +1092,25 @@ def _recording(ctx) -> bool:
     return bool(getattr(_GRAD_MODE, "on", True)) and any(ctx.needs_input_grad)
 
 
-# The [Cin][T][Cout] filter images clc_amd.train.FilterTransposer attaches to the parameters (`_clc_wt`) are refreshed at the START of an
-# engine step; after that step's optimizer update they are one update behind.  They are therefore trusted only while the engine is
-# running (or capturing) the forward/backward of a step — a plain autograd backward on the same model afterwards transposes on the fly.
+# The per-step images of the weights (clc_amd.train.StepImages: transposed filters, halo / Winograd packs, re-parametrised GDN gamma / beta)
+# are refreshed at the START of an owner's step; after that step's optimizer update they are one update behind.  They are therefore trusted
+# only while the owner is running (or capturing) the forward / backward of a step — a plain autograd backward on the same model afterwards
+# derives them on the fly.  The images belong to their owner, not to the parameters: the one set that is current (its refresh, or its
+# `valid()` block, made it so) answers _image() while the flag is set, so an owner is only ever handed the images it refreshed itself.
 WT_CACHE_VALID = False
+_IMAGES = None   # weakref.ref to the current image set (a module global must not keep a released model's parameters and images alive)
+
+
+def set_current_images(ref):
+    """ref: a weakref.ref to an image set (StepImages.make_current), or None"""
+    global _IMAGES
+    _IMAGES = ref
+
+
+def _image(p, kind):
+    """the current owner's image `kind` of parameter `p` while its images are valid, else None: the caller derives it from the weights"""
+    images = _IMAGES() if (WT_CACHE_VALID and _IMAGES is not None) else None
+    return images.map.get((id(p), kind)) if images is not None else None
 
 FUSED_RU = 1   # ResidualUnits on 16x16 maps with 128 channels: one launch forward, one for the data gradient
 
@@ -1118,7 +1146,7 @@ def residual_unit_fwd_raw(x, sets):
 
 def _wt_of(wp):
     """[Cin][taps][Cout] image of a filter parameter: refreshed once per step by the batched transpose (clc_amd.train), else made here."""
-    wt = getattr(wp, "_clc_wt", None) if WT_CACHE_VALID else None
+    wt = _image(wp, "wt")
     if wt is None:
         ks = wp.shape[2] if wp.dim() == 4 else 1
         wt = filter_transpose(to_kernel_weight(wp), wp.shape[0], ks * ks, wp.shape[1])
@@ -1805,7 +1833,7 @@ class _GDNParamFn(Function):
         sets = [(gamma, beta)] + ([(gamma2, beta2)] if gamma2 is not None else [])
         eff = []
         for g, b in sets:
-            cached = getattr(g, "_clc_gdn_eff", None) if WT_CACHE_VALID else None   # (clc_amd.train.GDNReparamCache: all modules in one launch per step)
+            cached = _image(g, "gdn")   # (all modules in one launch per step)
             if cached is not None and g.is_contiguous():
                 eff.append((g,) + tuple(cached))
                 continue

@@ -18,8 +18,10 @@ MI355X-first design of the step (not nn.DataParallel, not stock DDP):
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
+import weakref
 from typing import Dict, List, Optional
 
 import torch
@@ -242,147 +244,132 @@ class FusedAdamW:
                                     float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.wd), self.step_dev.data_ptr(), float(self.grad_scale), st), "clc_adamw_step")
 
 
-# ------------------------------------------------------------------------------------ the engine
+# ------------------------------------------------------------------------------------ per-step images of the weights
 
 
-class FilterTransposer:
-    """Keeps [Cin][T][Cout] copies of every conv / linear filter for the data-gradient kernels, refreshed by ONE launch
-    per step (clc_filter_transpose_batched) instead of one small launch per layer inside backward."""
+# The tensors a step derives from the weights once and that go stale at the optimizer update ("images"): transposed filters, halo / Winograd
+# packs of the filters and of their transposed images, and the re-parametrised GDN gamma / beta.  Each kind is one batched launch per step
+# over a table of entries.  An owner (a TrainEngine, one graphed plan) holds ONE StepImages: the images live in its map and nowhere else,
+# so two owners on the same parameters cannot hand each other stale ones.
 
-    def __init__(self, params: List[nn.Parameter]):
-        ws = [p for p in params if p.dim() in (2, 4) and getattr(p, "_clc_is_filter", False)]
-        self.n = len(ws)
-        if not ws:
-            return
-        dev = ws[0].device
-        total = sum(p.numel() for p in ws)
-        self.buf = torch.empty(total, dtype=torch.float32, device=dev)
-        entries, off, tiles = [], 0, 0
-        for p in ws:
+
+def _transpose_jobs(live):
+    """[Cin][T][Cout] copies of every conv / linear filter for the data-gradient kernels (clc_filter_transpose_batched)."""
+    jobs = []   # (key, piece shapes, work units, entry(output pointers, first work unit))
+    for p in live:
+        if p.dim() in (2, 4) and getattr(p, "_clc_is_filter", False):
             Cout, Cin = p.shape[0], p.shape[1]
             T = p.shape[2] * p.shape[3] if p.dim() == 4 else 1
-            wt = self.buf[off: off + p.numel()].view(Cin, T * Cout)
-            off += p.numel()
-            p._clc_wt = wt
-            entries.append(_lib.TransposeEntry(p.data_ptr(), wt.data_ptr(), Cout, T, Cin, tiles))
-            tiles += T * ((Cout + 31) // 32) * ((Cin + 31) // 32)
-        self.total_tiles = tiles
-        raw = b"".join(bytes(e) for e in entries)
-        self.table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
-
-    def refresh(self):
-        if self.n:
-            _lib.check(ops._L().clc_filter_transpose_batched(self.table.data_ptr(), self.n, self.total_tiles, ops._stream()), "clc_filter_transpose_batched")
+            jobs.append(((id(p), "wt"), [(Cin, T * Cout)], T * ((Cout + 31) // 32) * ((Cin + 31) // 32),
+                         lambda out, begin, p=p, d=(Cout, T, Cin): _lib.TransposeEntry(p.data_ptr(), out[0], *d, begin)))
+    return jobs
 
 
-class HaloPacker:
-    """Fragment-order images of the filters the halo-resident 3x3 kernel takes (csrc/conv_halo.hip: [k * C, C, 3, 3], C = 128 or 64, forward;
-    the transposed image of the [C, C, 3, 3] ones for their data gradients), refreshed by ONE launch per step (clc_filter_pack_halo_batched)
-    right behind the batched transpose, whose output it reads.  Which filters: the ones the discovery pass marked (ops.halo_packed sets
-    `_clc_halo_use` on a forward use, `_clc_halo_use_t` on a data-gradient use).  ops.halo_packed() hands the images out while
-    ops.WT_CACHE_VALID is set."""
-
-    def __init__(self, params: List[nn.Parameter]):
-        jobs = []   # (parameter, source tensor, rows, K, attribute)
-        for p in params:
-            if p.dim() != 4 or not getattr(p, "_clc_is_filter", False) or ops.to_kernel_weight(p) is not p:
-                continue
-            if getattr(p, "_clc_halo_use", False):
-                jobs.append((p, p, p.shape[0], p.shape[1], "_clc_hpk"))
-            wt = getattr(p, "_clc_wt", None)
-            if getattr(p, "_clc_halo_use_t", False) and wt is not None:    # [Cin][9][Cout]: rows = Cin, K = Cout
-                jobs.append((p, wt, p.shape[1], p.shape[0], "_clc_hpk_t"))
-        self.n = len(jobs)
-        if not jobs:
-            return
-        dev = jobs[0][0].device
-        total = sum(rows * 9 * K for _, _, rows, K, _ in jobs)
-        self.buf = torch.empty(total, dtype=torch.float32, device=dev)
-        entries, off, blocks = [], 0, 0
-        for p, src, rows, K, attr in jobs:
-            n = rows * 9 * K
-            out = self.buf[off: off + n]
-            off += n
-            setattr(p, attr, out)
-            entries.append(_lib.HaloPackEntry(src.data_ptr(), out.data_ptr(), int(rows), int(K), blocks))
-            blocks += (n // 4 + 255) // 256
-        self.total_blocks = blocks
-        self.table = torch.frombuffer(bytearray(b"".join(bytes(e) for e in entries)), dtype=torch.uint8).to(dev)
-
-    def refresh(self):
-        if self.n:
-            _lib.check(ops._L().clc_filter_pack_halo_batched(self.table.data_ptr(), self.n, self.total_blocks, ops._stream()), "clc_filter_pack_halo_batched")
+def _packable(live, uses, images, kind):
+    """(parameter, source, rows, K, image kind, transposed?) of the 3x3 filters the discovery pass saw take the halo / Winograd kernel
+    (ops.note_use): the filter itself on a forward use, its transposed image ([Cin][9][Cout]: rows = Cin, K = Cout) on a data-gradient use."""
+    for p in live:
+        if p.dim() != 4 or not getattr(p, "_clc_is_filter", False) or ops.to_kernel_weight(p) is not p:
+            continue
+        if (id(p), kind) in uses:
+            yield p, p, p.shape[0], p.shape[1], kind, 0
+        wt = images.get((id(p), "wt"))
+        if (id(p), kind + "_t") in uses and wt is not None:
+            yield p, wt, p.shape[1], p.shape[0], kind + "_t", 1
 
 
-class WinoPacker:
-    """Winograd-transformed images U = G g G^T of the filters conv_wino_kernel takes (csrc/conv_wino.hip), refreshed by ONE launch per step
-    (clc_filter_wino_batched) behind the batched transpose.  Which filters: the ones the discovery pass marked (ops.wino_packed:
-    `_clc_wino_use` forward, `_clc_wino_use_t` data gradient).  ops.wino_packed() hands the images out while ops.WT_CACHE_VALID is set."""
-
-    def __init__(self, params: List[nn.Parameter]):
-        jobs = []   # (parameter, source, rows, K, flip, attribute)
-        for p in params:
-            if p.dim() != 4 or not getattr(p, "_clc_is_filter", False) or ops.to_kernel_weight(p) is not p:
-                continue
-            if getattr(p, "_clc_wino_use", False):
-                jobs.append((p, p, p.shape[0], p.shape[1], 0, "_clc_wu"))
-            wt = getattr(p, "_clc_wt", None)
-            if getattr(p, "_clc_wino_use_t", False) and wt is not None:    # [Cin][9][Cout]: rows = Cin, K = Cout, taps flipped
-                jobs.append((p, wt, p.shape[1], p.shape[0], 1, "_clc_wu_t"))
-        self.n = len(jobs)
-        if not jobs:
-            return
-        dev = jobs[0][0].device
-        total = sum(-(-rows // 128) * 128 * 16 * K for _, _, rows, K, _, _ in jobs)   # (rows padded to the kernels' 128-row filter tiles)
-        self.buf = torch.empty(total, dtype=torch.float32, device=dev)
-        entries, off, blocks = [], 0, 0
-        for p, src, rows, K, flip, attr in jobs:
-            n = -(-rows // 128) * 128 * 16 * K
-            out = self.buf[off: off + n]
-            off += n
-            setattr(p, attr, out)
-            entries.append(_lib.WinoEntry(src.data_ptr(), out.data_ptr(), int(rows), int(K), int(flip), blocks))
-            blocks += (rows * K // 4 + 255) // 256
-        self.total_blocks = blocks
-        self.table = torch.frombuffer(bytearray(b"".join(bytes(e) for e in entries)), dtype=torch.uint8).to(dev)
-
-    def refresh(self):
-        if self.n:
-            _lib.check(ops._L().clc_filter_wino_batched(self.table.data_ptr(), self.n, self.total_blocks, ops._stream()), "clc_filter_wino_batched")
+def _halo_jobs(live, uses, images):
+    """fragment-order images for the halo-resident 3x3 kernel (csrc/conv_halo.hip; clc_filter_pack_halo_batched)"""
+    return [((id(p), kind), [(rows * 9 * K,)], (rows * 9 * K // 4 + 255) // 256,
+             lambda out, begin, s=src, d=(int(rows), int(K)): _lib.HaloPackEntry(s.data_ptr(), out[0], *d, begin))
+            for p, src, rows, K, kind, _ in _packable(live, uses, images, "halo")]
 
 
-class GDNReparamCache:
-    """The effective (re-parametrised) gamma / beta of every GDN module — and gamma transposed for the data-gradient conv — refreshed by ONE
-    launch per step (clc_gdn_reparam_fwd_batched) instead of one launch per module inside the forward pass.  Like the transposed filter
-    images, the cached tensors are this step's only between refresh() and the optimizer update (ops.WT_CACHE_VALID)."""
+def _wino_jobs(live, uses, images):
+    """Winograd-transformed images U = G g G^T for conv_wino_kernel (csrc/conv_wino.hip; clc_filter_wino_batched): rows padded to the
+    kernels' 128-row filter tiles, taps flipped for the data gradients"""
+    return [((id(p), kind), [(-(-rows // 128) * 128 * 16 * K,)], (rows * K // 4 + 255) // 256,
+             lambda out, begin, s=src, d=(int(rows), int(K), flip): _lib.WinoEntry(s.data_ptr(), out[0], *d, begin))
+            for p, src, rows, K, kind, flip in _packable(live, uses, images, "wino")]
 
-    def __init__(self, model: nn.Module, live: List[nn.Parameter]):
-        from .layers import GDN
 
-        ids = {id(p) for p in live}
-        mods = [m for m in model.modules() if isinstance(m, GDN) and id(m.gamma) in ids and id(m.beta) in ids and m.gamma.is_contiguous()]
-        self.n = len(mods)
-        if not mods:
-            return
-        dev = mods[0].gamma.device
-        entries, blocks, self.keep = [], 0, []
-        for m in mods:
+def _gdn_jobs(model, live):
+    """(gamma_eff, gamma_eff transposed for the data-gradient conv, beta_eff) of every GDN module (clc_gdn_reparam_fwd_batched)"""
+    from .layers import GDN
+
+    ids = {id(p) for p in live}
+    jobs = []
+    for m in model.modules():
+        if isinstance(m, GDN) and id(m.gamma) in ids and id(m.beta) in ids and m.gamma.is_contiguous():
             Cc = m.gamma.shape[0]
-            gb, bb, ped = m._consts()
-            g_eff = torch.empty((Cc, Cc), device=dev, dtype=torch.float32)
-            g_eff_t = torch.empty((Cc, Cc), device=dev, dtype=torch.float32)
-            b_eff = torch.empty((Cc,), device=dev, dtype=torch.float32)
-            m.gamma._clc_gdn_eff = (g_eff, g_eff_t, b_eff)
-            self.keep.append((g_eff, g_eff_t, b_eff))
-            entries.append(_lib.GDNEntry(m.gamma.data_ptr(), m.beta.data_ptr(), g_eff.data_ptr(), g_eff_t.data_ptr(), b_eff.data_ptr(), Cc, blocks, gb, bb, ped))
-            blocks += (Cc * Cc + Cc + 255) // 256
-        self.total_blocks = blocks
-        raw = b"".join(bytes(e) for e in entries)
-        self.table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
+            jobs.append(((id(m.gamma), "gdn"), [(Cc, Cc), (Cc, Cc), (Cc,)], (Cc * Cc + Cc + 255) // 256,
+                         lambda out, begin, m=m, Cc=Cc: _lib.GDNEntry(m.gamma.data_ptr(), m.beta.data_ptr(), *out, Cc, begin, *m._consts())))
+    return jobs
+
+
+class _Part:
+    """One kind of image: its jobs' outputs carved from one buffer, the table of entries, and refresh() = ONE launch over all of them."""
+
+    def __init__(self, owner, launch: str, jobs, dev):
+        self.owner, self.launch, self.n = owner.ref, launch, len(jobs)   # (a weak reference: the set owns its parts, not the reverse)
+        if not jobs:
+            return
+        self.buf = torch.empty(sum(math.prod(s) for _, shapes, _, _ in jobs for s in shapes), dtype=torch.float32, device=dev)
+        entries, off, self.total = [], 0, 0
+        for key, shapes, work, entry in jobs:
+            outs = []
+            for s in shapes:
+                outs.append(self.buf[off: off + math.prod(s)].view(s))
+                off += math.prod(s)
+            owner.map[key] = outs[0] if len(outs) == 1 else tuple(outs)
+            entries.append(entry([o.data_ptr() for o in outs], self.total))
+            self.total += work
+        self.table = torch.frombuffer(bytearray(b"".join(bytes(e) for e in entries)), dtype=torch.uint8).to(dev)
 
     def refresh(self):
+        ops.set_current_images(self.owner)   # (whoever sets ops.WT_CACHE_VALID after a refresh is handed the images just refreshed)
         if self.n:
-            _lib.check(ops._L().clc_gdn_reparam_fwd_batched(self.table.data_ptr(), self.n, self.total_blocks, ops._stream()), "clc_gdn_reparam_fwd_batched")
+            _lib.check(getattr(ops._L(), self.launch)(self.table.data_ptr(), self.n, self.total, ops._stream()), self.launch)
+
+
+class StepImages:
+    """One owner's images of the parameters `live`: map[(id(parameter), kind)] -> tensor (kind "gdn": the (g_eff, g_eff_t, b_eff) triple,
+    keyed by gamma) and the four batched refreshes.  `uses`: what ops.collecting_uses() gathered in the owner's discovery pass.
+    ops hands the images out inside `with images.valid():` only — between a refresh and the optimizer update that outdates them."""
+
+    def __init__(self, model: nn.Module, live: List[nn.Parameter], uses=frozenset()):
+        self.params = list(live)   # (kept alive: the map is keyed by their identities)
+        self.map = {}
+        self.ref = weakref.ref(self)
+        dev = live[0].device if live else None
+        self.transposer = _Part(self, "clc_filter_transpose_batched", _transpose_jobs(live), dev)
+        # (behind the transpose: the packs of the data gradients read its output)
+        self.halo_packer = _Part(self, "clc_filter_pack_halo_batched", _halo_jobs(live, uses, self.map), dev)
+        self.wino_packer = _Part(self, "clc_filter_wino_batched", _wino_jobs(live, uses, self.map), dev)
+        self.gdn_cache = _Part(self, "clc_gdn_reparam_fwd_batched", _gdn_jobs(model, live), dev)
+        self.parts = (self.transposer, self.halo_packer, self.wino_packer, self.gdn_cache)
+
+    def count(self, kind: str) -> int:
+        return sum(k == kind for _, k in self.map)
+
+    def make_current(self):
+        ops.set_current_images(self.ref)
+
+    def refresh(self):
+        for part in self.parts:
+            part.refresh()
+
+    @contextlib.contextmanager
+    def valid(self):
+        self.make_current()
+        ops.WT_CACHE_VALID = True
+        try:
+            yield self
+        finally:
+            ops.WT_CACHE_VALID = False
+
+
+# ------------------------------------------------------------------------------------ the engine
 
 
 class TrainEngine:
@@ -430,8 +417,9 @@ class TrainEngine:
         self.model.train(self.train_mode)
         for p in self.model.parameters():
             p.grad = None
-        out = self.criterion(self.model(x, refs), x)
-        out["loss"].backward()
+        with ops.collecting_uses() as uses:   # (which filters take the halo / Winograd kernels at the shape this engine steps)
+            out = self.criterion(self.model(x, refs), x)
+            out["loss"].backward()
         named = [(n, p) for n, p in self.model.named_parameters() if p.grad is not None and not n.endswith(".quantiles")]
         # arena order = [encoders | everything downstream]: the backward pass reaches the analysis transform and the reference
         # branch LAST, so their gradients are the second (small) exchange phase and everything else can go on the wire while
@@ -445,10 +433,8 @@ class TrainEngine:
         ops.enable_deferred_reductions(True)
         self.opt = self._make_opt(live, self.lr, self.clip)
         self.aux_opt = self._make_opt(aux, self.aux_lr, 0.0)
-        self.transposer = FilterTransposer(live)
-        self.halo_packer = HaloPacker(live)
-        self.wino_packer = WinoPacker(live)
-        self.gdn_cache = GDNReparamCache(self.model, live)
+        self.images = StepImages(self.model, live, uses)
+        self.transposer, self.halo_packer, self.wino_packer, self.gdn_cache = self.images.parts
         cut = self.opt.p_arena.offsets[len(late)] if (late and early) else 0
         n_el = self.opt.grad_flat.numel()
         self.early_params = early
@@ -479,16 +465,10 @@ class TrainEngine:
     def _fwd_bwd(self, x, refs):
         self.opt.zero_grad()
         self.aux_opt.zero_grad()
-        self.transposer.refresh()
-        self.halo_packer.refresh()
-        self.wino_packer.refresh()
-        self.gdn_cache.refresh()
-        ops.WT_CACHE_VALID = True      # (the transposed filter images are this step's: see ops.WT_CACHE_VALID)
-        try:
+        self.images.refresh()
+        with self.images.valid():      # (the images are this step's: see ops.WT_CACHE_VALID)
             out = self.criterion(self._model_out(x, refs), x)
             out["loss"].backward(self._one_like(out["loss"]))   # (a cached 1: no ones_like fill launch per step)
-        finally:
-            ops.WT_CACHE_VALID = False
         ops.join_side_streams()   # the deferred filter gradients and reductions are launched from here on
         return out
 
@@ -497,37 +477,27 @@ class TrainEngine:
         """forward + loss + backward of everything DOWNSTREAM of (y, ref_features); their gradients are parked on the boundary."""
         self.opt.zero_grad()
         self.aux_opt.zero_grad()
-        self.transposer.refresh()
-        self.halo_packer.refresh()
-        self.wino_packer.refresh()
-        self.gdn_cache.refresh()
+        self.images.refresh()
         self.model._keep_boundary = True
-        ops.WT_CACHE_VALID = True
         try:
-            out = self.criterion(self._model_out(x, refs), x)
+            with self.images.valid():
+                out = self.criterion(self._model_out(x, refs), x)
         finally:
             self.model._keep_boundary = False
-            ops.WT_CACHE_VALID = False
         self._bt = [t for t in self.model._boundary if t is not None and t.requires_grad]
         self.model._boundary = None
         for t in self._bt:
             t.grad = None
         # (retain_graph: the engine would otherwise also release the saved tensors of the boundary's producers, which stage 2 needs)
-        ops.WT_CACHE_VALID = True
-        try:
+        with self.images.valid():
             torch.autograd.backward([out["loss"]], [self._one_like(out["loss"])], inputs=list(self.early_params) + self._bt, retain_graph=True)
-        finally:
-            ops.WT_CACHE_VALID = False
         ops.join_side_streams()
         return out
 
     def _bwd_late(self):
         """backward of the analysis transform and the reference branch from the parked boundary gradients."""
-        ops.WT_CACHE_VALID = True
-        try:
+        with self.images.valid():
             torch.autograd.backward(self._bt, [t.grad for t in self._bt])
-        finally:
-            ops.WT_CACHE_VALID = False
         ops.join_side_streams()
         self._bt = None
 
@@ -602,7 +572,6 @@ class TrainEngine:
             set_precision(old)
 
     def _step(self, x, refs=None):
-        ops.WEIGHTS_EPOCH += 1   # this engine's kernels update the parameters through raw pointers (no version-counter bump): cached images keyed on it go stale
         refs = list(refs) if refs is not None else None
         if self.opt is None:
             self._discover(x, refs)

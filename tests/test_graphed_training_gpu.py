@@ -240,6 +240,13 @@ def test_second_plan_and_plan_limit(dev):
             if p.grad is not None:
                 assert torch.equal(p.grad, pe[n].grad), (b, n)
     assert len(m._clc_graphed.plans) == 2
+    # each plan owns its image set: distinct sets, disjoint buffers, and nothing of either on the model's Parameters
+    a, b = (pl.images for pl in m._clc_graphed.plans.values())
+    assert a is not b and a.map is not b.map and a.count("wt") > 0 and b.count("wt") > 0
+    spans = sorted((part.buf.data_ptr(), part.buf.data_ptr() + 4 * part.buf.numel()) for im in (a, b) for part in im.parts if part.n)
+    assert len(spans) >= 4 and all(s0[1] <= s1[0] for s0, s1 in zip(spans, spans[1:])), spans
+    for p in m.parameters():
+        assert {k for k in p.__dict__ if k.startswith("_clc_")} <= {"_clc_is_filter", "_clc_direct"}
 
 
 def test_noise_is_fresh_per_replay(dev):

@@ -546,8 +546,10 @@ def test_reduced_precision_mode_bf16(dev):
 
 
 def test_plain_autograd_after_engine_steps_uses_current_filters(dev):
-    """The [Cin][T][Cout] filter images the engine attaches to the parameters for its data-gradient kernels are one optimizer update
-    behind once a step has finished: a plain autograd backward on the same model afterwards must not use them (ops.WT_CACHE_VALID)."""
+    """The engine's per-step images of the weights ([Cin][T][Cout] filters for its data-gradient kernels, packs, GDN parameters) are one
+    optimizer update behind once a step has finished: a plain autograd backward on the same model afterwards must not use them
+    (ops.WT_CACHE_VALID), whether the engine's image set is still the current one or none is.  The images live in the engine's set, never
+    on the Parameters."""
     from clc_amd import ops
     from clc_amd.train import RateDistortionLoss, TrainEngine
 
@@ -557,20 +559,20 @@ def test_plain_autograd_after_engine_steps_uses_current_filters(dev):
     for _ in range(2):
         eng.step(x, refs)
     assert ops.WT_CACHE_VALID is False
-    # gradient of the loss w.r.t. the INPUT image through plain autograd, with and without the engine's cached images present
+    counts = {k: eng.images.count(k) for k in ("wt", "halo", "halo_t", "wino", "wino_t", "gdn")}
+    print("images per kind:", counts)
+    assert counts["wt"] > 0, "the engine built no transposed filter images"
+    assert counts["gdn"] > 0
+    for p in m.parameters():
+        assert {a for a in p.__dict__ if a.startswith("_clc_")} <= {"_clc_is_filter", "_clc_direct"}
+    # gradient of the loss w.r.t. the INPUT image through plain autograd, with the engine's image set current and with none current
     def input_grad():
         xi = x.clone().requires_grad_(True)
         out = RateDistortionLoss(0.0067)(m(xi, refs), xi.detach())
         (g,) = torch.autograd.grad(out["loss"], [xi])
         return g
+    eng.images.make_current()
     g_with = input_grad()
-    saved = {}
-    for p in m.parameters():
-        if hasattr(p, "_clc_wt"):
-            saved[p] = p._clc_wt
-            del p._clc_wt
-    assert saved, "the engine attached no transposed filter images"
+    ops.set_current_images(None)
     g_without = input_grad()
-    for p, wt in saved.items():
-        p._clc_wt = wt
     assert torch.equal(g_with, g_without)
