@@ -85,10 +85,12 @@ def install(force: bool = False):
         done += ["compressai.entropy_models", "compressai.ans", "compressai.layers"]
         _module("compressai.models", CompressionModel=_clc.CompressionModel, ScaleHyperprior=models.ScaleHyperprior,
                 MeanScaleHyperprior=models.MeanScaleHyperprior,
-                JointAutoregressiveHierarchicalPriors=models.JointAutoregressiveHierarchicalPriors)
+                JointAutoregressiveHierarchicalPriors=models.JointAutoregressiveHierarchicalPriors,
+                JointCheckerboardHierarchicalPriors=models.JointCheckerboardHierarchicalPriors)
         _module("compressai.datasets", ImageFolder=ImageFolder)
         _module("compressai.zoo", models={"clc": models.CLC, "tcm": models.TCM, "bmshj2018-hyperprior": models.ScaleHyperprior,
-                                         "mbt2018-mean": models.MeanScaleHyperprior, "mbt2018": models.JointAutoregressiveHierarchicalPriors})
+                                         "mbt2018-mean": models.MeanScaleHyperprior, "mbt2018": models.JointAutoregressiveHierarchicalPriors,
+                                         "mbt2018-checkerboard": models.JointCheckerboardHierarchicalPriors})
         done += ["compressai.models", "compressai.datasets", "compressai.zoo"]
         c = sys.modules["compressai"]
         for sub in ("entropy_models", "ans", "layers", "models", "datasets", "zoo"):

@@ -150,6 +150,42 @@ class MaskedConv2d(Conv2d):
         return super().forward(x, act=act)
 
 
+class CheckerboardMaskedConv2d(nn.Conv2d):
+    """The checkerboard context layer of He et al. (CVPR 2021): a 5x5 'same' convolution whose 12 live taps are the (kh + kw)-odd ones,
+    evaluated at the non-anchor pixels ((h + w) even) and exactly 0 — no bias — at the anchors ((h + w) odd).  A live tap of a non-anchor
+    lands on an anchor or outside the map, so the layer reads anchors only; this equals "zero the non-anchors, convolve with the masked
+    filter, zero the anchors' outputs".  Parameter names ``weight`` / ``bias`` and a registered ``mask`` buffer of the weight's shape, so
+    the ``state_dict`` keys are those of MaskedConv2d and an ``mbt2018`` checkpoint loads.  As MaskedConv2d does, forward multiplies
+    ``weight.data`` by the mask in place; the masked taps' gradients are exactly 0.  Runs on csrc/ckbd_context.hip (ops.ckbd_conv).
+
+    The kernels use the structural tap table, never the buffer's contents.  Loading an ``mbt2018`` state dict overwrites the buffer with
+    mask A: the layer re-establishes its own mask after every load_state_dict.  Only the BUFFER is reset — the loaded weights are kept
+    as they are until the next forward multiplies them by the mask."""
+
+    def __init__(self, in_ch, out_ch, kernel_size=5, padding=2, stride=1, bias=True):
+        if kernel_size != 5 or padding != 2 or stride != 1:
+            raise ValueError("clc_amd.layers.CheckerboardMaskedConv2d supports kernel_size=5, padding=2, stride=1 only "
+                             f"(got kernel_size={kernel_size}, padding={padding}, stride={stride})")
+        if in_ch % 4:
+            raise ValueError(f"clc_amd.layers.CheckerboardMaskedConv2d: in_channels must be a multiple of 4 (got {in_ch})")
+        super().__init__(in_ch, out_ch, 5, stride=1, padding=2, bias=bias)
+        self.weight.data = self.weight.data.contiguous(memory_format=CL)
+        self.weight._clc_is_filter = True
+        self.register_buffer("mask", torch.zeros_like(self.weight.data))
+        self._reset_mask()
+        self.register_load_state_dict_post_hook(lambda module, incompatible_keys: module._reset_mask())
+
+    @torch.no_grad()
+    def _reset_mask(self):
+        self.mask.zero_()
+        for kh, kw in ops.CKBD_TAPS:
+            self.mask[:, :, kh, kw] = 1
+
+    def forward(self, x, act=ACT_NONE):
+        self.weight.data *= self.mask
+        return ops.ckbd_conv(x, self.weight, self.bias, act=act)
+
+
 class Linear(nn.Linear):
     """nn.Linear over the channel dim of a pixel-major [N,C,H,W] tensor (tokens are pixels)."""
 

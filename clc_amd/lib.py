@@ -112,6 +112,19 @@ class ArSrc(C.Structure):
     _fields_ = [("p", fp), ("ld", C.c_int), ("C", C.c_int), ("kind", C.c_int)]
 
 
+class CkbdDesc(C.Structure):
+    _fields_ = [("x", fp), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int), ("ldx", C.c_int),
+                ("w", fp), ("bias", fp),
+                ("y", fp), ("Cout", C.c_int), ("ldy", C.c_int),
+                ("transposed", C.c_int), ("act", C.c_int)]
+
+
+class CkbdWgradDesc(C.Structure):
+    _fields_ = [("x", fp), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int), ("ldx", C.c_int),
+                ("dy", fp), ("Cout", C.c_int), ("lddy", C.c_int),
+                ("dw", fp), ("accumulate", C.c_int)]
+
+
 class ParamEntry(C.Structure):
     _fields_ = [("p", fp), ("g", fp), ("m", fp), ("v", fp), ("n", C.c_long)]
 
@@ -247,6 +260,8 @@ SIGNATURES = {
     "clc_ar_linear": (_i, [C.POINTER(ArSrc), _i, fp, _i, _i, _i, _i, fp, fp, _i, _i, fp, _i, fp]),
     "clc_ar_finish": (_i, [fp, _i, _i, fp, _i, _i, _i, _i, fp, _i, fp, _i, fp, _i, fp, fp, _i, fp]),
     "clc_ar_commit": (_i, [fp, fp, _i, _i, fp, _i, _i, _i, _i, fp, _i, fp]),
+    "clc_ckbd_conv": (_i, [C.POINTER(CkbdDesc), fp]),
+    "clc_ckbd_wgrad": (_i, [C.POINTER(CkbdWgradDesc), fp]),
 }
 
 

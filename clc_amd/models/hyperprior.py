@@ -18,7 +18,7 @@ import torch.nn as nn
 
 from .. import ans, ops
 from ..entropy_models import EntropyBottleneck, GaussianConditional
-from ..layers import GDN, Conv2d, MaskedConv2d, conv, deconv
+from ..layers import GDN, CheckerboardMaskedConv2d, Conv2d, MaskedConv2d, conv, deconv
 from ..ops import ACT_LRELU, ACT_NONE, ACT_RELU, CL
 from .clc import CompressionModel, _resize_registered_buffers, get_scale_table
 
@@ -189,6 +189,18 @@ def ar_schedule(H, W, order="wavefront"):
     return steps
 
 
+def ckbd_pixels(H, W):
+    """(anchors, non-anchors) of an H x W latent under the checkerboard context model, each a raster-ordered list of (h, w): anchors are
+    the pixels with (h + w) odd, coded from the hyperprior alone; non-anchors ((h + w) even, (0, 0) among them) are coded from the
+    hyperprior and the 12 (kh + kw)-odd taps of the 5x5 window, every one of which is an anchor or outside the map."""
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"ckbd_pixels: H and W must be positive (got {H}, {W})")
+    anchors = [(h, w) for h in range(H) for w in range(W) if (h + w) & 1]
+    others = [(h, w) for h in range(H) for w in range(W) if not (h + w) & 1]
+    return anchors, others
+
+
 class JointAutoregressiveHierarchicalPriors(MeanScaleHyperprior):
     """Minnen et al. 2018 with the context model (``mbt2018``): the mean-scale hyperprior plus a masked 5x5 convolution over the coded
     latent and a three-layer 1x1 ``entropy_parameters`` net on cat((hyper parameters, context)).
@@ -201,7 +213,7 @@ class JointAutoregressiveHierarchicalPriors(MeanScaleHyperprior):
 
     def __init__(self, N=192, M=192, **kwargs):
         if M % 12:
-            raise ValueError(f"JointAutoregressiveHierarchicalPriors needs M % 12 == 0 (then 10M/3, 8M/3 and 3M/2 are whole and multiples of 4, the "
+            raise ValueError(f"{type(self).__name__} needs M % 12 == 0 (then 10M/3, 8M/3 and 3M/2 are whole and multiples of 4, the "
                              f"kernels' aligned path); got M = {M}" + (": M = 320 (mbt2018 qualities 5-8) is not built" if M == 320 else ""))
         super().__init__(N=N, M=M, **kwargs)
         self.entropy_parameters = nn.Sequential(Conv2d(M * 4, M * 10 // 3, 1), nn.LeakyReLU(inplace=True),
@@ -341,4 +353,149 @@ class JointAutoregressiveHierarchicalPriors(MeanScaleHyperprior):
                 sym_np[b] = d.decode_stream(idx_np[b], cdf, ln, off)
             sym_dev.copy_(sym_host, non_blocking=True)
             ops.ar_commit(sym_dev, ws["gp"], M, px, y_hat)
+        return {"x_hat": self._synthesis(y_hat).clamp_(0, 1)}
+
+
+class JointCheckerboardHierarchicalPriors(JointAutoregressiveHierarchicalPriors):
+    """The checkerboard context model of He et al. (CVPR 2021) on the ``mbt2018`` architecture: the same g_a / g_s / h_a / h_s, the same
+    ``entropy_parameters`` and the same ``state_dict`` keys, with ``context_prediction`` a CheckerboardMaskedConv2d (csrc/ckbd_context.hip).
+    Half of the latent pixels — the anchors, (h + w) odd — are coded from the hyperprior alone, the other half from the hyperprior plus a
+    5x5 convolution over the anchors only: encoder and decoder both take two parallel passes, whatever the image size.
+
+    forward is a single pass in training and in eval: the layer reads anchors only and returns 0 at anchors, which equals the usual "zero
+    the non-anchors, convolve, zero the anchors' outputs".
+
+    The coder.  Pass 1 runs the three 1x1 layers on the anchor list with a zero context map (fmaf(0, w, acc) == acc, so the zero range
+    changes nothing) and finishes the anchors; pass 2 evaluates the context layer over the whole map in one launch and runs the same
+    layers on the non-anchor list.  The 1x1 layers run on clc_ar_linear, whose summation order is a function of K alone; the context
+    layer on ckbd_conv_kernel, whose order is a function of Cin alone; h_s on the batch-invariant kernels: a stream written at batch 8
+    decodes at batch 1.
+
+    STREAM ORDER: one rANS stream per image for y — all anchors in raster order, then all non-anchors in raster order, channels inner;
+    z as in the other hyperprior models.  This is the project's own order: CompressAI is not a dependency and is not installed where
+    this is built, so nothing here is pinned against its checkerboard classes."""
+
+    def __init__(self, N=192, M=192, **kwargs):
+        super().__init__(N=N, M=M, **kwargs)
+        self.context_prediction = CheckerboardMaskedConv2d(M, 2 * M, kernel_size=5, padding=2, stride=1)
+
+    def _ar_encode(self, y, params, order="wavefront"):
+        raise NotImplementedError("JointCheckerboardHierarchicalPriors has no autoregressive pass (mask A): the coder is _ckbd_encode / _ckbd_decode")
+
+    # ---- the two-pass coder ----
+    def _ckbd_lists(self, H, W, dev):
+        """(number of anchors, number of non-anchors, the uploaded pixel list: anchors first)"""
+        anchors, others = ckbd_pixels(H, W)
+        return len(anchors), len(others), torch.tensor(anchors + others, dtype=torch.int32).reshape(-1, 2).to(dev)
+
+    def _ckbd_workspace(self, rows, dev):
+        M = self.M
+        mk = lambda c: torch.empty((rows, c), device=dev, dtype=torch.float32)
+        return {"h1": mk(M * 10 // 3), "h2": mk(M * 8 // 3), "gp": mk(2 * M)}
+
+    def _ckbd_chain(self, px, B, H, W, params, ctx_map, ws, filt):
+        """(scales | means) of the listed pixels of every image -> ws["gp"]; three launches.  filt: _ckbd_filters()"""
+        ops.ar_linear([("pixel", params), ("pixel", ctx_map)], px, B, H, W, filt[0][0], filt[0][1], ws["h1"], act=ACT_LRELU)
+        ops.ar_linear([("dense", ws["h1"])], px, B, H, W, filt[1][0], filt[1][1], ws["h2"], act=ACT_LRELU)
+        ops.ar_linear([("dense", ws["h2"])], px, B, H, W, filt[2][0], filt[2][1], ws["gp"])
+
+    def _ckbd_filters(self):
+        ep = self.entropy_parameters
+        out = []
+        for i in (0, 2, 4):
+            w = ep[i].weight.detach()
+            out.append((w.reshape(w.shape[0], w.shape[1]).contiguous(), ep[i].bias.detach().contiguous()))
+        return out
+
+    @torch.no_grad()
+    def _ckbd_encode(self, y, params):
+        """The two passes of compress -> (symbols int32 [B, H*W, M], indexes int32 [B, H*W, M], y_hat), the buffers in raster order: all
+        launches on the current stream, no host sync."""
+        ops._require_gpu(y, "mbt2018-checkerboard compress")
+        B, M, H, W = y.shape
+        y = y.contiguous(memory_format=CL)
+        params = params.contiguous(memory_format=CL)
+        na, nn_, pix = self._ckbd_lists(H, W, y.device)
+        ws = self._ckbd_workspace(B * max(na, nn_), y.device)
+        filt = self._ckbd_filters()
+        table = self.gaussian_conditional.scale_table
+        y_hat = torch.zeros_like(y, memory_format=CL)
+        sym = torch.empty((B, H * W, M), device=y.device, dtype=torch.int32)
+        idx = torch.empty((B, H * W, M), device=y.device, dtype=torch.int32)
+        if na:
+            ctx_map = torch.zeros((B, 2 * M, H, W), device=y.device, dtype=torch.float32).contiguous(memory_format=CL)
+            self._ckbd_chain(pix[:na], B, H, W, params, ctx_map, ws, filt)
+            ops.ar_finish_encode(ws["gp"], M, pix[:na], y, y_hat, table, sym, idx)
+        ctx_map = self.context_prediction(y_hat)
+        self._ckbd_chain(pix[na:], B, H, W, params, ctx_map, ws, filt)
+        ops.ar_finish_encode(ws["gp"], M, pix[na:], y, y_hat, table, sym, idx)
+        return sym, idx, y_hat
+
+    @staticmethod
+    def _ckbd_order(H, W):
+        """raster positions h * W + w in the stream's order: anchors, then non-anchors"""
+        anchors, others = ckbd_pixels(H, W)
+        return np.array([h * W + w for h, w in anchors + others], dtype=np.int64)
+
+    @torch.no_grad()
+    def compress(self, x):
+        y, params, z_strings, z_size = self._code_inputs(x)
+        cdf, ln, off = self.gaussian_conditional.host_tables()
+        sym, idx, _ = self._ckbd_encode(y, params)
+        both = torch.stack((sym, idx)).cpu().numpy()   # the one device -> host copy: [2, B, H*W, M], raster pixels, channels inner
+        order = self._ckbd_order(y.shape[2], y.shape[3])
+        y_strings = [ans.encode(np.ascontiguousarray(both[0, i][order]).reshape(-1), np.ascontiguousarray(both[1, i][order]).reshape(-1), cdf, ln, off)
+                     for i in range(both.shape[1])]
+        from ..codec import kernel_config
+
+        return {"strings": [y_strings, z_strings], "shape": z_size, "kernel_config": kernel_config()}
+
+    @torch.no_grad()
+    def _ckbd_decode(self, y_strings, params):
+        """The two passes of decompress -> y_hat: per pass one index download, one incremental decode per image, one symbol upload."""
+        params = params.contiguous(memory_format=CL)
+        dev = params.device
+        B, M, (H, W) = params.shape[0], self.M, params.shape[2:]
+        if len(y_strings) != B:
+            raise ValueError(f"decompress: {len(y_strings)} y streams for {B} z streams")
+        cdf, ln, off = self.gaussian_conditional.host_tables()
+        table = self.gaussian_conditional.scale_table
+        na, nn_, pix = self._ckbd_lists(H, W, dev)
+        rows = B * max(na, nn_)
+        ws = self._ckbd_workspace(rows, dev)
+        filt = self._ckbd_filters()
+        y_hat = torch.zeros((B, M, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
+        decoders = []
+        for s in y_strings:
+            d = ans.RansDecoder()
+            d.set_stream(s)
+            decoders.append(d)
+        idx_dev = torch.empty((rows, M), device=dev, dtype=torch.int32)
+        sym_dev = torch.empty((rows, M), device=dev, dtype=torch.int32)
+        idx_host = torch.empty((rows, M), dtype=torch.int32).pin_memory()
+        sym_host = torch.empty((rows, M), dtype=torch.int32).pin_memory()
+        idx_np, sym_np = idx_host.numpy(), sym_host.numpy()
+        stream = torch.cuda.current_stream(dev)
+        ctx_map = torch.zeros((B, 2 * M, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
+        for lo, cnt in ((0, na), (na, nn_)):
+            if not cnt:
+                continue
+            px = pix[lo:lo + cnt]
+            if lo:
+                ctx_map = self.context_prediction(y_hat)
+            self._ckbd_chain(px, B, H, W, params, ctx_map, ws, filt)
+            ops.ar_finish_decode(ws["gp"], M, px, B, H, W, table, idx_dev)
+            idx_host.copy_(idx_dev, non_blocking=True)
+            stream.synchronize()   # (also: the previous pass's symbol upload has left sym_host)
+            for b, d in enumerate(decoders):   # rows b * cnt .. of the pass are image b's pixels in list order, channels inner
+                sym_np[b * cnt:(b + 1) * cnt] = d.decode_stream(idx_np[b * cnt:(b + 1) * cnt].reshape(-1), cdf, ln, off).reshape(cnt, M)
+            sym_dev.copy_(sym_host, non_blocking=True)
+            ops.ar_commit(sym_dev, ws["gp"], M, px, y_hat)
+        return y_hat
+
+    @torch.no_grad()
+    def decompress(self, strings, shape):
+        assert isinstance(strings, (list, tuple)) and len(strings) == 2
+        z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
+        y_hat = self._ckbd_decode(strings[0], self._hyper_synthesis(z_hat))
         return {"x_hat": self._synthesis(y_hat).clamp_(0, 1)}

@@ -2687,3 +2687,107 @@ def ar_commit(symbols, gp, M, pix, y_hat):
     if gp.shape[1] < 2 * M or lds != M or Ch != M:
         raise ValueError(f"ar_commit: gp needs 2 M = {2 * M} columns, symbols a dense [rows, M = {M}] buffer, y_hat M channels")
     _lib.check(_L().clc_ar_commit(sp, gpp, ldg, M, pp, P, B, H, W, hp, ldh, _stream()), "clc_ar_commit")
+
+
+# ------------------------------------------------------------------- checkerboard context layer (csrc/ckbd_context.hip)
+# Anchors are the pixels with (h + w) odd.  The 12 live taps of the 5x5 window, (kh + kw) odd, in (kh, kw) ascending order:
+CKBD_TAPS = tuple((kh, kw) for kh in range(5) for kw in range(5) if (kh + kw) & 1)
+_CKBD_IDX = {}
+
+
+def _ckbd_tap_index(dev):
+    """int64 [12] positions of the live taps among the 25 (kh, kw) positions, on the device"""
+    t = _CKBD_IDX.get(dev)
+    if t is None:
+        t = _CKBD_IDX[dev] = torch.tensor([kh * 5 + kw for kh, kw in CKBD_TAPS], dtype=torch.int64, device=dev)
+    return t
+
+
+def ckbd_filter(w):
+    """[Cout, Cin, 5, 5] parameter -> the kernel's [Cout][12][Cin] filter image (the live taps of the channels-last filter)"""
+    Cout, Cin = w.shape[0], w.shape[1]
+    return to_kernel_weight(w).permute(0, 2, 3, 1).reshape(Cout, 25, Cin).index_select(1, _ckbd_tap_index(w.device)).contiguous()
+
+
+def ckbd_conv_raw(x, w12, bias, Cout, *, transposed=False, act=ACT_NONE):
+    """clc_ckbd_conv: x a pixel-major [B, Cin, H, W] map (a channel slice is read in place), w12 [Cout][12][Cin] (transposed: the
+    clc_filter_transpose image) -> a new [B, Cout, H, W] map, every element written by the one launch."""
+    x, xp, B, H, W, Cin, ldx = nhwc(x)
+    y = new_act(B, Cout, H, W, x)
+    d = _lib.CkbdDesc()
+    d.x, d.B, d.H, d.W, d.Cin, d.ldx = xp, B, H, W, Cin, ldx
+    d.w, d.bias = w12.data_ptr(), (bias.data_ptr() if bias is not None else None)
+    d.y, d.Cout, d.ldy = y.data_ptr(), Cout, Cout
+    d.transposed, d.act = int(transposed), act
+    _prof_hint(2.0 * B * H * ((W + 1) // 2) * 12 * Cin * Cout, f"ckbd {Cin}->{Cout} {'T ' if transposed else ''}{B}x{H}x{W}")
+    _lib.check(_L().clc_ckbd_conv(C.byref(d), _stream()), "clc_ckbd_conv")
+    return y
+
+
+def ckbd_wgrad_raw(x, dy, Cout, Cin, dw_out=None):
+    """clc_ckbd_wgrad -> dw [Cout][12][Cin]; with dw_out the result is accumulated into it"""
+    x, xp, B, H, W, _, ldx = nhwc(x)
+    dy, dp, *_r, lddy = nhwc(dy)
+    dw = dw_out if dw_out is not None else torch.empty((Cout, 12, Cin), device=x.device, dtype=torch.float32)
+    d = _lib.CkbdWgradDesc()
+    d.x, d.B, d.H, d.W, d.Cin, d.ldx = xp, B, H, W, Cin, ldx
+    d.dy, d.Cout, d.lddy = dp, Cout, lddy
+    d.dw, d.accumulate = dw.data_ptr(), int(dw_out is not None)
+    _prof_hint(2.0 * B * H * ((W + 1) // 2) * 12 * Cin * Cout, f"ckbd wgrad {Cin}->{Cout} {B}x{H}x{W}")
+    _lib.check(_L().clc_ckbd_wgrad(C.byref(d), _stream()), "clc_ckbd_wgrad")
+    return dw
+
+
+def ckbd_nonanchor_mask(H, W, dev):
+    """float32 [1, 1, H, W]: 1 where (h + w) is even"""
+    hh = torch.arange(H, device=dev).view(H, 1)
+    ww = torch.arange(W, device=dev).view(1, W)
+    return (((hh + ww) & 1) == 0).to(torch.float32).view(1, 1, H, W)
+
+
+class _CkbdConvFn(Function):
+    """y = act(checkerboard-masked 5x5 convolution of x + b) at the non-anchors, exactly 0 at the anchors; w is the [Cout, Cin, 5, 5]
+    parameter, of which the 12 (kh + kw)-odd taps are read.  Backward: dx on the transposed launch (anchors; 0 at non-anchors), dw on
+    the filter-gradient launch, scattered into the parameter's shape with exact zeros at the 13 masked taps, db = column sums of dz over
+    the non-anchors.  An anchor's dy reaches none of them.  Launched in line; f32 whatever set_precision says."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, act):
+        _own(ctx)
+        if x.dim() != 4 or w.dim() != 4 or tuple(w.shape[2:]) != (5, 5) or x.shape[1] != w.shape[1]:
+            raise _lib.ClcError(f"ckbd_conv: input {tuple(x.shape)} does not match the filter {tuple(w.shape)} (expected [Cout, Cin, 5, 5] and Cin input channels)")
+        if act not in (ACT_NONE, ACT_LRELU):
+            raise _lib.ClcError(f"ckbd_conv: act must be ACT_NONE or ACT_LRELU (got {act})")
+        y = ckbd_conv_raw(x, ckbd_filter(w), b, int(w.shape[0]), act=act)
+        ctx.act, ctx.has_b = act, b is not None
+        ctx.save_for_backward(x, w, y if (act != ACT_NONE and _recording(ctx)) else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        _reown(ctx)
+        x, w, y = ctx.saved_tensors
+        Cout, Cin = int(w.shape[0]), int(w.shape[1])
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_b and ctx.needs_input_grad[2]
+        dz = dy if ctx.act == ACT_NONE else act_bwd(dy, y, False, ctx.act)
+        dx = dw = db = None
+        if need_x:
+            if Cout % 4:
+                raise _lib.ClcError(f"ckbd_conv: the data gradient needs Cout % 4 == 0 (dy feeds the aligned loaders; got Cout={Cout})")
+            wt = filter_transpose(ckbd_filter(w), Cout, 12, Cin)   # [Cin][12][Cout]
+            dx = ckbd_conv_raw(dz, wt, None, Cin, transposed=True)
+        if need_w:
+            dw12 = ckbd_wgrad_raw(x, dz, Cout, Cin)
+            full = torch.zeros((Cout, 25, Cin), device=dw12.device, dtype=torch.float32)
+            full.index_copy_(1, _ckbd_tap_index(dw12.device), dw12)
+            dw = full.view(Cout, 5, 5, Cin).permute(0, 3, 1, 2)   # logical OIHW, channels_last strides
+        if need_b:
+            db = colsum(dz * ckbd_nonanchor_mask(dz.shape[2], dz.shape[3], dz.device))
+        return dx, dw, db, None
+
+
+def ckbd_conv(x, w, b=None, act=ACT_NONE):
+    """The checkerboard context layer: see _CkbdConvFn and include/clc_hip.h (clc_ckbd_conv)."""
+    _require_gpu(x, "ckbd_conv")
+    _note_grad_mode()
+    return _CkbdConvFn.apply(x, w, b, act)

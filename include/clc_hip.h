@@ -710,6 +710,49 @@ int clc_ar_finish(const float* gp, int ldg, int M, const int32_t* pix, int P, in
 int clc_ar_commit(const int32_t* symbols, const float* gp, int ldg, int M, const int32_t* pix, int P, int B, int H, int W, float* y_hat,
                   int ldh, clc_stream_t stream);
 
+/* ---- the checkerboard context layer (He et al., CVPR 2021; JointCheckerboardHierarchicalPriors; ckbd_context.hip) ----
+ * What they replace: the dense masked layer — layers.MaskedConv2d -> conv5_kernel on the 25-tap filter with 13 taps multiplied by zero,
+ * then zeroing the anchors of the result — which spends 25 * 2 / 12 = 4.2 times the multiplications the layer needs.
+ *
+ * PARITY: a pixel (h, w) of the NHWC [B][H][W][ld] map is an ANCHOR iff (h + w) is odd, a NON-ANCHOR iff (h + w) is even; (0, 0) is a
+ * non-anchor.  TAPS: (kh, kw) of the 5x5 / pad-2 window is live iff (kh + kw) is odd: 12 taps, in (kh, kw) ascending order
+ *   (0,1) (0,3) (1,0) (1,2) (1,4) (2,1) (2,3) (3,0) (3,2) (3,4) (4,1) (4,3)
+ * — the centre is not one of them, a live tap of a non-anchor lands on an anchor or outside the map, and the set is symmetric under
+ * (kh, kw) -> (4 - kh, 4 - kw).  Filters are [Cout][12][Cin] in that tap order.
+ *
+ * clc_ckbd_conv   transposed = 0: y[non-anchor p][co] = act(bias[co] + sum_t sum_ci x[p + offset_t][ci] w[co][t][ci]), y[anchor] = 0.0f
+ *                 exactly (no bias); act CLC_ACT_NONE or CLC_ACT_LRELU.  transposed = 1 (the data gradient; x is dy with Cin = the
+ *                 layer's output channels, w the [Cin][12][Cout] image clc_filter_transpose(w, Cout, 12, Cin) makes of the layer's
+ *                 filter): y[anchor p] = sum_t x[p - offset_t] w[.][t][.], y[non-anchor] = 0.0f; p - offset_t is a non-anchor, an
+ *                 anchor's x is never read.  ONE launch writes every element of the output map (no memset needed), no workspace.
+ *                 ORDER RULE: taps outside the map contribute exact zeros and are never skipped; every output element is summed in
+ *                 the order (tap ascending, 32-channel chunks ascending, inside a chunk by MFMA and lane half) — a function of Cin
+ *                 alone, not of B, the image's place in the batch, H, W or the tile the pixel lands in.  A stream written from a batch
+ *                 of 8 therefore decodes one image at a time.
+ * clc_ckbd_wgrad  dw[co][t][ci] (+)= sum over the non-anchor pixels p of all images of dy[p][co] x[p + offset_t][ci]; an anchor's dy is
+ *                 never read.  A single pass: every dw element is written once by one lane (read-modified-written with accumulate);
+ *                 no atomics, no workspace.  The bias gradient is the column sum of dy over the non-anchor pixels (clc_colsum of a
+ *                 masked dy).
+ * Both: Cin % 4 == 0, ldx % 4 == 0, 16-byte aligned x (and w), any Cout (16-byte stores when Cout % 4 == 0, ldy % 4 == 0 and y is
+ * aligned, scalar otherwise), any H, W >= 1, B * H * W < 2^31; anything else is refused by name.  Stream-ordered, graph-capturable,
+ * allocation- and sync-free, no workgroup waits on another. */
+typedef struct {
+  const float* x; int B, H, W, Cin, ldx;   /* NHWC input map (transposed: dy) */
+  const float* w;                          /* [Cout][12][Cin] */
+  const float* bias;                       /* [Cout] or NULL */
+  float* y; int Cout, ldy;                 /* NHWC output map, written whole */
+  int transposed;                          /* 0 forward (non-anchors), 1 data gradient (anchors) */
+  int act;                                 /* CLC_ACT_NONE or CLC_ACT_LRELU */
+} clc_ckbd_desc;
+typedef struct {
+  const float* x; int B, H, W, Cin, ldx;   /* the layer's input map */
+  const float* dy; int Cout, lddy;         /* gradient of the layer's output map (read at non-anchors only) */
+  float* dw;                               /* [Cout][12][Cin] */
+  int accumulate;                          /* 0: dw = ..., 1: dw += ... */
+} clc_ckbd_wgrad_desc;
+int clc_ckbd_conv(const clc_ckbd_desc* d, clc_stream_t stream);
+int clc_ckbd_wgrad(const clc_ckbd_wgrad_desc* d, clc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
