@@ -86,11 +86,11 @@ def install(force: bool = False):
         _module("compressai.models", CompressionModel=_clc.CompressionModel, ScaleHyperprior=models.ScaleHyperprior,
                 MeanScaleHyperprior=models.MeanScaleHyperprior,
                 JointAutoregressiveHierarchicalPriors=models.JointAutoregressiveHierarchicalPriors,
-                JointCheckerboardHierarchicalPriors=models.JointCheckerboardHierarchicalPriors)
+                JointCheckerboardHierarchicalPriors=models.JointCheckerboardHierarchicalPriors, Elic2022=models.Elic2022)
         _module("compressai.datasets", ImageFolder=ImageFolder)
         _module("compressai.zoo", models={"clc": models.CLC, "tcm": models.TCM, "bmshj2018-hyperprior": models.ScaleHyperprior,
                                          "mbt2018-mean": models.MeanScaleHyperprior, "mbt2018": models.JointAutoregressiveHierarchicalPriors,
-                                         "mbt2018-checkerboard": models.JointCheckerboardHierarchicalPriors})
+                                         "mbt2018-checkerboard": models.JointCheckerboardHierarchicalPriors, "elic2022": models.Elic2022})
         done += ["compressai.models", "compressai.datasets", "compressai.zoo"]
         c = sys.modules["compressai"]
         for sub in ("entropy_models", "ans", "layers", "models", "datasets", "zoo"):

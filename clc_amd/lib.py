@@ -262,6 +262,7 @@ SIGNATURES = {
     "clc_ar_commit": (_i, [fp, fp, _i, _i, fp, _i, _i, _i, _i, fp, _i, fp]),
     "clc_ckbd_conv": (_i, [C.POINTER(CkbdDesc), fp]),
     "clc_ckbd_wgrad": (_i, [C.POINTER(CkbdWgradDesc), fp]),
+    "clc_row_gemm": (_i, [C.POINTER(ArSrc), _i, fp, _i, _i, _i, _i, fp, fp, _i, _i, fp, _i, fp]),
 }
 
 

@@ -2,6 +2,7 @@
 from .clc import CLC, TCM  # noqa: F401
 from .hyperprior import (JointAutoregressiveHierarchicalPriors, JointCheckerboardHierarchicalPriors, MeanScaleHyperprior,  # noqa: F401
                          ScaleHyperprior, ar_schedule, ckbd_pixels)
+from .elic import Elic2022, scctx_order  # noqa: F401
 
 __all__ = ["TCM", "CLC", "ScaleHyperprior", "MeanScaleHyperprior", "JointAutoregressiveHierarchicalPriors", "JointCheckerboardHierarchicalPriors",
-           "ar_schedule", "ckbd_pixels"]
+           "Elic2022", "ar_schedule", "ckbd_pixels", "scctx_order"]

@@ -2649,6 +2649,46 @@ def ar_linear(srcs, pix, B, H, W, w, bias, out, act=ACT_NONE):
     return out
 
 
+def row_gemm(srcs, pix, B, H, W, w, bias, out, act=ACT_NONE):
+    """clc_row_gemm (csrc/row_gemm.hip): ar_linear's contract on the matrix cores — out[r, :N] = act(bias + sum_k in(r, k) w[n, k]) for
+    the rows r = b * P + p of the pixel list.  srcs: one to four (kind, tensor) ranges of the K axis, ("dense", [rows, C] buffer) or
+    ("pixel", map; a channel slice of a map is read in place); "taps" stays with ar_linear.  act: ACT_NONE, ACT_LRELU or ACT_RELU.
+    Every element's summation order depends on the C of each range alone — and is NOT ar_linear's: never mix the two in one stream."""
+    pp, P = _ar_pix(pix)
+    rows = B * P
+    if not 1 <= len(srcs) <= 4:
+        raise ValueError(f"row_gemm: one to four K ranges (got {len(srcs)})")
+    arr, K = (_lib.ArSrc * 4)(), 0
+    for i, (kind, t) in enumerate(srcs):
+        if kind == "taps":
+            raise ValueError("row_gemm: a 'taps' range is not taken (the gather stays with ar_linear)")
+        if kind not in AR_KINDS:
+            raise ValueError(f"row_gemm: unknown source kind {kind!r} (dense or pixel)")
+        if kind == "dense":
+            _require_gpu(t, "row_gemm")
+            p, ld = _ar_dense(t, rows, "row_gemm dense range")
+            Cc = int(t.shape[1])
+        else:
+            p, Bm, Hm, Wm, Cc, ld = _ar_map(t, "row_gemm")
+            if (Bm, Hm, Wm) != (B, H, W):
+                raise ValueError(f"row_gemm: map {tuple(t.shape)} does not match B, H, W = {B}, {H}, {W}")
+        arr[i] = _lib.ArSrc(p, ld, Cc, AR_KINDS[kind])
+        K += Cc
+    _require_gpu(w, "row_gemm")
+    if w.dim() != 2 or not w.is_contiguous() or w.shape[1] != K or w.dtype != torch.float32:
+        raise ValueError(f"row_gemm: the filter must be a contiguous float32 [N, K = {K}] matrix (got {tuple(w.shape)})")
+    N = int(w.shape[0])
+    if bias is not None and (bias.numel() != N or not bias.is_contiguous() or bias.dtype != torch.float32 or not bias.is_cuda):
+        raise ValueError("row_gemm: bias must be a contiguous float32 [N] device tensor")
+    op, ldo = _ar_dense(out, rows, "row_gemm out")
+    if out.shape[1] < N:
+        raise ValueError(f"row_gemm: out has {out.shape[1]} columns, N = {N}")
+    _prof_hint(2.0 * rows * K * N, f"row_gemm {K}->{N} {rows} rows")
+    _lib.check(_L().clc_row_gemm(arr, len(srcs), pp, P, B, H, W, w.data_ptr(), bias.data_ptr() if bias is not None else None, N, act, op, ldo,
+                                 _stream()), "clc_row_gemm")
+    return out
+
+
 def ar_finish_encode(gp, M, pix, y, y_hat, scale_table, symbols, indexes):
     """clc_ar_finish, encode mode: gp [rows, >= 2M] (scales | means) -> y_hat map in place, symbols / indexes int32 [B, H*W, M] at the
     pixels' raster places.  The arithmetic of quantize_build_indexes, bit for bit."""

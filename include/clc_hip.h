@@ -753,6 +753,30 @@ typedef struct {
 int clc_ckbd_conv(const clc_ckbd_desc* d, clc_stream_t stream);
 int clc_ckbd_wgrad(const clc_ckbd_wgrad_desc* d, clc_stream_t stream);
 
+/* ---- the batch-invariant row GEMM of the space-channel context model (ELIC, He et al., CVPR 2022; models.Elic2022; row_gemm.hip) ----
+ * What it replaces: the 1x1 "parameter aggregation" layers of the per-group checkerboard passes on clc_ar_linear — one wave per (output
+ * channel, 8 rows) on the plain VALU, every wave re-reading its rows and its filter row — at the 768 .. 6 144 rows and 704 .. 1 408 ->
+ * 640 -> 512 channels such a pass has.
+ *
+ * clc_row_gemm    the contract of clc_ar_linear: rows r = b * P + p over a pixel list, w [N][K] row-major with K = sum of C_s,
+ *                 out[r][n] = act(bias[n] + sum_k in(r, k) * w[n][k]) into a dense [rows][ldo] buffer.  nsrc is 1 to 4 consecutive K
+ *                 ranges, each CLC_AR_SRC_DENSE or CLC_AR_SRC_PIXEL (CLC_AR_SRC_TAPS is refused by name: the gather stays with
+ *                 clc_ar_linear); act is CLC_ACT_NONE, CLC_ACT_LRELU or CLC_ACT_RELU.  f32 on v_mfma_f32_32x32x2_f32: a workgroup of
+ *                 four waves owns 128 rows x 64 output channels, a K-step is 32 channels of one range, both operands go through
+ *                 [rows][32 + 4] LDS images, two stages, one barrier per step.  A row whose pixel lies outside the H x W map is
+ *                 zero-filled on load and never stored.
+ *                 ORDER RULE: every output element sums its ranges in order, within a range the 32-channel chunks ascending — the last
+ *                 chunk of a range zero-filled on both operands, never skipped — and inside a chunk by MFMA and lane half (lane half h
+ *                 takes k = 8 ks + 4 h + {0..3}, ks = 0..3); then bias + sum, then the activation.  A function of (C_1, ..., C_nsrc)
+ *                 alone: not of P, B, the row's place in the list, the tile it lands in or the grid.  This is NOT the order of
+ *                 clc_ar_linear: the two are not interchangeable inside one stream.
+ * Requires per range C % 4 == 0, ld % 4 == 0, ld >= C and a 16-byte aligned base, a 16-byte aligned w, ldo >= N; any N >= 1 (16-byte
+ * stores when N % 4 == 0, ldo % 4 == 0 and out is aligned, scalar otherwise), any row count with B * P < 2^31, B * H * W < 2^31;
+ * anything else is refused by name.  Stream-ordered, graph-capturable, allocation- and sync-free, no workspace, no workgroup waits on
+ * another. */
+int clc_row_gemm(const clc_ar_src* srcs /* HOST */, int nsrc, const int32_t* pix, int P, int B, int H, int W, const float* w, const float* bias,
+                 int N, int act, float* out, int ldo, clc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
