@@ -47,6 +47,24 @@ def encode(symbols, indexes, cdfs, cdfs_sizes, offsets) -> bytes:
     return buf[:n].tobytes()
 
 
+def encode_direct(triples) -> bytes:
+    """One stream from per-symbol (start, freq, esc) int32 triples ([n, 3], or flat 3 n) read from each symbol's own CDF row
+    (clc_rans_encode_direct): the bytes ``encode`` gives for the same symbols coded through their full rows."""
+    L = _lib.load()
+    t = _i32(triples).reshape(-1)
+    if t.size % 3:
+        raise ValueError(f"encode_direct: the triples must be 3 n int32 values (got {t.size})")
+    n = t.size // 3
+    cap = L.clc_rans_encode_bound(n)
+    buf = np.empty(cap, dtype=np.uint8)
+    nb = L.clc_rans_encode_direct(t.ctypes.data, n, buf.ctypes.data, cap)
+    _lib.check(nb, "clc_rans_encode_direct")
+    return buf[:nb].tobytes()
+
+
+_ROW_INDEX = {}   # n -> (arange(n), full(n, size)) int32: the index / size arrays of a decode over per-symbol rows
+
+
 class _Decoder:
     def __init__(self, stream: bytes):
         L = _lib.load()
@@ -67,6 +85,26 @@ class _Decoder:
                                       out.ctypes.data)
         _lib.check(n, "clc_rans_decoder_decode")
         self.words = n
+        return out
+
+    def decode_rows(self, rows, offsets):
+        """The next n symbols, symbol i through its own row rows[i] (int32 [n, size], every entry used) at offsets[i]: numpy arrays
+        (views of pinned buffers as they are), nothing goes through a Python list."""
+        L = _lib.load()
+        for a, what in ((rows, "rows"), (offsets, "offsets")):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.int32 and a.flags.c_contiguous):
+                raise ValueError(f"decode_rows: {what} must be a C-contiguous int32 numpy array")
+        if rows.ndim != 2 or offsets.size != rows.shape[0]:
+            raise ValueError(f"decode_rows: rows [n, size] and n offsets (got {rows.shape}, {offsets.shape})")
+        n, size = rows.shape
+        key = (n, size)
+        if key not in _ROW_INDEX:
+            _ROW_INDEX[key] = (np.arange(n, dtype=np.int32), np.full(n, size, dtype=np.int32))
+        idx, ln = _ROW_INDEX[key]
+        out = np.empty(n, dtype=np.int32)
+        w = L.clc_rans_decoder_decode(self._h, idx.ctypes.data, n, rows.ctypes.data, size, ln.ctypes.data, offsets.ctypes.data, out.ctypes.data)
+        _lib.check(w, "clc_rans_decoder_decode")
+        self.words = w
         return out
 
     def close(self):
@@ -128,6 +166,12 @@ class RansDecoder:
             raise ValueError("set_stream() must be called first")
         out = self._d.decode(indexes, cdfs, cdfs_sizes, offsets)
         return out if isinstance(indexes, np.ndarray) else out.tolist()
+
+    def decode_rows(self, rows, offsets):
+        """decode_stream over per-symbol CDF rows (see _Decoder.decode_rows)"""
+        if self._d is None:
+            raise ValueError("set_stream() must be called first")
+        return self._d.decode_rows(rows, offsets)
 
     def decode_with_indexes(self, stream, indexes, cdfs, cdfs_sizes, offsets):
         self.set_stream(stream)

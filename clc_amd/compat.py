@@ -86,11 +86,13 @@ def install(force: bool = False):
         _module("compressai.models", CompressionModel=_clc.CompressionModel, ScaleHyperprior=models.ScaleHyperprior,
                 MeanScaleHyperprior=models.MeanScaleHyperprior,
                 JointAutoregressiveHierarchicalPriors=models.JointAutoregressiveHierarchicalPriors,
-                JointCheckerboardHierarchicalPriors=models.JointCheckerboardHierarchicalPriors, Elic2022=models.Elic2022)
+                JointCheckerboardHierarchicalPriors=models.JointCheckerboardHierarchicalPriors, Elic2022=models.Elic2022,
+                Cheng2020Anchor=models.Cheng2020Anchor, Cheng2020Attention=models.Cheng2020Attention)
         _module("compressai.datasets", ImageFolder=ImageFolder)
         _module("compressai.zoo", models={"clc": models.CLC, "tcm": models.TCM, "bmshj2018-hyperprior": models.ScaleHyperprior,
                                          "mbt2018-mean": models.MeanScaleHyperprior, "mbt2018": models.JointAutoregressiveHierarchicalPriors,
-                                         "mbt2018-checkerboard": models.JointCheckerboardHierarchicalPriors, "elic2022": models.Elic2022})
+                                         "mbt2018-checkerboard": models.JointCheckerboardHierarchicalPriors, "elic2022": models.Elic2022,
+                                         "cheng2020-anchor": models.Cheng2020Anchor, "cheng2020-attn": models.Cheng2020Attention})
         done += ["compressai.models", "compressai.datasets", "compressai.zoo"]
         c = sys.modules["compressai"]
         for sub in ("entropy_models", "ans", "layers", "models", "datasets", "zoo"):

@@ -111,6 +111,16 @@ inline void enc_put_bits(uint64_t& x, BackWriter& o, uint32_t val) {
   if (x >= x_max) { o.put((uint32_t)x); x >>= 32; }
   x = (x << kBypassBits) | val;
 }
+// the bypass escape of a symbol outside its CDF's support; forward order is: symbol, count (unary in 15s), nibbles LSB first -> emitted
+// in reverse, before the symbol
+inline void enc_put_escape(uint64_t& x, BackWriter& o, uint32_t raw) {
+  int nb = 0;
+  while (nb < 8 && (raw >> (nb * kBypassBits)) != 0) ++nb;
+  for (int j = nb - 1; j >= 0; --j) enc_put_bits(x, o, (raw >> (j * kBypassBits)) & kBypassMax);
+  const int full = nb / (int)kBypassMax, rem = nb % (int)kBypassMax;
+  enc_put_bits(x, o, (uint32_t)rem);
+  for (int j = 0; j < full; ++j) enc_put_bits(x, o, kBypassMax);
+}
 }  // namespace
 
 extern "C" long clc_rans_encode_bound(long n) { return 4 * (n * 12 + 18); }
@@ -134,15 +144,7 @@ extern "C" long clc_rans_encode(const int32_t* symbols, const int32_t* indexes, 
     bool escape = false;
     if (value < 0) { raw = (uint32_t)(-2 * (int64_t)value - 1); value = max_value; escape = true; }
     else if (value >= max_value) { raw = (uint32_t)(2 * ((int64_t)value - max_value)); value = max_value; escape = true; }
-    if (escape) {
-      // forward order is: symbol, count (unary in 15s), nibbles LSB first -> emit in reverse
-      int nb = 0;
-      while (nb < 8 && (raw >> (nb * kBypassBits)) != 0) ++nb;
-      for (int j = nb - 1; j >= 0; --j) enc_put_bits(x, o, (raw >> (j * kBypassBits)) & kBypassMax);
-      const int full = nb / (int)kBypassMax, rem = nb % (int)kBypassMax;
-      enc_put_bits(x, o, (uint32_t)rem);
-      for (int j = 0; j < full; ++j) enc_put_bits(x, o, kBypassMax);
-    }
+    if (escape) enc_put_escape(x, o, raw);
     const uint32_t start = (uint32_t)cdf[value] & 0xFFFFu;
     const uint32_t freq = (uint32_t)(cdf[value + 1] - cdf[value]) & 0xFFFFu;
     if (freq == 0) { clc_set_error("clc_rans_encode: zero-frequency symbol (index %d value %d)", ci, value); return -1; }
@@ -151,6 +153,34 @@ extern "C" long clc_rans_encode(const int32_t* symbols, const int32_t* indexes, 
   o.put((uint32_t)(x >> 32));
   o.put((uint32_t)x);
   if (o.overflow) { clc_set_error("clc_rans_encode: output buffer too small"); return -2; }
+  const long nbytes = (long)(end - o.ptr) * 4;
+  memmove(out, o.ptr, (size_t)nbytes);
+  return nbytes;
+}
+
+// The same stream from (start, freq, esc) triples, one per symbol, that the caller read from each symbol's own CDF row (gmm.hip computes
+// them on the device): esc < 0 for a symbol inside its row, else the escape payload `raw` of clc_rans_encode and (start, freq) those of
+// the row's tail symbol.
+extern "C" long clc_rans_encode_direct(const int32_t* triples, long n, uint8_t* out, long out_cap) {
+  if (n < 0 || (n > 0 && !triples) || !out) { clc_set_error("clc_rans_encode_direct: bad args"); return -1; }
+  if (out_cap < 8 || (reinterpret_cast<uintptr_t>(out) & 3)) { clc_set_error("clc_rans_encode_direct: output buffer too small or unaligned"); return -1; }
+  BackWriter o;
+  o.begin = reinterpret_cast<uint32_t*>(out);
+  o.ptr = o.begin + out_cap / 4;
+  uint32_t* const end = o.ptr;
+  uint64_t x = kL;
+  for (long i = n - 1; i >= 0; --i) {
+    const int32_t start = triples[3 * i], freq = triples[3 * i + 1], esc = triples[3 * i + 2];
+    if (start < 0 || freq <= 0 || freq > 0xFFFF || (int64_t)start + freq > (1 << kPrec)) {
+      clc_set_error("clc_rans_encode_direct: symbol %ld has start %d, freq %d (needs 0 <= start, 0 < freq < 2^16, start + freq <= 2^16)", i, start, freq);
+      return -1;
+    }
+    if (esc >= 0) enc_put_escape(x, o, (uint32_t)esc);
+    enc_put(x, o, (uint32_t)start, (uint32_t)freq);
+  }
+  o.put((uint32_t)(x >> 32));
+  o.put((uint32_t)x);
+  if (o.overflow) { clc_set_error("clc_rans_encode_direct: output buffer too small"); return -2; }
   const long nbytes = (long)(end - o.ptr) * 4;
   memmove(out, o.ptr, (size_t)nbytes);
   return nbytes;

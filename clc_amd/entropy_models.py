@@ -271,3 +271,45 @@ class GaussianConditional(EntropyModel):
     def quantize_and_index(self, y, means, scales):
         """symbols, indexes, y_hat = quantize(y,'symbols',means), build_indexes(scales), symbols+means — one kernel."""
         return ops.quantize_build_indexes(y, means, scales, self.scale_table)
+
+
+class GaussianMixtureConditional(nn.Module):
+    """The discretised K-component Gaussian mixture of Cheng et al. (CVPR 2020): every element has K weight logits, means and scales of
+    its own (``[B, K C, H, W]`` each, component k of channel c at channel k C + c),
+
+        likelihood = LowerBound(1e-9)(sum_k softmax_k(weights) [Phi((1/2 - |v - mu_k|) / s_k) - Phi((-1/2 - |v - mu_k|) / s_k)]),
+        s_k = LowerBound(0.11)(scales_k),  Phi(x) = erfc(-x / sqrt 2) / 2,
+
+    per component GaussianConditional's expression; v = inputs + U(-1/2, 1/2) in training, round(inputs) in eval — no mean enters the
+    quantiser.  On clc_gmm_likelihood_fwd / _bwd (csrc/gmm.hip).  There is no CDF table (the coder builds one integer row per symbol on
+    the device, ops.gmm_finish_*), so the module has no state_dict entries and update() returns False."""
+
+    def __init__(self, K, scale_bound=0.11, likelihood_bound=1e-9):
+        super().__init__()
+        if not 1 <= int(K) <= 4:
+            raise ValueError(f"GaussianMixtureConditional: K must be between 1 and 4 (got {K})")
+        if abs(float(scale_bound) - 0.11) > 1e-12 or abs(float(likelihood_bound) - 1e-9) > 1e-15:
+            raise ValueError("the HIP likelihood kernels are built for scale_bound = 0.11 and likelihood_bound = 1e-9")
+        self.K = int(K)
+
+    def update(self, *args, **kwargs):
+        return False
+
+    def _noise(self, inputs, training):
+        training = self.training if training is None else training
+        return training, (torch.empty_like(inputs, memory_format=ops.CL).uniform_(-0.5, 0.5) if training else None)
+
+    @staticmethod
+    def _outputs(inputs, noise):
+        return inputs + noise if noise is not None else torch.round(inputs.detach())
+
+    def forward(self, inputs, scales, means, weights, training=None):
+        training, noise = self._noise(inputs, training)
+        lik = ops.gmm_likelihood(inputs, scales, means, weights, noise, training, self.K)
+        return self._outputs(inputs, noise), lik
+
+    def forward_packed(self, inputs, params, training=None):
+        """forward with (scales | means | weights) as the channel thirds of one [B, 3 K C, H, W] map, read in place"""
+        training, noise = self._noise(inputs, training)
+        lik = ops.gmm_likelihood_packed(inputs, params, noise, training, self.K)
+        return self._outputs(inputs, noise), lik

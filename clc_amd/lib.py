@@ -16,6 +16,8 @@ IN_NONE, IN_SQUARE = 0, 1
 NORM_NONE, NORM_GDN, NORM_IGDN, NORM_MUL2 = 0, 1, 2, 3
 AR_SRC_DENSE, AR_SRC_PIXEL, AR_SRC_TAPS = 0, 1, 2
 AR_ENCODE, AR_DECODE = 0, 1
+GMM_R = 32                      # CLC_GMM_R (checked against clc_gmm_half_width() of the loaded library)
+GMM_ROW_STRIDE = 2 * GMM_R + 3  # entries of a per-symbol CDF row: L + 2 with L = 2 R + 1
 
 fp = C.c_void_p  # device / host pointers are passed as integers (tensor.data_ptr())
 
@@ -245,6 +247,7 @@ SIGNATURES = {
     "clc_scalar_add": (_i, [fp, _f, fp]),
     "clc_rans_encode_bound": (_l, [_l]),
     "clc_rans_encode": (_l, [fp, fp, _l, fp, _i, fp, fp, fp, _l]),
+    "clc_rans_encode_direct": (_l, [fp, _l, fp, _l]),
     "clc_rans_decoder_create": (fp, [fp, _l]),
     "clc_rans_decoder_decode": (_l, [fp, fp, _l, fp, _i, fp, fp, fp]),
     "clc_rans_decoder_destroy": (None, [fp]),
@@ -263,6 +266,11 @@ SIGNATURES = {
     "clc_ckbd_conv": (_i, [C.POINTER(CkbdDesc), fp]),
     "clc_ckbd_wgrad": (_i, [C.POINTER(CkbdWgradDesc), fp]),
     "clc_row_gemm": (_i, [C.POINTER(ArSrc), _i, fp, _i, _i, _i, _i, fp, fp, _i, _i, fp, _i, fp]),
+    "clc_gmm_half_width": (_i, []),
+    "clc_gmm_likelihood_fwd": (_i, [fp, _i, fp, _i, fp, fp, fp, _i, fp, _i, _l, _i, _i, _i, fp]),
+    "clc_gmm_likelihood_bwd": (_i, [fp, _i, fp, _i, fp, _i, fp, fp, fp, _i, fp, _i, fp, fp, fp, _i, _l, _i, _i, _i, fp]),
+    "clc_gmm_finish": (_i, [fp, _i, _i, _i, fp, _i, _i, _i, _i, fp, _i, fp, _i, fp, fp, fp, _i, fp]),
+    "clc_gmm_commit": (_i, [fp, _i, fp, _i, _i, _i, _i, fp, _i, fp]),
 }
 
 
@@ -293,6 +301,8 @@ def load():
         if L.clc_set_tuning(int(k), int(v)) < 0:
             msg = L.clc_last_error()
             raise ClcError(f"CLC_TUNING={item}: {msg.decode() if msg else 'rejected'}")
+    if L.clc_gmm_half_width() != GMM_R:
+        raise ClcError(f"{LIB_PATH} was built with CLC_GMM_R = {L.clc_gmm_half_width()}, this package expects {GMM_R}")
     _lib = L
     return L
 

@@ -1,0 +1,241 @@
+"""``cheng2020-anchor`` / ``cheng2020-attn`` — Cheng et al., "Learned Image Compression with Discretized Gaussian Mixture Likelihoods and
+Attention Modules" (CVPR 2020) on the engine's own kernels: the "Cheng" curve of the RD plot.
+
+Transforms: residual blocks with 3x3 convolutions, sub-pixel upsampling and (``-attn``) the simplified attention block — exactly the leaves
+CLC runs on the 3x3 kernels.  Entropy model: the ``mbt2018`` context model (masked 5x5 convolution + three 1x1 layers) predicting, per
+latent element, a K-component Gaussian mixture.
+
+The layer list is written from the published CompressAI classes (``Cheng2020Anchor`` / ``Cheng2020Attention``: module names, hence the
+``state_dict`` keys) and the paper; CompressAI is not a dependency and is not installed where this is built, so nothing here is pinned
+against it.  Like the other baselines the models are checked against a plain-torch restatement of the same definitions
+(tests/cheng_ref.py).  The ``K > 1`` parameter layout and stream are the project's own.
+
+K = 1 is the published single-Gaussian model: forward, compress and decompress are ``mbt2018``'s, stream, schedule and bits as
+JointAutoregressiveHierarchicalPriors defines them; only the four transforms differ.
+
+K > 1.  ``entropy_parameters`` ends in 3 K N channels, output channel part * K N + k N + c with part 0 the scales, 1 the means, 2 the
+weight logits; ``gaussian_conditional`` is a GaussianMixtureConditional (csrc/gmm.hip), which reads the three groups of that one map in
+place.  With a mixture there is no mean to subtract before rounding: y_hat = round(y) is known before the context model runs, so the
+ENCODER's autoregressive pass is one parallel step over all pixels; the DECODER follows the wavefront, W + 3 (H - 1) steps.
+
+STREAM ORDER (K > 1): one rANS stream per image for y — the pixels of ``ar_wavefront_order(H, W)`` (the steps of
+``ar_schedule(H, W, "wavefront")`` ascending, raster inside a step), channels inner; every symbol through its own integer CDF row (THE ROW
+RULE of include/clc_hip.h), built on the device by the same scan on both sides; z as in the other hyperprior models.  The four-layer
+chain runs on clc_ar_linear on both sides (its summation order depends on K alone), h_s on the batch-invariant 3x3 routes the CLC codec
+relies on: a stream written at batch 8 decodes at batch 1.
+
+TrainEngine, graphed_training, CodecEngine and ReferenceBank do not take these models.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+from .. import ans, ops
+from ..entropy_models import GaussianMixtureConditional
+from ..layers import (AttentionBlock, Conv2d, ResidualBlock, ResidualBlockUpsample, ResidualBlockWithStride, conv3x3, subpel_conv3x3)
+from ..ops import ACT_LRELU, CL
+from .clc import _resize_registered_buffers
+from .hyperprior import JointAutoregressiveHierarchicalPriors, ar_schedule
+
+_SYM_BOUND = float(1 << 24)
+_CHUNK_ROWS = 8192   # rows of the chain's workspace in the encoder's one parallel step (the order rule makes the chunking invisible)
+
+
+def ar_wavefront_order(H, W):
+    """The pixels of an H x W latent in the order of the K > 1 stream: the steps of ar_schedule(H, W, "wavefront") ascending, raster inside
+    a step.  -> list of (h, w)"""
+    return [p for s in ar_schedule(H, W, "wavefront") for p in s]
+
+
+def _run_lrelu(seq, x):
+    """a Sequential whose LeakyReLU placeholders are fused into the producing layer's epilogue"""
+    mods = list(seq)
+    i = 0
+    while i < len(mods):
+        if i + 1 < len(mods) and isinstance(mods[i + 1], nn.LeakyReLU):
+            x = mods[i](x, act=ACT_LRELU)
+            i += 2
+        else:
+            x = mods[i](x)
+            i += 1
+    return x
+
+
+class Cheng2020Anchor(JointAutoregressiveHierarchicalPriors):
+    """cheng2020-anchor (no attention), M = N; K mixture components (K = 1: the published single-Gaussian model).  See the module
+    docstring for the layer list's source, the K > 1 layout and the stream."""
+
+    def __init__(self, N=192, K=1, **kwargs):
+        name = type(self).__name__
+        if N == 128:
+            raise ValueError(f"{name}: N = 128: cheng2020 qualities 1–3 are not built (N % 12 != 0: 10N/3 and 8N/3 must be whole multiples of 4)")
+        if N % 12:
+            raise ValueError(f"{name} needs N % 12 == 0 (then 10N/3, 8N/3 and 3N/2 are whole and multiples of 4, the kernels' aligned "
+                             f"path); got N = {N}")
+        if not 1 <= int(K) <= 4:
+            raise ValueError(f"{name}: K must be between 1 and 4 mixture components (got K = {K})")
+        super().__init__(N=N, M=N, **kwargs)
+        self.K = int(K)
+        self.g_a, self.g_s = self._build_transforms(N)
+        lrelu = lambda: nn.LeakyReLU(inplace=True)
+        self.h_a = nn.Sequential(conv3x3(N, N), lrelu(), conv3x3(N, N), lrelu(), conv3x3(N, N, stride=2), lrelu(), conv3x3(N, N), lrelu(),
+                                 conv3x3(N, N, stride=2))
+        self.h_s = nn.Sequential(conv3x3(N, N), lrelu(), subpel_conv3x3(N, N, 2), lrelu(), conv3x3(N, N * 3 // 2), lrelu(),
+                                 subpel_conv3x3(N * 3 // 2, N * 3 // 2, 2), lrelu(), conv3x3(N * 3 // 2, N * 2))
+        if self.K > 1:
+            self.entropy_parameters[4] = Conv2d(N * 8 // 3, 3 * self.K * N, 1)
+            self.gaussian_conditional = GaussianMixtureConditional(self.K)
+
+    @staticmethod
+    def _build_transforms(N):
+        RBWS, RBU, RB = ResidualBlockWithStride, ResidualBlockUpsample, ResidualBlock
+        g_a = nn.Sequential(RBWS(3, N, 2), RB(N, N), RBWS(N, N, 2), RB(N, N), RBWS(N, N, 2), RB(N, N), conv3x3(N, N, stride=2))
+        g_s = nn.Sequential(RB(N, N), RBU(N, N, 2), RB(N, N), RBU(N, N, 2), RB(N, N), RBU(N, N, 2), RB(N, N), subpel_conv3x3(N, 3, 2))
+        return g_a, g_s
+
+    def _hyper_analysis(self, y):
+        return _run_lrelu(self.h_a, y)
+
+    def _hyper_synthesis(self, z_hat):
+        return _run_lrelu(self.h_s, z_hat)
+
+    # ---- K > 1: the mixture ----
+    def forward(self, x):
+        if self.K == 1:
+            return super().forward(x)
+        x = self._prep(x)
+        y = self._analysis(x)
+        z = self._hyper_analysis(y)
+        z_hat, z_likelihoods = self.entropy_bottleneck(z)
+        params = self._hyper_synthesis(z_hat)
+        if self.training:
+            y_hat = y + torch.empty_like(y, memory_format=CL).uniform_(-0.5, 0.5)
+        else:
+            y_hat = torch.round(y.detach())
+        ctx_params = self.context_prediction(y_hat)
+        mixture = self._entropy_parameters(torch.cat((params, ctx_params), 1))   # [B, 3 K N, H, W]: read in place, no chunk copies
+        _, y_likelihoods = self.gaussian_conditional.forward_packed(y, mixture)
+        x_hat = self._synthesis(y_hat)
+        return {"x_hat": x_hat, "likelihoods": {"y": y_likelihoods, "z": z_likelihoods}}
+
+    def update(self, scale_table=None, force=False):
+        if self.K == 1:
+            return super().update(scale_table, force=force)
+        return self.entropy_bottleneck.update(force=force)   # the mixture has no table
+
+    def load_state_dict(self, state_dict, strict=True):
+        if self.K == 1:
+            return super().load_state_dict(state_dict, strict=strict)
+        _resize_registered_buffers(self.entropy_bottleneck, "entropy_bottleneck", ["_quantized_cdf", "_offset", "_cdf_length"], state_dict)
+        return nn.Module.load_state_dict(self, state_dict, strict=strict)
+
+    def _gmm_workspace(self, rows, dev):
+        N, K = self.N, self.K
+        mk = lambda c: torch.empty((rows, c), device=dev, dtype=torch.float32)
+        return {"ctx": mk(2 * N), "h1": mk(N * 10 // 3), "h2": mk(N * 8 // 3), "gp": mk(3 * K * N)}
+
+    @torch.no_grad()
+    def _gmm_encode(self, y, params):
+        """The encoder's one parallel step -> (triples int32 [B, H*W, N, 3] in ar_wavefront_order, y_hat = round(y)): all launches on the
+        current stream, no host sync."""
+        ops._require_gpu(y, "cheng2020 compress")
+        B, N, H, W = y.shape
+        y = y.contiguous(memory_format=CL)
+        params = params.contiguous(memory_format=CL)
+        # known before the context model runs: no mean enters the quantiser.  (The symbol range of THE ROW RULE: +-2^24, NaN at the bottom.)
+        y_hat = torch.round(y).nan_to_num_(nan=-_SYM_BOUND, posinf=_SYM_BOUND, neginf=-_SYM_BOUND).clamp_(-_SYM_BOUND, _SYM_BOUND)
+        pix = torch.tensor(ar_wavefront_order(H, W), dtype=torch.int32).reshape(-1, 2).to(y.device)
+        chunk = max(1, _CHUNK_ROWS // B)
+        ws = self._gmm_workspace(B * min(chunk, H * W), y.device)
+        filt = self._ar_filters()
+        parts = []
+        for lo in range(0, H * W, chunk):
+            px = pix[lo:lo + chunk]
+            self._ar_chain(px, B, H, W, y_hat, params, ws, filt)
+            t = torch.empty((B, px.shape[0], N, 3), device=y.device, dtype=torch.int32)
+            ops.gmm_finish_encode(ws["gp"], N, self.K, px, y, y_hat, t)   # (rewrites y_hat[pixel] with the value it already holds)
+            parts.append(t)
+        return (parts[0] if len(parts) == 1 else torch.cat(parts, 1)), y_hat
+
+    @torch.no_grad()
+    def compress(self, x, order="wavefront"):
+        if self.K == 1:
+            return super().compress(x, order)
+        y, params, z_strings, z_size = self._code_inputs(x)
+        triples, _ = self._gmm_encode(y, params)
+        t = triples.cpu().numpy()   # the one device -> host copy
+        y_strings = [ans.encode_direct(t[i]) for i in range(t.shape[0])]
+        from ..codec import kernel_config
+
+        return {"strings": [y_strings, z_strings], "shape": z_size, "kernel_config": kernel_config()}
+
+    @torch.no_grad()
+    def _gmm_decode(self, y_strings, params):
+        """The wavefront pass of decompress -> y_hat: per non-empty step, for the whole batch, one row download, one incremental decode
+        per image on a decoder opened once, one symbol upload."""
+        params = params.contiguous(memory_format=CL)
+        dev = params.device
+        B, N, K, (H, W) = params.shape[0], self.N, self.K, params.shape[2:]
+        if len(y_strings) != B:
+            raise ValueError(f"decompress: {len(y_strings)} y streams for {B} z streams")
+        steps, pix = self._ar_pixels(ar_schedule(H, W, "wavefront"), dev)
+        rows = B * max(len(s) for s in steps)
+        ws = self._gmm_workspace(rows, dev)
+        filt = self._ar_filters()
+        y_hat = torch.zeros((B, N, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
+        decoders = []
+        for s in y_strings:
+            d = ans.RansDecoder()
+            d.set_stream(s)
+            decoders.append(d)
+        S = ops.GMM_ROW_STRIDE
+        # one pinned buffer per hop: the rows and, behind them, the offsets
+        down_dev = torch.empty((rows * N * (S + 1),), device=dev, dtype=torch.int32)
+        down_host = torch.empty((rows * N * (S + 1),), dtype=torch.int32).pin_memory()
+        sym_dev = torch.empty((rows, N), device=dev, dtype=torch.int32)
+        sym_host = torch.empty((rows, N), dtype=torch.int32).pin_memory()
+        down_np, sym_np = down_host.numpy(), sym_host.numpy()
+        stream = torch.cuda.current_stream(dev)
+        off = 0
+        for s in steps:
+            cnt = len(s)
+            n = B * cnt
+            px = pix[off:off + cnt]
+            off += cnt
+            self._ar_chain(px, B, H, W, y_hat, params, ws, filt)
+            rows_dev = down_dev[:n * N * S].view(n, N, S)
+            offs_dev = down_dev[n * N * S:n * N * (S + 1)].view(n, N)
+            ops.gmm_finish_decode(ws["gp"], N, K, px, B, H, W, rows_dev, offs_dev)
+            down_host[:n * N * (S + 1)].copy_(down_dev[:n * N * (S + 1)], non_blocking=True)
+            stream.synchronize()   # (also: the previous step's symbol upload has left sym_host)
+            rows_np = down_np[:n * N * S].reshape(n * N, S)
+            offs_np = down_np[n * N * S:n * N * (S + 1)]
+            e = cnt * N   # image b's elements of the step: rows b * cnt .. in list order, channels inner
+            for b, d in enumerate(decoders):
+                sym_np[b * cnt:(b + 1) * cnt] = d.decode_rows(rows_np[b * e:(b + 1) * e], offs_np[b * e:(b + 1) * e]).reshape(cnt, N)
+            sym_dev[:n].copy_(sym_host[:n], non_blocking=True)
+            ops.gmm_commit(sym_dev[:n], N, px, y_hat)
+        return y_hat
+
+    @torch.no_grad()
+    def decompress(self, strings, shape):
+        if self.K == 1:
+            return super().decompress(strings, shape)
+        assert isinstance(strings, (list, tuple)) and len(strings) == 2
+        z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
+        y_hat = self._gmm_decode(strings[0], self._hyper_synthesis(z_hat))
+        return {"x_hat": self._synthesis(y_hat).clamp_(0, 1)}
+
+
+class Cheng2020Attention(Cheng2020Anchor):
+    """cheng2020-attn: the anchor model with the simplified attention block after the second strided block and at the end of g_a, and
+    first and after the second upsampling block of g_s."""
+
+    @staticmethod
+    def _build_transforms(N):
+        RBWS, RBU, RB, AB = ResidualBlockWithStride, ResidualBlockUpsample, ResidualBlock, AttentionBlock
+        g_a = nn.Sequential(RBWS(3, N, 2), RB(N, N), RBWS(N, N, 2), AB(N), RB(N, N), RBWS(N, N, 2), RB(N, N), conv3x3(N, N, stride=2), AB(N))
+        g_s = nn.Sequential(AB(N), RB(N, N), RBU(N, N, 2), RB(N, N), RBU(N, N, 2), AB(N), RB(N, N), RBU(N, N, 2), RB(N, N),
+                            subpel_conv3x3(N, 3, 2))
+        return g_a, g_s

@@ -2831,3 +2831,131 @@ def ckbd_conv(x, w, b=None, act=ACT_NONE):
     _require_gpu(x, "ckbd_conv")
     _note_grad_mode()
     return _CkbdConvFn.apply(x, w, b, act)
+
+
+# ------------------------------------------------------------------- Gaussian-mixture entropy model (csrc/gmm.hip)
+GMM_R, GMM_ROW_STRIDE = _lib.GMM_R, _lib.GMM_ROW_STRIDE
+
+
+def _gmm_groups(groups, N, H, W, Cc, K, what):
+    """(pointers, the one leading dimension) of three [B, K C, H, W] parameter groups: channel ranges of one map, or three maps of one
+    leading dimension, read in place; anything else is copied into one map first."""
+    for t in groups:
+        _require_gpu(t, what)
+        if tuple(t.shape) != (N, K * Cc, H, W):
+            raise ValueError(f"{what}: every parameter group must be [B, K C, H, W] = {(N, K * Cc, H, W)} (got {tuple(t.shape)})")
+    got = [nhwc(t) for t in groups]
+    if any(g[0] is not t for g, t in zip(got, groups)) or len({g[6] for g in got}) != 1:
+        one = torch.cat(list(groups), 1).contiguous(memory_format=CL)
+        got = [nhwc(one[:, i * K * Cc:(i + 1) * K * Cc]) for i in range(3)]
+    return [g[0] for g in got], [g[1] for g in got], got[0][6]
+
+
+class _GmmLikFn(Function):
+    """The mixture likelihood of clc_gmm_likelihood_fwd / _bwd.  packed: the three groups are the channel thirds of ONE map (the output
+    of entropy_parameters), whose gradient comes back as one map; else three tensors."""
+
+    @staticmethod
+    def forward(ctx, y, noise, training, K, packed, *params):
+        _require_gpu(y, "gmm_likelihood")
+        y, yp, N, H, W, Cc, ldy = nhwc(y)
+        if packed:
+            (gp,) = params
+            if gp.dim() != 4 or gp.shape[1] != 3 * K * Cc:
+                raise ValueError(f"gmm_likelihood: the parameter map must have 3 K C = {3 * K * Cc} channels (got {tuple(gp.shape)})")
+            gp = nhwc(gp)[0]
+            groups = [gp[:, i * K * Cc:(i + 1) * K * Cc] for i in range(3)]
+        else:
+            groups = list(params)
+        keep, ptrs, ldp = _gmm_groups(groups, N, H, W, Cc, K, "gmm_likelihood")
+        npn, ldn = None, 0
+        if training:
+            _require_gpu(noise, "gmm_likelihood")
+            noise, npn, *_c, ldn = nhwc(noise)
+        lik = new_act(N, Cc, H, W, y)
+        _lib.check(_L().clc_gmm_likelihood_fwd(yp, ldy, npn, ldn, ptrs[0], ptrs[1], ptrs[2], ldp, lik.data_ptr(), Cc, N * H * W, Cc, K,
+                                               0 if training else 1, _stream()), "clc_gmm_likelihood_fwd")
+        ctx.cfg = (training, K, packed)
+        ctx.save_for_backward(y, noise if training else None, *keep)
+        return lik
+
+    @staticmethod
+    def backward(ctx, dlik):
+        training, K, packed = ctx.cfg
+        y, noise, *groups = ctx.saved_tensors
+        y, yp, N, H, W, Cc, ldy = nhwc(y)
+        got = [nhwc(t) for t in groups]
+        ldp = got[0][6]
+        dlik, dlp, *_c, lddl = nhwc(dlik)
+        npn, ldn = None, 0
+        if training:
+            noise, npn, *_d, ldn = nhwc(noise)
+        dy = new_act(N, Cc, H, W, y) if training else None
+        dgp = new_act(N, 3 * K * Cc, H, W, y)   # the three gradient groups are channel ranges of one map
+        base, step = dgp.data_ptr(), 4 * K * Cc
+        _lib.check(_L().clc_gmm_likelihood_bwd(dlp, lddl, yp, ldy, npn, ldn, got[0][1], got[1][1], got[2][1], ldp,
+                                               dy.data_ptr() if dy is not None else None, Cc, base, base + step, base + 2 * step, 3 * K * Cc,
+                                               N * H * W, Cc, K, 0 if training else 1, _stream()), "clc_gmm_likelihood_bwd")
+        if packed:
+            return dy, None, None, None, None, dgp
+        return (dy, None, None, None, None) + tuple(dgp[:, i * K * Cc:(i + 1) * K * Cc] for i in range(3))
+
+
+def gmm_likelihood(y, scales, means, weights, noise, training, K):
+    """-> likelihood [B, C, H, W] of v = y + noise (training) or round(y) (eval) under the per-element K-component Gaussian mixture;
+    scales / means / weights: [B, K C, H, W], component k of channel c at channel k C + c.  Both LowerBounds (0.11 on the scales, 1e-9
+    on the likelihood) with their gradient rules are inside."""
+    return _GmmLikFn.apply(y, noise, bool(training), int(K), False, scales, means, weights)
+
+
+def gmm_likelihood_packed(y, params, noise, training, K):
+    """gmm_likelihood with the three groups as the channel thirds (scales | means | weight logits) of one [B, 3 K C, H, W] map, read in
+    place; the map's gradient is written as one map."""
+    return _GmmLikFn.apply(y, noise, bool(training), int(K), True, params)
+
+
+def _gmm_gp(gp, rows, N, K, what):
+    gpp, ldg = _ar_dense(gp, rows, f"{what} gp")
+    if gp.shape[1] < 3 * K * N:
+        raise ValueError(f"{what}: gp has {gp.shape[1]} columns, needs 3 K N = {3 * K * N}")
+    return gpp, ldg
+
+
+def gmm_finish_encode(gp, N, K, pix, y, y_hat, triples):
+    """clc_gmm_finish, encode mode: gp [rows, >= 3 K N] -> y_hat[pixel] = round(y[pixel]) in place and the (start, freq, esc) triples of
+    clc_rans_encode_direct, int32 [B, P, N, 3] in list order."""
+    pp, P = _ar_pix(pix)
+    yp, B, H, W, Cy, ldy = _ar_map(y, "gmm_finish")
+    hp, Bh, Hh, Wh, Ch, ldh = _ar_map(y_hat, "gmm_finish")
+    if (Bh, Hh, Wh, Ch) != (B, H, W, Cy) or Cy != N:
+        raise ValueError(f"gmm_finish: y {tuple(y.shape)} and y_hat {tuple(y_hat.shape)} must be [B, N = {N}, H, W] maps of one shape")
+    gpp, ldg = _gmm_gp(gp, B * P, N, K, "gmm_finish")
+    if triples.dtype != torch.int32 or not triples.is_cuda or not triples.is_contiguous() or tuple(triples.shape) != (B, P, N, 3):
+        raise ValueError(f"gmm_finish: triples must be a contiguous int32 [B, P, N, 3] = {(B, P, N, 3)} device tensor")
+    _lib.check(_L().clc_gmm_finish(gpp, ldg, N, K, pp, P, B, H, W, yp, ldy, hp, ldh, triples.data_ptr(), None, None, _lib.AR_ENCODE, _stream()),
+               "clc_gmm_finish")
+
+
+def gmm_finish_decode(gp, N, K, pix, B, H, W, cdf_rows, offsets):
+    """clc_gmm_finish, decode mode: the per-symbol CDF rows int32 [rows, N, GMM_ROW_STRIDE] and their offsets int32 [rows, N]."""
+    pp, P = _ar_pix(pix)
+    rows = B * P
+    gpp, ldg = _gmm_gp(gp, rows, N, K, "gmm_finish")
+    if (cdf_rows.dtype != torch.int32 or not cdf_rows.is_cuda or not cdf_rows.is_contiguous() or cdf_rows.dim() != 3 or cdf_rows.shape[0] < rows
+            or tuple(cdf_rows.shape[1:]) != (N, GMM_ROW_STRIDE)):
+        raise ValueError(f"gmm_finish: cdf_rows must be a contiguous int32 [>= {rows}, N = {N}, {GMM_ROW_STRIDE}] device tensor (got {tuple(cdf_rows.shape)})")
+    op, ldo = _ar_dense(offsets, rows, "gmm_finish offsets", torch.int32)
+    if ldo != N or offsets.shape[1] != N:
+        raise ValueError(f"gmm_finish: offsets must be a dense int32 [rows, N = {N}] buffer")
+    _lib.check(_L().clc_gmm_finish(gpp, ldg, N, K, pp, P, B, H, W, None, 0, None, 0, None, cdf_rows.data_ptr(), op, _lib.AR_DECODE, _stream()),
+               "clc_gmm_finish")
+
+
+def gmm_commit(symbols, N, pix, y_hat):
+    """clc_gmm_commit: y_hat[pixel] = (float)symbols[r] from decoded symbols (dense int32 [rows, N])."""
+    pp, P = _ar_pix(pix)
+    hp, B, H, W, Ch, ldh = _ar_map(y_hat, "gmm_commit")
+    sp, lds = _ar_dense(symbols, B * P, "gmm_commit symbols", torch.int32)
+    if lds != N or symbols.shape[1] != N or Ch != N:
+        raise ValueError(f"gmm_commit: symbols must be a dense [rows, N = {N}] buffer and y_hat have N channels")
+    _lib.check(_L().clc_gmm_commit(sp, N, pp, P, B, H, W, hp, ldh, _stream()), "clc_gmm_commit")

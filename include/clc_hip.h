@@ -521,6 +521,12 @@ int clc_scalar_add(float* x_dev, float v, clc_stream_t stream);
 long clc_rans_encode_bound(long n_symbols);
 long clc_rans_encode(const int32_t* symbols, const int32_t* indexes, long n, const int32_t* cdfs, int cdf_stride,
                      const int32_t* cdf_sizes, const int32_t* offsets, uint8_t* out, long out_cap); /* HOST */
+/* The same stream from per-symbol (start, freq, esc) int32 triples (n of them, 3 n values) that the caller read from each symbol's own CDF
+ * row: esc < 0 for a symbol inside its row, start = cdf[v], freq = cdf[v + 1] - cdf[v]; else esc is the escape payload `raw` of
+ * clc_rans_encode (below the row's window -2 v - 1, at or above max_value 2 (v - max_value)) and (start, freq) are those of the row's
+ * tail symbol.  The bytes equal clc_rans_encode's for the same symbols coded through their full rows.  Needs 0 <= start, 0 < freq < 2^16,
+ * start + freq <= 2^16; anything else is refused by name.  out_cap as for clc_rans_encode (clc_rans_encode_bound). */
+long clc_rans_encode_direct(const int32_t* triples, long n, uint8_t* out, long out_cap);           /* HOST */
 typedef struct clc_rans_decoder clc_rans_decoder;
 clc_rans_decoder* clc_rans_decoder_create(const uint8_t* stream, long nbytes);                    /* HOST, copies */
 long clc_rans_decoder_decode(clc_rans_decoder* d, const int32_t* indexes, long n, const int32_t* cdfs, int cdf_stride,
@@ -776,6 +782,51 @@ int clc_ckbd_wgrad(const clc_ckbd_wgrad_desc* d, clc_stream_t stream);
  * another. */
 int clc_row_gemm(const clc_ar_src* srcs /* HOST */, int nsrc, const int32_t* pix, int P, int B, int H, int W, const float* w, const float* bias,
                  int N, int act, float* out, int ldo, clc_stream_t stream);
+
+/* ---- the Gaussian-mixture entropy model of cheng2020 (Cheng et al., CVPR 2020; models.Cheng2020Anchor / Cheng2020Attention, K > 1; gmm.hip) ----
+ * Every latent element has K weight logits, means and scales of its own, so the 64-row scale table of the other coders does not apply.
+ *
+ * Parameter groups.  scales, means and weights are three base pointers with ONE leading dimension ldp; a group is K blocks of C channels,
+ * component k of channel c at [row * ldp + k * C + c] — channel ranges of the one map entropy_parameters writes are read in place.
+ *
+ * clc_gmm_likelihood_fwd   lik = max(sum_k softmax_k(weights) [Phi((1/2 - |v - mu_k|) / s_k) - Phi((-1/2 - |v - mu_k|) / s_k)], 1e-9) with
+ *                          s_k = max(scale_k, 0.11), Phi(x) = erfc(-x / sqrt 2) / 2, v = y + noise (mode 0) or round(y) (mode 1).
+ * clc_gmm_likelihood_bwd   from dlik: dy (mode 0 only; pass NULL in mode 1, where v does not depend on y), and dscales / dmeans / dweights
+ *                          as three base pointers with one leading dimension lddp, laid out like the parameters.  Both LowerBounds
+ *                          pass the gradient where the input is at or above the bound or the gradient is negative.
+ * NHWC f32 [rows][ld] maps, one pass.  Any C >= 1, K in 1 .. 4; 16-byte accesses when C % 4 == 0 and every base and leading dimension is
+ * 16-byte aligned, scalar ones otherwise.
+ *
+ * THE ROW RULE of the coder — per element (row r, channel c), from the 3 K parameters gp[r][part * K * N + k * N + c] (part 0 scales,
+ * 1 means, 2 weight logits), everything in f32:
+ *   pi = softmax(logits) (max subtracted), s_k = max(scale_k, 0.11), ctr = round(sum_k pi_k mu_k) clamped to [-2^20, 2^20] (NaN: -2^20);
+ *   R = CLC_GMM_R, L = 2 R + 1 regular symbols j = 0 .. L - 1 for the values offset + j, offset = ctr - R, and one tail symbol j = L
+ *   that carries everything outside through the bypass escape: a GaussianConditional table row with size = L + 2, max_value = L;
+ *   F_j = sum_k pi_k Phi((offset + j - 1/2 - mu_k) / s_k) for j = 0 .. L, summed k ascending, then sent into [0, 1] by comparisons that
+ *   put a NaN at 0;  G_0 = F_0, G_j = max(G_{j-1}, F_j);
+ *   cdf[j] = j + floor((G_j - G_0) * S), S = 65535 - L, for j = 0 .. L;  cdf[L + 1] = 65536.
+ * So every regular frequency is >= 1, the tail's is >= 1 and the total is 2^16, for ANY float parameters (NaN and +-Inf included).
+ * The symbol is round(y) clamped to [-2^24, 2^24] (NaN: -2^24).
+ *
+ * clc_gmm_finish   rows r = b * P + p over a pixel list like clc_ar_finish; gp a dense [rows][ldg] buffer, ldg >= 3 K N.
+ *                    CLC_AR_ENCODE  sym = round(y[pixel]); y_hat[pixel] = (float)sym; triples[(r * N + c) * 3 ..] = (start, freq, esc) for
+ *                                   clc_rans_encode_direct (a pixel outside the map is neither read nor written).
+ *                    CLC_AR_DECODE  cdf_rows[(r * N + c) * CLC_GMM_ROW_STRIDE ..] = the row, offsets[r * N + c] = offset.
+ *                  Both modes run the same scan, so an encoder's (start, freq) are the decoder's row entries bit for bit.
+ * clc_gmm_commit   y_hat[pixel][c] = (float)symbols[r * N + c] from decoded symbols (dense [rows][N] int32).
+ * All stream-ordered, graph-capturable, allocation- and sync-free; no workspace; no workgroup waits on another.  Bad arguments are
+ * refused by name before any launch. */
+#define CLC_GMM_R 32
+#define CLC_GMM_ROW_STRIDE (2 * CLC_GMM_R + 3)
+int clc_gmm_half_width(void);   /* CLC_GMM_R of the built library */
+int clc_gmm_likelihood_fwd(const float* y, int ldy, const float* noise, int ldn, const float* scales, const float* means, const float* weights,
+                           int ldp, float* lik, int ldl, long rows, int C, int K, int mode, clc_stream_t stream);
+int clc_gmm_likelihood_bwd(const float* dlik, int lddl, const float* y, int ldy, const float* noise, int ldn, const float* scales,
+                           const float* means, const float* weights, int ldp, float* dy, int lddy, float* dscales, float* dmeans,
+                           float* dweights, int lddp, long rows, int C, int K, int mode, clc_stream_t stream);
+int clc_gmm_finish(const float* gp, int ldg, int N, int K, const int32_t* pix, int P, int B, int H, int W, const float* y, int ldy, float* y_hat,
+                   int ldh, int32_t* triples, int32_t* cdf_rows, int32_t* offsets, int mode, clc_stream_t stream);
+int clc_gmm_commit(const int32_t* symbols, int N, const int32_t* pix, int P, int B, int H, int W, float* y_hat, int ldh, clc_stream_t stream);
 
 #ifdef __cplusplus
 }
