@@ -62,6 +62,58 @@ def encode_direct(triples) -> bytes:
     return buf[:nb].tobytes()
 
 
+SPLIT_MAGIC = b"CGS1"
+SPLIT_MAX = 64   # sub-streams per image: one wave each on the device decoder (clc_gmm_decode_step)
+
+
+def _split_length_ok(n):
+    return n >= 8 and n % 4 == 0
+
+
+def split_pack(streams) -> bytes:
+    """S independent rANS sub-streams of one image as one string, little endian:
+
+        b"CGS1" | u8 S | 3 x u8 0 | S x u32 byte length | the S sub-streams, back to back
+
+    Every sub-stream is a whole stream of ``encode_direct`` (32-bit words, at least the two of its final state).  Overhead: 8 + 4 S
+    bytes of header plus the 8-byte final state of each sub-stream, 8 + 12 S bytes — 200 per image at S = 16 (the one stream it
+    replaces carried one such state)."""
+    streams = [bytes(s) for s in streams]
+    S = len(streams)
+    if not 1 <= S <= SPLIT_MAX:
+        raise ValueError(f"split_pack: S must be between 1 and {SPLIT_MAX} sub-streams (got {S})")
+    for i, s in enumerate(streams):
+        if not _split_length_ok(len(s)):
+            raise ValueError(f"split_pack: sub-stream {i} has {len(s)} bytes; a length must be a multiple of 4 and at least 8")
+    head = SPLIT_MAGIC + bytes([S, 0, 0, 0]) + np.array([len(s) for s in streams], dtype="<u4").tobytes()
+    return head + b"".join(streams)
+
+
+def split_unpack(blob) -> list:
+    """-> the S sub-streams of a ``split_pack`` string; anything malformed is refused by name."""
+    blob = bytes(blob)
+    if len(blob) < 8 or blob[:4] != SPLIT_MAGIC:
+        raise ValueError(f"split_unpack: bad magic {blob[:4]!r} (a split stream starts with {SPLIT_MAGIC!r})")
+    S = blob[4]
+    if not 1 <= S <= SPLIT_MAX:
+        raise ValueError(f"split_unpack: S must be between 1 and {SPLIT_MAX} sub-streams (got {S})")
+    if blob[5:8] != b"\0\0\0":
+        raise ValueError(f"split_unpack: non-zero pad byte in the header ({blob[5:8].hex()})")
+    if len(blob) < 8 + 4 * S:
+        raise ValueError(f"split_unpack: the lengths do not add up to the blob ({len(blob)} bytes end inside the header of S = {S})")
+    lengths = [int(n) for n in np.frombuffer(blob, dtype="<u4", count=S, offset=8)]
+    for i, n in enumerate(lengths):
+        if not _split_length_ok(n):
+            raise ValueError(f"split_unpack: sub-stream {i} has length {n}; a length must be a multiple of 4 and at least 8")
+    if 8 + 4 * S + sum(lengths) != len(blob):
+        raise ValueError(f"split_unpack: the lengths do not add up to the blob (header {8 + 4 * S} + {sum(lengths)} != {len(blob)} bytes)")
+    out, at = [], 8 + 4 * S
+    for n in lengths:
+        out.append(blob[at:at + n])
+        at += n
+    return out
+
+
 _ROW_INDEX = {}   # n -> (arange(n), full(n, size)) int32: the index / size arrays of a decode over per-symbol rows
 
 

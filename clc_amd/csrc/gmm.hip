@@ -166,6 +166,25 @@ __device__ __forceinline__ float clamp_fixed(float v, float bound) {   // NaN ->
   return (v <= bound) ? v : bound;
 }
 
+// The parameters of one element's row, from its 3 K floats at g (stride N between a group's blocks): the mixture and -> offset = ctr - R.
+// The encoder's scan and the device decoder both call this, so their rows start from the same bits.
+template <int K>
+__device__ __forceinline__ int gmm_row_params(const float* g, int N, float (&pi)[K], float (&mu)[K], float (&sg)[K]) {
+  float lg[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    sg[k] = fmaxf(g[k * N], kScaleBound);
+    mu[k] = g[(K + k) * N];
+    lg[k] = g[(2 * K + k) * N];
+  }
+  softmax<K>(lg, pi);
+  float m = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) m += pi[k] * mu[k];
+  const int ctr = (int)clamp_fixed(rintf(m), kCtrBound);
+  return ctr - kR;
+}
+
 struct GmmFinArgs {
   const float* gp; int ldg;
   int N;
@@ -186,19 +205,8 @@ __global__ __launch_bounds__(256) void gmm_finish_kernel(const GmmFinArgs a) {
     const long r = i / a.N;
     const int c = (int)(i - r * a.N);
     const float* g = a.gp + r * a.ldg + c;
-    float lg[K], pi[K], mu[K], sg[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      sg[k] = fmaxf(g[k * a.N], kScaleBound);
-      mu[k] = g[(K + k) * a.N];
-      lg[k] = g[(2 * K + k) * a.N];
-    }
-    softmax<K>(lg, pi);
-    float m = 0.f;
-#pragma unroll
-    for (int k = 0; k < K; ++k) m += pi[k] * mu[k];
-    const int ctr = (int)clamp_fixed(rintf(m), kCtrBound);
-    const int offset = ctr - kR;
+    float pi[K], mu[K], sg[K];
+    const int offset = gmm_row_params<K>(g, a.N, pi, mu, sg);
     int value = 0;   // encode: the symbol's place in the row; < 0 or >= kL: escaped
     if (a.mode == CLC_AR_ENCODE) {
       const int b = (int)(r / a.P), p = (int)(r - (long)b * a.P);
@@ -256,6 +264,112 @@ __global__ __launch_bounds__(256) void gmm_commit_kernel(const int32_t* __restri
     const int h = pix[2 * p], w = pix[2 * p + 1];
     if (h < 0 || h >= H || w < 0 || w >= W) continue;
     y_hat[(((long)b * H + h) * W + w) * ldh + c] = (float)symbols[i];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------- the split stream's device decoder
+// One wave per (image, sub-stream): the rANS state and every branch are wave-uniform, the 64 lanes share the work of ONE symbol's row
+// (lane l owns edge j = l; the edges 64 and 65 are evaluated beside them and kept by every lane), and the symbol is found by a ballot.
+// No row is written anywhere, nothing is read back by the host: see include/clc_hip.h (clc_gmm_decode_step) for the procedure.
+struct GmmDecArgs {
+  const float* gp; int ldg;
+  int N;
+  const int32_t* pix; int P, B, H, W;
+  const uint32_t* words;
+  const int32_t* spans;
+  uint32_t* state;   // per (b, s): x low, x high, pos, pad
+  int S;
+  float* y_hat; int ldh;
+};
+
+struct SubStream {
+  const uint32_t* w;   // the sub-stream's first word
+  uint32_t count, pos;
+  uint64_t x;
+  __device__ __forceinline__ void renorm() {   // rans_host.cpp: one word when x < 2^31, zeros at or past the end
+    if (x < (1ull << 31)) {
+      const uint32_t v = pos < count ? w[pos] : 0u;
+      ++pos;
+      x = (x << 32) | v;
+    }
+  }
+  __device__ __forceinline__ uint32_t get_bits() {
+    const uint32_t v = (uint32_t)x & 15u;
+    x >>= 4;
+    renorm();
+    return v;
+  }
+};
+
+template <int K>
+__global__ __launch_bounds__(256) void gmm_decode_kernel(const GmmDecArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);   // (b, s); the last workgroup's spare waves leave
+  if (wid >= a.B * a.S) return;
+  const int b = wid / a.S, s = wid - b * a.S;
+  const int first = a.spans[2 * wid], count = a.spans[2 * wid + 1];
+  uint32_t* st = a.state + 4 * (long)wid;
+  SubStream d;
+  d.w = a.words + (first > 0 ? first : 0);
+  d.count = (first >= 0 && count > 0) ? (uint32_t)count : 0u;
+  d.x = (uint64_t)st[0] | ((uint64_t)st[1] << 32);
+  d.pos = st[2];
+#pragma unroll 1
+  for (int p = 0; p < a.P; ++p) {
+    const int h = a.pix[2 * p], w = a.pix[2 * p + 1];
+    if (h < 0 || h >= a.H || w < 0 || w >= a.W) continue;   // neither read nor written, consumes nothing
+    const float* grow = a.gp + ((long)b * a.P + p) * a.ldg;
+    float* out = a.y_hat + (((long)b * a.H + h) * a.W + w) * a.ldh;
+#pragma unroll 1
+    for (int c = s; c < a.N; c += a.S) {
+      float pi[K], mu[K], sg[K];
+      const int offset = gmm_row_params<K>(grow + c, a.N, pi, mu, sg);
+      // the 66 edges: j = lane, and j = 64 + (lane & 1), of which lanes 0 and 1 hold the two that count
+      const float f = gmm_cdf<K>((float)(offset + lane) - 0.5f, pi, mu, sg);
+      const float fx = gmm_cdf<K>((float)(offset + 64 + (lane & 1)) - 0.5f, pi, mu, sg);
+      float g = f;   // -> G_lane, the inclusive running maximum
+#pragma unroll
+      for (int dlt = 1; dlt < 64; dlt <<= 1) {
+        const float t = __shfl_up(g, dlt);
+        g = (lane >= dlt && t > g) ? t : g;
+      }
+      const float g0 = __shfl(g, 0), f64 = __shfl(fx, 0), f65 = __shfl(fx, 1);
+      float gt = __shfl(g, 63);
+      gt = (f64 > gt) ? f64 : gt;
+      const int cdf64 = 64 + (int)floorf((gt - g0) * kS);
+      gt = (f65 > gt) ? f65 : gt;
+      const int cdf65 = 65 + (int)floorf((gt - g0) * kS);   // (kL == 65)
+      const int cdf_l = lane + (int)floorf((g - g0) * kS);
+      // the symbol
+      const uint32_t cf = (uint32_t)d.x & 0xFFFFu;
+      const unsigned long long below = __ballot(lane >= 1 && (uint32_t)cdf_l <= cf);
+      const int v = __popcll(below) + ((uint32_t)cdf64 <= cf ? 1 : 0) + ((uint32_t)cdf65 <= cf ? 1 : 0);   // 0 .. kL
+      const int lo_l = __shfl(cdf_l, v & 63), hi_l = __shfl(cdf_l, (v + 1) & 63);
+      const int start = v < 64 ? lo_l : (v == 64 ? cdf64 : cdf65);
+      const int end = v < 63 ? hi_l : (v == 63 ? cdf64 : (v == 64 ? cdf65 : 65536));
+      d.x = (uint64_t)(uint32_t)(end - start) * (d.x >> 16) + cf - (uint32_t)start;
+      d.renorm();
+      uint32_t value = (uint32_t)v;
+      if (v == kL) {   // the tail: the bypass escape of clc_rans_decoder_decode, every loop bounded
+        uint32_t nb = d.get_bits();
+        if (nb == 15u) nb += d.get_bits();
+        nb = nb < 16u ? nb : 16u;
+        uint32_t raw = 0;
+#pragma unroll 1
+        for (uint32_t j = 0; j < nb; ++j) {
+          const uint32_t bits = d.get_bits();
+          if (j < 8) raw |= bits << (4 * j);
+        }
+        value = raw >> 1;
+        value = (raw & 1u) ? ~value : value + (uint32_t)kL;   // (-value - 1 == ~value)
+      }
+      if (lane == 0) out[c] = (float)(int32_t)(value + (uint32_t)offset);
+    }
+  }
+  if (lane == 0) {
+    st[0] = (uint32_t)d.x;
+    st[1] = (uint32_t)(d.x >> 32);
+    st[2] = d.pos;
   }
 }
 
@@ -357,6 +471,32 @@ extern "C" int clc_gmm_commit(const int32_t* symbols, int N, const int32_t* pix,
   CLC_CHECK((long)B * H * W < (1l << 31), "clc_gmm_commit: B * H * W must be below 2^31");
   const long rows = (long)B * P;
   hipLaunchKernelGGL(gmm_commit_kernel, dim3(grid_of(rows * N)), dim3(256), 0, ST, symbols, N, pix, P, H, W, y_hat, ldh, rows);
+  CLC_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int clc_gmm_decode_step(const float* gp, int ldg, int N, int K, const int32_t* pix, int P, int B, int H, int W, const uint32_t* words,
+                                   const int32_t* spans, clc_gmm_substream_state* state, int S, float* y_hat, int ldh, clc_stream_t stream) {
+  static_assert(kL == 65 && sizeof(clc_gmm_substream_state) == 16, "gmm_decode_kernel: 64 lanes and two extra edges; a 16-byte state");
+  CLC_CHECK(gp && pix && words && spans && state && y_hat, "clc_gmm_decode_step: null pointer");
+  CLC_CHECK(K >= 1 && K <= 4, "clc_gmm_decode_step: K must be between 1 and 4 (got %d)", K);
+  CLC_CHECK(P > 0 && B > 0 && H > 0 && W > 0 && N > 0, "clc_gmm_decode_step: P, B, H, W and N must be positive");
+  CLC_CHECK(S >= 1 && S <= 64, "clc_gmm_decode_step: S must be between 1 and 64 sub-streams (got %d)", S);
+  CLC_CHECK(S <= N, "clc_gmm_decode_step: S > N (%d sub-streams for %d channels: channel c belongs to sub-stream c mod S)", S, N);
+  CLC_CHECK((long)ldg >= 3l * K * N, "clc_gmm_decode_step: ldg < 3 K N (scales, means, weight logits: K blocks of N channels each)");
+  CLC_CHECK(ldh >= N, "clc_gmm_decode_step: ldh < N");
+  CLC_CHECK((long)B * H * W < (1l << 31), "clc_gmm_decode_step: B * H * W must be below 2^31");
+  CLC_CHECK((long)B * S < (1l << 24), "clc_gmm_decode_step: B * S must be below 2^24");
+  GmmDecArgs a = {};
+  a.gp = gp; a.ldg = ldg; a.N = N; a.pix = pix; a.P = P; a.B = B; a.H = H; a.W = W; a.words = words; a.spans = spans;
+  a.state = reinterpret_cast<uint32_t*>(state); a.S = S; a.y_hat = y_hat; a.ldh = ldh;
+  const dim3 grid((B * S + 3) / 4), block(256);
+  switch (K) {
+    case 1: hipLaunchKernelGGL(gmm_decode_kernel<1>, grid, block, 0, ST, a); break;
+    case 2: hipLaunchKernelGGL(gmm_decode_kernel<2>, grid, block, 0, ST, a); break;
+    case 3: hipLaunchKernelGGL(gmm_decode_kernel<3>, grid, block, 0, ST, a); break;
+    default: hipLaunchKernelGGL(gmm_decode_kernel<4>, grid, block, 0, ST, a); break;
+  }
   CLC_LAUNCH_CHECK();
   return 0;
 }

@@ -271,6 +271,7 @@ SIGNATURES = {
     "clc_gmm_likelihood_bwd": (_i, [fp, _i, fp, _i, fp, _i, fp, fp, fp, _i, fp, _i, fp, fp, fp, _i, _l, _i, _i, _i, fp]),
     "clc_gmm_finish": (_i, [fp, _i, _i, _i, fp, _i, _i, _i, _i, fp, _i, fp, _i, fp, fp, fp, _i, fp]),
     "clc_gmm_commit": (_i, [fp, _i, fp, _i, _i, _i, _i, fp, _i, fp]),
+    "clc_gmm_decode_step": (_i, [fp, _i, _i, _i, fp, _i, _i, _i, _i, fp, fp, fp, _i, fp, _i, fp]),
 }
 
 

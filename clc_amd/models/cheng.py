@@ -24,10 +24,18 @@ RULE of include/clc_hip.h), built on the device by the same scan on both sides; 
 chain runs on clc_ar_linear on both sides (its summation order depends on K alone), h_s on the batch-invariant 3x3 routes the CLC codec
 relies on: a stream written at batch 8 decodes at batch 1.
 
+THE SPLIT STREAM (K > 1, opt-in: ``compress(x, substreams=S)`` / ``decompress(..., substreams=S)``).  The y string becomes
+``ans.split_pack`` of S independent rANS sub-streams: element (position i of ar_wavefront_order, channel c) belongs to sub-stream c mod S,
+inside a sub-stream i ascending then c ascending, and sub-stream s is exactly ``ans.encode_direct(triples[:, s::S])`` — same triples, same
+host coder.  8 + 12 S bytes more per image (200 at S = 16).  Its decoder runs on the device, one wave per (image, sub-stream)
+(clc_gmm_decode_step): the whole wavefront pass is stream-ordered launches with no host hop.  The default stays the one-stream format,
+byte for byte.
+
 TrainEngine, graphed_training, CodecEngine and ReferenceBank do not take these models.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -158,17 +166,37 @@ class Cheng2020Anchor(JointAutoregressiveHierarchicalPriors):
             parts.append(t)
         return (parts[0] if len(parts) == 1 else torch.cat(parts, 1)), y_hat
 
+    def _split_count(self, substreams, what):
+        """the checked S of a ``substreams=`` keyword (None: the one-stream format)"""
+        if substreams is None:
+            return None
+        name = type(self).__name__
+        if self.K == 1:
+            raise ValueError(f"{name}.{what}: substreams= needs a mixture model (K > 1); the K = 1 stream is CompressAI's and stays one stream")
+        S = int(substreams)
+        if not 1 <= S <= ans.SPLIT_MAX:
+            raise ValueError(f"{name}.{what}: substreams must be between 1 and {ans.SPLIT_MAX} (got {substreams})")
+        if S > self.N:
+            raise ValueError(f"{name}.{what}: substreams = {S} > N = {self.N} (channel c belongs to sub-stream c mod S: some would be empty)")
+        return S
+
     @torch.no_grad()
-    def compress(self, x, order="wavefront"):
+    def compress(self, x, order="wavefront", substreams=None):
+        """substreams=None: the one-stream format.  substreams=S (K > 1): THE SPLIT STREAM of the module docstring, and "substreams": S
+        in the result; pass the same S to decompress."""
+        S = self._split_count(substreams, "compress")
         if self.K == 1:
             return super().compress(x, order)
         y, params, z_strings, z_size = self._code_inputs(x)
         triples, _ = self._gmm_encode(y, params)
         t = triples.cpu().numpy()   # the one device -> host copy
-        y_strings = [ans.encode_direct(t[i]) for i in range(t.shape[0])]
         from ..codec import kernel_config
 
-        return {"strings": [y_strings, z_strings], "shape": z_size, "kernel_config": kernel_config()}
+        if S is None:
+            y_strings = [ans.encode_direct(t[i]) for i in range(t.shape[0])]
+            return {"strings": [y_strings, z_strings], "shape": z_size, "kernel_config": kernel_config()}
+        y_strings = [ans.split_pack([ans.encode_direct(t[i][:, s::S, :]) for s in range(S)]) for i in range(t.shape[0])]
+        return {"strings": [y_strings, z_strings], "shape": z_size, "kernel_config": kernel_config(), "substreams": S}
 
     @torch.no_grad()
     def _gmm_decode(self, y_strings, params):
@@ -218,14 +246,134 @@ class Cheng2020Anchor(JointAutoregressiveHierarchicalPriors):
             ops.gmm_commit(sym_dev[:n], N, px, y_hat)
         return y_hat
 
+    def _split_parse(self, y_strings, S):
+        """-> per image the S sub-streams of its split string; a header that disagrees with the caller's S is refused"""
+        subs = []
+        for b, blob in enumerate(y_strings):
+            got = ans.split_unpack(blob)
+            if len(got) != S:
+                raise ValueError(f"decompress: substreams = {S}, but the header of image {b} says {len(got)} sub-streams")
+            subs.append(got)
+        return subs
+
     @torch.no_grad()
-    def decompress(self, strings, shape):
+    def _gmm_decode_split(self, subs, params, device_decoder=True):
+        """The wavefront pass over split streams (subs[b][s]: bytes) -> (y_hat, state).
+        device_decoder: one pinned upload of every sub-stream's words, spans and initial states, then per non-empty step the chain and
+        one clc_gmm_decode_step — stream-ordered launches only, no download, no synchronize, no per-image loop; state is the device's
+        int32 [B, S, 4] (x low, x high, pos, pad) as the last step left it.
+        Host decoder: the hop per step of _gmm_decode with one RansDecoder per (image, sub-stream); state is None."""
+        params = params.contiguous(memory_format=CL)
+        dev = params.device
+        B, N, K, (H, W) = params.shape[0], self.N, self.K, params.shape[2:]
+        if len(subs) != B:
+            raise ValueError(f"decompress: {len(subs)} y streams for {B} z streams")
+        S = len(subs[0])
+        steps, pix = self._ar_pixels(ar_schedule(H, W, "wavefront"), dev)
+        rows = B * max(len(s) for s in steps)
+        ws = self._gmm_workspace(rows, dev)
+        filt = self._ar_filters()
+        y_hat = torch.zeros((B, N, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
+        off = 0
+        if device_decoder:
+            flat = [np.frombuffer(s, dtype="<u4") for img in subs for s in img]
+            counts = np.array([w.size for w in flat], dtype=np.int64)
+            firsts = np.concatenate(([0], np.cumsum(counts)[:-1]))
+            n_words = int(counts.sum())
+            if n_words >= 1 << 31:
+                raise ValueError(f"decompress: {n_words} stream words in one batch; the spans are int32")
+            # one pinned buffer, one upload: the states, the spans, the words
+            host = torch.empty((6 * B * S + n_words,), dtype=torch.int32).pin_memory()
+            h = host.numpy().view(np.uint32)
+            st = h[:4 * B * S].reshape(B * S, 4)
+            st[:, 0], st[:, 1], st[:, 2], st[:, 3] = [w[0] for w in flat], [w[1] for w in flat], 2, 0
+            sp = h[4 * B * S:6 * B * S].reshape(B * S, 2)
+            sp[:, 0], sp[:, 1] = firsts, counts
+            h[6 * B * S:] = np.concatenate(flat)
+            d = torch.empty((host.numel(),), device=dev, dtype=torch.int32)
+            d.copy_(host, non_blocking=True)
+            state, spans, words = d[:4 * B * S].view(B, S, 4), d[4 * B * S:6 * B * S].view(B, S, 2), d[6 * B * S:]
+            for s in steps:
+                px = pix[off:off + len(s)]
+                off += len(s)
+                self._ar_chain(px, B, H, W, y_hat, params, ws, filt)
+                ops.gmm_decode_step(ws["gp"], N, K, px, words, spans, state, y_hat)
+            # (host's pages stay pinned until the copy has run: the caching host allocator holds them back until then)
+            return y_hat, state
+        decoders = []
+        for img in subs:
+            decoders.append([])
+            for s in img:
+                dd = ans.RansDecoder()
+                dd.set_stream(s)
+                decoders[-1].append(dd)
+        R = ops.GMM_ROW_STRIDE
+        down_dev = torch.empty((rows * N * (R + 1),), device=dev, dtype=torch.int32)
+        down_host = torch.empty((rows * N * (R + 1),), dtype=torch.int32).pin_memory()
+        sym_dev = torch.empty((rows, N), device=dev, dtype=torch.int32)
+        sym_host = torch.empty((rows, N), dtype=torch.int32).pin_memory()
+        down_np, sym_np = down_host.numpy(), sym_host.numpy()
+        stream = torch.cuda.current_stream(dev)
+        for s in steps:
+            cnt = len(s)
+            n = B * cnt
+            px = pix[off:off + cnt]
+            off += cnt
+            self._ar_chain(px, B, H, W, y_hat, params, ws, filt)
+            ops.gmm_finish_decode(ws["gp"], N, K, px, B, H, W, down_dev[:n * N * R].view(n, N, R), down_dev[n * N * R:n * N * (R + 1)].view(n, N))
+            down_host[:n * N * (R + 1)].copy_(down_dev[:n * N * (R + 1)], non_blocking=True)
+            stream.synchronize()
+            rows_np = down_np[:n * N * R].reshape(B, cnt, N, R)
+            offs_np = down_np[n * N * R:n * N * (R + 1)].reshape(B, cnt, N)
+            for b in range(B):
+                for k, dd in enumerate(decoders[b]):   # sub-stream k's elements of the step: list order, then its channels ascending
+                    r = np.ascontiguousarray(rows_np[b, :, k::S]).reshape(-1, R)
+                    o = np.ascontiguousarray(offs_np[b, :, k::S]).reshape(-1)
+                    sym_np[b * cnt:(b + 1) * cnt, k::S] = dd.decode_rows(r, o).reshape(cnt, -1)
+            sym_dev[:n].copy_(sym_host[:n], non_blocking=True)
+            ops.gmm_commit(sym_dev[:n], N, px, y_hat)
+        return y_hat, None
+
+    @staticmethod
+    def _split_check(state, subs):
+        """A sub-stream decoded to its end leaves x == 2^31 and pos == its word count (the coder's end-state property); anything else
+        raises, naming per image every sub-stream that did not.  (A wrong symbol enters the context of the pixels after it, so a damaged
+        sub-stream usually takes the image's others out of step with it: the list holds the damaged one, it cannot single it out.)"""
+        st = state.cpu().numpy().view(np.uint32)   # the one download of the device path
+        bad = []
+        for b, img in enumerate(subs):
+            off = [s for s, blob in enumerate(img)
+                   if (int(st[b, s, 0]), int(st[b, s, 1]), int(st[b, s, 2])) != (1 << 31, 0, len(blob) // 4)]
+            if off:
+                s = off[0]
+                bad.append(f"image {b}: sub-streams {off} did not decode to their end (sub-stream {s}: final state x = "
+                           f"{int(st[b, s, 0]) | int(st[b, s, 1]) << 32:#x}, {int(st[b, s, 2])} of {len(img[s]) // 4} words consumed)")
+        if bad:
+            raise ValueError("decompress: " + "; ".join(bad) + ": the stream is corrupt, truncated or belongs to other parameters")
+
+    @torch.no_grad()
+    def decompress(self, strings, shape, substreams=None, device_decoder=True, check=True):
+        """substreams=None: the one-stream format.  substreams=S: the split stream of compress(x, substreams=S), decoded on the device
+        (device_decoder=True: no device -> host copy and no synchronize between the upload of the streams and the finished y_hat;
+        check=True adds ONE download of the final coder states, after the synthesis transform has been launched, and raises ValueError
+        naming the image and the sub-streams that did not end where a whole stream ends — a check against streams out of step or cut
+        short, not a checksum: a changed bit inside an escape's raw payload decodes to another symbol and ends clean) or on the host (device_decoder=False: a hop per
+        step, the rows of clc_gmm_finish through RansDecoder.decode_rows — the same symbols)."""
+        S = self._split_count(substreams, "decompress")
         if self.K == 1:
             return super().decompress(strings, shape)
         assert isinstance(strings, (list, tuple)) and len(strings) == 2
+        if S is None:
+            z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
+            y_hat = self._gmm_decode(strings[0], self._hyper_synthesis(z_hat))
+            return {"x_hat": self._synthesis(y_hat).clamp_(0, 1)}
+        subs = self._split_parse(strings[0], S)
         z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
-        y_hat = self._gmm_decode(strings[0], self._hyper_synthesis(z_hat))
-        return {"x_hat": self._synthesis(y_hat).clamp_(0, 1)}
+        y_hat, state = self._gmm_decode_split(subs, self._hyper_synthesis(z_hat), device_decoder)
+        x_hat = self._synthesis(y_hat).clamp_(0, 1)
+        if check and state is not None:
+            self._split_check(state, subs)
+        return {"x_hat": x_hat}
 
 
 class Cheng2020Attention(Cheng2020Anchor):

@@ -2959,3 +2959,25 @@ def gmm_commit(symbols, N, pix, y_hat):
     if lds != N or symbols.shape[1] != N or Ch != N:
         raise ValueError(f"gmm_commit: symbols must be a dense [rows, N = {N}] buffer and y_hat have N channels")
     _lib.check(_L().clc_gmm_commit(sp, N, pp, P, B, H, W, hp, ldh, _stream()), "clc_gmm_commit")
+
+
+def gmm_decode_step(gp, N, K, pix, words, spans, state, y_hat):
+    """clc_gmm_decode_step: one wavefront step of the split stream's device decoder.  gp [>= B P, >= 3 K N] parameter rows of the step;
+    words int32 [n] (every sub-stream's 32-bit words), spans int32 [B, S, 2] (first word, word count), state int32 [B, S, 4]
+    (x low, x high, pos, pad: read, advanced and written back) — all on the device; y_hat[pixel][c] = the decoded symbol.  No copy to
+    the host, no sync: the caller keeps every span inside ``words``."""
+    pp, P = _ar_pix(pix)
+    hp, B, H, W, Ch, ldh = _ar_map(y_hat, "gmm_decode_step")
+    if Ch != N:
+        raise ValueError(f"gmm_decode_step: y_hat must have N = {N} channels (got {Ch})")
+    gpp, ldg = _gmm_gp(gp, B * P, N, K, "gmm_decode_step")
+    for t, what in ((words, "words"), (spans, "spans"), (state, "state")):
+        if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"gmm_decode_step: {what} must be a contiguous int32 device tensor")
+    if spans.dim() != 3 or spans.shape[0] != B or spans.shape[2] != 2 or words.dim() != 1 or words.numel() < 1:
+        raise ValueError(f"gmm_decode_step: words must be int32 [n >= 1] and spans int32 [B = {B}, S, 2] (got {tuple(words.shape)}, {tuple(spans.shape)})")
+    S = int(spans.shape[1])
+    if tuple(state.shape) != (B, S, 4) or state.data_ptr() % 8:
+        raise ValueError(f"gmm_decode_step: state must be an 8-byte aligned int32 [B, S, 4] = {(B, S, 4)} tensor (got {tuple(state.shape)})")
+    _lib.check(_L().clc_gmm_decode_step(gpp, ldg, N, K, pp, P, B, H, W, words.data_ptr(), spans.data_ptr(), state.data_ptr(), S, hp, ldh,
+                                        _stream()), "clc_gmm_decode_step")

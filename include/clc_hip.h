@@ -814,8 +814,35 @@ int clc_row_gemm(const clc_ar_src* srcs /* HOST */, int nsrc, const int32_t* pix
  *                    CLC_AR_DECODE  cdf_rows[(r * N + c) * CLC_GMM_ROW_STRIDE ..] = the row, offsets[r * N + c] = offset.
  *                  Both modes run the same scan, so an encoder's (start, freq) are the decoder's row entries bit for bit.
  * clc_gmm_commit   y_hat[pixel][c] = (float)symbols[r * N + c] from decoded symbols (dense [rows][N] int32).
- * All stream-ordered, graph-capturable, allocation- and sync-free; no workspace; no workgroup waits on another.  Bad arguments are
- * refused by name before any launch. */
+ *
+ * clc_gmm_decode_step   the decoder of the SPLIT stream (clc_amd/ans.py: split_pack), on the device: one step of the wavefront for the
+ *                  whole batch with no copy to the host.  An image's y symbols are dealt to S independent rANS sub-streams, channel c
+ *                  to sub-stream c mod S; sub-stream s of image b is the 32-bit words words[first .. first + count) with
+ *                  (first, count) = spans[(b * S + s) * 2 ..], and its decoder's state is state[b * S + s] (x, pos: the words consumed
+ *                  so far; a fresh decoder has x = word 0 | word 1 << 32, pos = 2), carried in device memory from call to call.
+ *                  One wave per (b, s), four waves per workgroup.  The wave walks the list's pixels p = 0 .. P - 1 in list order and
+ *                  per pixel its channels c = s, s + S, ... < N; a pixel outside the map is neither read nor written and consumes
+ *                  nothing.  PER SYMBOL, from the parameter row gp[(b * P + p) * ldg ..] at channel c:
+ *                    pi, s_k, ctr, offset as THE ROW RULE has them (the code of clc_gmm_finish);
+ *                    lane l evaluates F_l, lanes 0 and 1 also F_64 and F_65 (L = 65: the 66 edges j = 0 .. L); G_j is the running
+ *                    maximum in j order (an inclusive max-scan over the lanes, continued into the two extra edges; max is exact, so
+ *                    the scan's shape changes no bit); cdf[j] = j + floor((G_j - G_0) * S'), S' = 65535 - L, cdf[L + 1] = 65536: the
+ *                    row of clc_gmm_finish bit for bit, never written to memory;
+ *                    cf = x & 0xFFFF; the symbol's place v = #{j in 1 .. L : cdf[j] <= cf} (a ballot and a popcount);
+ *                    x = (cdf[v + 1] - cdf[v]) * (x >> 16) + cf - cdf[v]; then, as after every nibble below, while-free renorm:
+ *                    if x < 2^31: x = x << 32 | word[pos] (zero at or past count), pos += 1;
+ *                    v == L, the tail: a nibble n = x & 15, x >>= 4 (and one more, added, if the first was 15 — never more than two),
+ *                    then min(n, 16) payload nibbles LSB first, the first 8 of them kept as raw; value = raw >> 1, and
+ *                    v = -value - 1 if raw is odd, else value + L: what clc_rans_decoder_decode reads;
+ *                    y_hat[pixel][c] = (float)(v + offset).
+ *                  When the wave is done, (x, pos) go back to state.  On every stream clc_rans_encode_direct can produce, the symbols
+ *                  are those of clc_rans_decoder_decode through the rows of clc_gmm_finish, and a sub-stream decoded to its end
+ *                  leaves x == 2^31 and pos == count.  On any other words they are some wrong symbols: every loop is bounded by a
+ *                  constant or the symbol count, and no word outside [first, first + count) is read (a negative first or count
+ *                  reads nothing).  The caller keeps first + count inside the words buffer.
+ *                  Requires K in 1 .. 4, S in 1 .. 64, S <= N, ldg >= 3 K N, ldh >= N, B * H * W < 2^31.
+ * All stream-ordered, graph-capturable, allocation- and sync-free; no workspace, no LDS, no barrier; no workgroup (and in
+ * clc_gmm_decode_step no wave) waits on another.  Bad arguments are refused by name before any launch. */
 #define CLC_GMM_R 32
 #define CLC_GMM_ROW_STRIDE (2 * CLC_GMM_R + 3)
 int clc_gmm_half_width(void);   /* CLC_GMM_R of the built library */
@@ -827,6 +854,10 @@ int clc_gmm_likelihood_bwd(const float* dlik, int lddl, const float* y, int ldy,
 int clc_gmm_finish(const float* gp, int ldg, int N, int K, const int32_t* pix, int P, int B, int H, int W, const float* y, int ldy, float* y_hat,
                    int ldh, int32_t* triples, int32_t* cdf_rows, int32_t* offsets, int mode, clc_stream_t stream);
 int clc_gmm_commit(const int32_t* symbols, int N, const int32_t* pix, int P, int B, int H, int W, float* y_hat, int ldh, clc_stream_t stream);
+typedef struct { uint64_t x; uint32_t pos; uint32_t pad; } clc_gmm_substream_state;   /* 16 bytes, DEVICE memory */
+int clc_gmm_decode_step(const float* gp, int ldg, int N, int K, const int32_t* pix, int P, int B, int H, int W, const uint32_t* words,
+                        const int32_t* spans /* [B][S][2]: first word, word count */, clc_gmm_substream_state* state /* [B][S] */, int S,
+                        float* y_hat, int ldh, clc_stream_t stream);
 
 #ifdef __cplusplus
 }
