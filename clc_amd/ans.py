@@ -114,6 +114,150 @@ def split_unpack(blob) -> list:
     return out
 
 
+LANES_MAGIC = b"CLN1"
+LANES = 64          # rANS lanes of a wave stream: one per GPU lane
+LANES_MAX_W = 16    # wave streams per image: one wave each on the device coder (clc_rans_lanes_decode_step / clc_rans_lanes_encode)
+
+
+def _lanes_length_ok(n):
+    return n >= 8 * LANES and n % 4 == 0
+
+
+def _lanes_w(W, who):
+    if isinstance(W, bool) or not isinstance(W, (int, np.integer)) or not 1 <= int(W) <= LANES_MAX_W:
+        raise ValueError(f"{who}: W must be between 1 and {LANES_MAX_W} wave streams (got {W!r})")
+    return int(W)
+
+
+def lanes_pack(streams) -> bytes:
+    """The W wave streams of one image's lane-interleaved stream (include/clc_hip.h: the "lanes" stream) as one string, little endian:
+
+        b"CLN1" | u8 W | u8 64 | 2 x u8 0 | W x u32 byte length | the W wave streams, back to back
+
+    A wave stream is 32-bit words and starts with its 64 lane states (512 bytes).  Overhead against the one stream of ``encode``:
+    8 + 4 W bytes of header plus 512 W bytes of lane states."""
+    streams = [bytes(s) for s in streams]
+    W = len(streams)
+    if not 1 <= W <= LANES_MAX_W:
+        raise ValueError(f"lanes_pack: W must be between 1 and {LANES_MAX_W} wave streams (got {W})")
+    for i, s in enumerate(streams):
+        if not _lanes_length_ok(len(s)):
+            raise ValueError(f"lanes_pack: wave stream {i} has {len(s)} bytes; a length must be a multiple of 4 and at least {8 * LANES}")
+    head = LANES_MAGIC + bytes([W, LANES, 0, 0]) + np.array([len(s) for s in streams], dtype="<u4").tobytes()
+    return head + b"".join(streams)
+
+
+def lanes_unpack(blob) -> list:
+    """-> the W wave streams of a ``lanes_pack`` string; anything malformed is refused by name."""
+    blob = bytes(blob)
+    if len(blob) < 8 or blob[:4] != LANES_MAGIC:
+        raise ValueError(f"lanes_unpack: bad magic {blob[:4]!r} (a lanes stream starts with {LANES_MAGIC!r})")
+    W = blob[4]
+    if not 1 <= W <= LANES_MAX_W:
+        raise ValueError(f"lanes_unpack: W must be between 1 and {LANES_MAX_W} wave streams (got {W})")
+    if blob[5] != LANES:
+        raise ValueError(f"lanes_unpack: the lane byte must be {LANES} (got {blob[5]})")
+    if blob[6:8] != b"\0\0":
+        raise ValueError(f"lanes_unpack: non-zero pad byte in the header ({blob[6:8].hex()})")
+    if len(blob) < 8 + 4 * W:
+        raise ValueError(f"lanes_unpack: the lengths do not add up to the blob ({len(blob)} bytes end inside the header of W = {W})")
+    lengths = [int(n) for n in np.frombuffer(blob, dtype="<u4", count=W, offset=8)]
+    for i, n in enumerate(lengths):
+        if not _lanes_length_ok(n):
+            raise ValueError(f"lanes_unpack: wave stream {i} has length {n}; a length must be a multiple of 4 and at least {8 * LANES}")
+    if 8 + 4 * W + sum(lengths) != len(blob):
+        raise ValueError(f"lanes_unpack: the lengths do not add up to the blob (header {8 + 4 * W} + {sum(lengths)} != {len(blob)} bytes)")
+    out, at = [], 8 + 4 * W
+    for n in lengths:
+        out.append(blob[at:at + n])
+        at += n
+    return out
+
+
+def lanes_wave_symbols(segments, W):
+    """-> per wave stream the number of symbols it carries: chunk q (64 symbols) of every segment belongs to wave q % W"""
+    n_w = [0] * W
+    for n in segments:
+        n = int(n)
+        for q in range((n + LANES - 1) // LANES):
+            n_w[q % W] += min(LANES, n - q * LANES)
+    return n_w
+
+
+def lanes_encode(symbols, indexes, segments, W, cdfs, cdfs_sizes, offsets) -> list:
+    """One image's symbols / indexes in stream order (the segments back to back) -> its W wave streams (bytes), by the host coder
+    (clc_rans_lanes_encode_host): the bytes the device encoder writes."""
+    L = _lib.load()
+    W = _lanes_w(W, "lanes_encode")
+    sym, idx = _i32(symbols).reshape(-1), _i32(indexes).reshape(-1)
+    seg = _i32(segments).reshape(-1)
+    if sym.size != idx.size:
+        raise ValueError("lanes_encode: symbols and indexes must have the same length")
+    if (seg < 0).any() or int(seg.sum()) != sym.size:
+        raise ValueError(f"lanes_encode: the segment lengths must be non-negative and add up to the {sym.size} symbols (got {seg.tolist()})")
+    cdf, ln, off = _tables(cdfs, cdfs_sizes, offsets)
+    cap = sum(L.clc_rans_lanes_bound(n) for n in lanes_wave_symbols(seg, W))
+    buf = np.empty(cap, dtype=np.uint8)
+    lengths = np.zeros(W, dtype=np.int32)
+    n = L.clc_rans_lanes_encode_host(sym.ctypes.data, idx.ctypes.data, seg.ctypes.data, seg.size, W, cdf.ctypes.data, cdf.shape[1], cdf.shape[0],
+                                     ln.ctypes.data, off.ctypes.data, buf.ctypes.data, cap, lengths.ctypes.data)
+    _lib.check(n, "clc_rans_lanes_encode_host")
+    ends = np.cumsum(lengths)
+    return [buf[e - m:e].tobytes() for e, m in zip(ends, lengths)]
+
+
+class LanesDecoder:
+    """Incremental host decoder of one image's W wave streams (clc_rans_lanes_decoder_*): ``decode`` takes the next segment's indexes."""
+
+    def __init__(self, streams):
+        L = _lib.load()
+        streams = [bytes(s) for s in streams]
+        self.W = len(streams)
+        self._h = None
+        self.lengths = np.array([len(s) for s in streams], dtype=np.int32)
+        b = np.frombuffer(b"".join(streams) or b"\0", dtype=np.uint8)
+        self._h = L.clc_rans_lanes_decoder_create(b.ctypes.data, self.lengths.ctypes.data, self.W)
+        if not self._h:
+            raise _lib.ClcError(f"clc_rans_lanes_decoder_create failed: {L.clc_last_error().decode()}")
+
+    def decode(self, indexes, cdfs, cdfs_sizes, offsets):
+        L = _lib.load()
+        idx = _i32(indexes).reshape(-1)
+        cdf, ln, off = _tables(cdfs, cdfs_sizes, offsets)
+        out = np.empty(idx.size, dtype=np.int32)
+        n = L.clc_rans_lanes_decoder_decode(self._h, idx.ctypes.data, idx.size, cdf.ctypes.data, cdf.shape[1], cdf.shape[0], ln.ctypes.data,
+                                            off.ctypes.data, out.ctypes.data)
+        _lib.check(n, "clc_rans_lanes_decoder_decode")
+        return out
+
+    def state(self, w):
+        """-> (the 64 lane states of wave stream w as uint64, the words consumed so far)"""
+        L = _lib.load()
+        x = np.empty(LANES, dtype=np.uint64)
+        pos = C.c_long(0)
+        _lib.check(L.clc_rans_lanes_decoder_state(self._h, int(w), x.ctypes.data, C.byref(pos)), "clc_rans_lanes_decoder_state")
+        return x, int(pos.value)
+
+    def at_end(self):
+        """every wave stream decoded to its end: all lanes at 2^31 and pos == its word count"""
+        for w in range(self.W):
+            x, pos = self.state(w)
+            if not (x == np.uint64(1 << 31)).all() or pos != int(self.lengths[w]) // 4:
+                return False
+        return True
+
+    def close(self):
+        if self._h:
+            _lib.load().clc_rans_lanes_decoder_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 _ROW_INDEX = {}   # n -> (arange(n), full(n, size)) int32: the index / size arrays of a decode over per-symbol rows
 
 

@@ -278,3 +278,246 @@ extern "C" int clc_pmf_to_quantized_cdf(const float* pmf, int n, int precision, 
   for (int i = 0; i <= n; ++i) cdf_out[i] = (int32_t)c[i];
   return 0;
 }
+
+// ------------------------------------------------------------------------------------------------ the lane-interleaved ("lanes") stream
+// The host coder of the format include/clc_hip.h fixes under clc_rans_lanes_*: W wave streams per image, each 64 rANS lanes that share
+// one word array.  The arithmetic per lane is the one above (enc_put / enc_put_bits / the escape; the symbol update, renorm and get_bits
+// of clc_rans_decoder_decode); what is new is only WHO takes the next word: per round (one chunk of 64 symbols) the lanes run sub-steps
+// t = 0, 1, ... (0: the symbol; 1 ..: the escape's nibbles), and inside a sub-step the lanes that renormalise take the next words in
+// ascending lane order.  The encoder is the exact reverse.  csrc/rans_lanes.hip runs the same procedure with one lane per GPU lane.
+namespace {
+constexpr int kLanes = 64, kLanesMaxW = 16, kLanesMaxCount = 2, kLanesMaxPayload = 16;
+
+struct LaneTables {
+  const int32_t* cdfs; int cdf_stride, n_rows; const int32_t* cdf_sizes; const int32_t* offsets;
+};
+
+// every index inside the table, every row's size usable: checked before a coder changes any state
+bool lanes_check_rows(const char* who, const LaneTables& T, const int32_t* indexes, long n) {
+  for (long i = 0; i < n; ++i) {
+    const int32_t ci = indexes[i];
+    if (ci < 0 || ci >= T.n_rows) { clc_set_error("%s: index %d outside the table of %d rows (symbol %ld)", who, ci, T.n_rows, i); return false; }
+    if (T.cdf_sizes[ci] < 2 || T.cdf_sizes[ci] > T.cdf_stride) { clc_set_error("%s: bad cdf size %d at index %d", who, T.cdf_sizes[ci], ci); return false; }
+  }
+  return true;
+}
+
+// symbols of a segment of n that wave w of W owns: its chunks q = w, w + W, ...
+long lanes_wave_symbols(long n, int w, int W) {
+  const long chunks = (n + kLanes - 1) / kLanes;
+  long total = 0;
+  for (long q = w; q < chunks; q += W) total += (q + 1) * kLanes <= n ? kLanes : n - q * kLanes;
+  return total;
+}
+
+struct LaneOp { uint32_t start, freq; };   // freq == 0: a 4-bit bypass of value start
+}  // namespace
+
+extern "C" long clc_rans_lanes_bound(long n_w) { return 4 * (2 * kLanes + 10 * n_w); }
+
+extern "C" long clc_rans_lanes_encode_host(const int32_t* symbols, const int32_t* indexes, const int32_t* seg_len, int P, int W, const int32_t* cdfs,
+                                      int cdf_stride, int n_rows, const int32_t* cdf_sizes, const int32_t* offsets, uint8_t* out, long out_cap,
+                                      int32_t* lengths) {
+  if (W < 1 || W > kLanesMaxW) { clc_set_error("clc_rans_lanes_encode_host: W must be between 1 and %d waves (got %d)", kLanesMaxW, W); return -1; }
+  if (P < 0 || (P > 0 && !seg_len) || !cdfs || !cdf_sizes || !offsets || !out || !lengths || cdf_stride < 2 || n_rows < 1) {
+    clc_set_error("clc_rans_lanes_encode_host: bad args");
+    return -1;
+  }
+  long total = 0;
+  for (int p = 0; p < P; ++p) {
+    if (seg_len[p] < 0) { clc_set_error("clc_rans_lanes_encode_host: segment %d has a negative length (%d)", p, seg_len[p]); return -1; }
+    total += seg_len[p];
+  }
+  if (total > 0 && (!symbols || !indexes)) { clc_set_error("clc_rans_lanes_encode_host: bad args"); return -1; }
+  const LaneTables T = {cdfs, cdf_stride, n_rows, cdf_sizes, offsets};
+  if (!lanes_check_rows("clc_rans_lanes_encode_host", T, indexes, total)) return -1;
+  long need = 0;
+  std::vector<long> n_w((size_t)W, 0);
+  for (int w = 0; w < W; ++w) {
+    for (int p = 0; p < P; ++p) n_w[(size_t)w] += lanes_wave_symbols(seg_len[p], w, W);
+    need += clc_rans_lanes_bound(n_w[(size_t)w]);
+  }
+  if (out_cap < need || (reinterpret_cast<uintptr_t>(out) & 3)) {
+    clc_set_error("clc_rans_lanes_encode_host: output buffer too small or unaligned (%ld bytes, needs %ld)", out_cap, need);
+    return -1;
+  }
+  std::vector<long> seg_at((size_t)P + 1, 0);
+  for (int p = 0; p < P; ++p) seg_at[(size_t)p + 1] = seg_at[(size_t)p] + seg_len[p];
+  std::vector<uint32_t> region;
+  long written = 0;
+  for (int w = 0; w < W; ++w) {
+    region.assign((size_t)(2 * kLanes + 10 * n_w[(size_t)w]), 0u);
+    BackWriter o;
+    o.begin = region.data();
+    o.ptr = o.begin + region.size();
+    uint32_t* const end = o.ptr;
+    uint64_t x[kLanes];
+    for (int l = 0; l < kLanes; ++l) x[l] = kL;
+    for (int p = P - 1; p >= 0; --p) {
+      const long n = seg_len[p], chunks = (n + kLanes - 1) / kLanes;
+      if (chunks <= w) continue;
+      for (long q = chunks - 1 - (chunks - 1 - w) % W; q >= 0; q -= W) {   // the wave's chunks of the segment, last first
+        LaneOp ops[kLanes][10];
+        int nops[kLanes];
+        for (int l = 0; l < kLanes; ++l) {
+          const long j = q * kLanes + l;
+          nops[l] = 0;
+          if (j >= n) continue;
+          const int32_t ci = indexes[seg_at[(size_t)p] + j];
+          const int32_t* cdf = cdfs + (long)ci * cdf_stride;
+          const int32_t max_value = cdf_sizes[ci] - 2;
+          int32_t value = (int32_t)((uint32_t)symbols[seg_at[(size_t)p] + j] - (uint32_t)offsets[ci]);
+          uint32_t raw = 0;
+          bool escape = false;
+          if (value < 0) { raw = (uint32_t)(-2 * (int64_t)value - 1); value = max_value; escape = true; }
+          else if (value >= max_value) { raw = (uint32_t)(2 * ((int64_t)value - max_value)); value = max_value; escape = true; }
+          const uint32_t start = (uint32_t)cdf[value] & 0xFFFFu, freq = (uint32_t)(cdf[value + 1] - cdf[value]) & 0xFFFFu;
+          if (freq == 0) { clc_set_error("clc_rans_lanes_encode_host: zero-frequency symbol (index %d value %d)", ci, value); return -1; }
+          ops[l][0] = {start, freq};
+          nops[l] = 1;
+          if (escape) {   // a payload has at most 8 nibbles: one count nibble, then the nibbles LSB first
+            int nb = 0;
+            while (nb < 8 && (raw >> (nb * kBypassBits)) != 0) ++nb;
+            ops[l][1] = {(uint32_t)nb, 0u};
+            for (int k = 0; k < nb; ++k) ops[l][2 + k] = {(raw >> (k * kBypassBits)) & kBypassMax, 0u};
+            nops[l] = 2 + nb;
+          }
+        }
+        for (int t = 9; t >= 0; --t)
+          for (int l = kLanes - 1; l >= 0; --l) {
+            if (t >= nops[l]) continue;
+            if (ops[l][t].freq) enc_put(x[l], o, ops[l][t].start, ops[l][t].freq); else enc_put_bits(x[l], o, ops[l][t].start);
+          }
+      }
+    }
+    for (int l = kLanes - 1; l >= 0; --l) { o.put((uint32_t)(x[l] >> 32)); o.put((uint32_t)x[l]); }
+    if (o.overflow) { clc_set_error("clc_rans_lanes_encode_host: wave stream %d overflows its region of %zu words", w, region.size()); return -2; }
+    const long nbytes = (long)(end - o.ptr) * 4;
+    memcpy(out + written, o.ptr, (size_t)nbytes);
+    lengths[w] = (int32_t)nbytes;
+    written += nbytes;
+  }
+  return written;
+}
+
+struct clc_rans_lanes_decoder {
+  int W;
+  std::vector<std::vector<uint32_t>> words;   // per wave
+  std::vector<uint64_t> x;                    // [W][64]
+  std::vector<size_t> pos;                    // [W]
+};
+
+extern "C" clc_rans_lanes_decoder* clc_rans_lanes_decoder_create(const uint8_t* streams, const int32_t* lengths, int W) {
+  if (W < 1 || W > kLanesMaxW) { clc_set_error("clc_rans_lanes_decoder_create: W must be between 1 and %d waves (got %d)", kLanesMaxW, W); return nullptr; }
+  if (!streams || !lengths) { clc_set_error("clc_rans_lanes_decoder_create: bad args"); return nullptr; }
+  for (int w = 0; w < W; ++w)
+    if (lengths[w] < 8 * kLanes || (lengths[w] & 3)) {
+      clc_set_error("clc_rans_lanes_decoder_create: wave stream %d has %d bytes; a stream must be >= %d bytes, multiple of 4", w, lengths[w], 8 * kLanes);
+      return nullptr;
+    }
+  clc_rans_lanes_decoder* d = new (std::nothrow) clc_rans_lanes_decoder();
+  if (!d) { clc_set_error("clc_rans_lanes_decoder_create: out of memory"); return nullptr; }
+  d->W = W;
+  d->words.resize((size_t)W);
+  d->x.resize((size_t)W * kLanes);
+  d->pos.assign((size_t)W, 2 * kLanes);
+  long at = 0;
+  for (int w = 0; w < W; ++w) {
+    auto& v = d->words[(size_t)w];
+    v.resize((size_t)lengths[w] / 4);
+    memcpy(v.data(), streams + at, (size_t)lengths[w]);
+    at += lengths[w];
+    for (int l = 0; l < kLanes; ++l) d->x[(size_t)w * kLanes + l] = (uint64_t)v[2 * l] | ((uint64_t)v[2 * l + 1] << 32);
+  }
+  return d;
+}
+
+extern "C" void clc_rans_lanes_decoder_destroy(clc_rans_lanes_decoder* d) { delete d; }
+
+extern "C" int clc_rans_lanes_decoder_state(const clc_rans_lanes_decoder* d, int w, uint64_t* x, long* pos) {
+  if (!d || !x || !pos || w < 0 || w >= d->W) { clc_set_error("clc_rans_lanes_decoder_state: bad args"); return -1; }
+  memcpy(x, d->x.data() + (size_t)w * kLanes, sizeof(uint64_t) * kLanes);
+  *pos = (long)d->pos[(size_t)w];
+  return 0;
+}
+
+extern "C" long clc_rans_lanes_decoder_decode(clc_rans_lanes_decoder* d, const int32_t* indexes, long n, const int32_t* cdfs, int cdf_stride, int n_rows,
+                                              const int32_t* cdf_sizes, const int32_t* offsets, int32_t* out) {
+  if (!d || n < 0 || (n > 0 && (!indexes || !out)) || !cdfs || !cdf_sizes || !offsets || cdf_stride < 2 || n_rows < 1) {
+    clc_set_error("clc_rans_lanes_decoder_decode: bad args");
+    return -1;
+  }
+  const LaneTables T = {cdfs, cdf_stride, n_rows, cdf_sizes, offsets};
+  if (!lanes_check_rows("clc_rans_lanes_decoder_decode", T, indexes, n)) return -1;
+  const long chunks = (n + kLanes - 1) / kLanes;
+  for (long q = 0; q < chunks; ++q) {
+    const int w = (int)(q % d->W);
+    const std::vector<uint32_t>& words = d->words[(size_t)w];
+    uint64_t* x = d->x.data() + (size_t)w * kLanes;
+    size_t& pos = d->pos[(size_t)w];
+    auto renorm = [&](uint64_t& xl) {
+      if (xl < kL) {
+        const uint32_t v = pos < words.size() ? words[pos] : 0u;   // truncated stream: feed zeros, never read outside it
+        pos++;
+        xl = (xl << 32) | v;
+      }
+    };
+    // per lane: nb < 0 — no escape; else the nibbles read so far
+    int32_t maxv[kLanes], nb[kLanes], base[kLanes];
+    uint32_t raw[kLanes];
+    const int active = (int)((q + 1) * kLanes <= n ? kLanes : n - q * kLanes);
+    for (int t = 0; t < 1 + kLanesMaxCount + kLanesMaxPayload; ++t) {
+      bool any = false;
+      for (int l = 0; l < active; ++l) {
+        const long j = q * kLanes + l;
+        if (t == 0) {
+          const int32_t ci = indexes[j];
+          const int32_t* cdf = cdfs + (long)ci * cdf_stride;
+          const int32_t size = cdf_sizes[ci];
+          maxv[l] = size - 2;
+          const uint32_t cf = (uint32_t)(x[l] & 0xFFFFu);
+          int32_t lo = 0, hi = size - 2;   // largest s <= max_value with cdf[s] <= cf (cdf[0] == 0; the row is strictly increasing)
+          while (lo < hi) {
+            const int32_t mid = (lo + hi + 1) >> 1;
+            if ((uint32_t)cdf[mid] <= cf) lo = mid; else hi = mid - 1;
+          }
+          const uint32_t start = (uint32_t)cdf[lo], freq = (uint32_t)(cdf[lo + 1] - cdf[lo]);
+          x[l] = (uint64_t)freq * (x[l] >> kPrec) + cf - start;
+          renorm(x[l]);
+          nb[l] = lo == maxv[l] ? 0 : -1;
+          base[l] = 2;
+          raw[l] = 0;
+          out[j] = lo;
+          any = true;
+          continue;
+        }
+        if (nb[l] < 0) continue;
+        if (t == 1 || (t == 2 && nb[l] == (int32_t)kBypassMax && base[l] == 2)) {   // the count: one nibble, a second one after a 15
+          const uint32_t v = (uint32_t)(x[l] & kBypassMax);
+          x[l] >>= kBypassBits;
+          renorm(x[l]);
+          nb[l] += (int32_t)v;
+          if (t == 2) base[l] = 3;
+          any = true;
+          continue;
+        }
+        const int k = t - base[l];
+        if (k < (nb[l] < kLanesMaxPayload ? nb[l] : kLanesMaxPayload)) {
+          const uint32_t v = (uint32_t)(x[l] & kBypassMax);
+          x[l] >>= kBypassBits;
+          renorm(x[l]);
+          if (k < 8) raw[l] |= v << (k * kBypassBits);
+          any = true;
+        }
+      }
+      if (!any) break;
+    }
+    for (int l = 0; l < active; ++l) {
+      const long j = q * kLanes + l;
+      uint32_t value = (uint32_t)out[j];   // (unsigned: other words than an encoder's may carry any payload, and must only wrap)
+      if (nb[l] >= 0) value = (raw[l] & 1u) ? ~(raw[l] >> 1) : (raw[l] >> 1) + (uint32_t)maxv[l];   // (-v - 1 == ~v)
+      out[j] = (int32_t)(value + (uint32_t)offsets[indexes[j]]);
+    }
+  }
+  return n;
+}

@@ -131,6 +131,17 @@ class ParamEntry(C.Structure):
     _fields_ = [("p", fp), ("g", fp), ("m", fp), ("v", fp), ("n", C.c_long)]
 
 
+RANS_LANES = 64                 # lanes of a wave stream of the "lanes" rANS format
+RANS_LANES_MAX_W = 16           # CLC_RANS_LANES_MAX_W
+RANS_LANES_MAX_SEGMENTS = 32    # CLC_RANS_LANES_MAX_SEGMENTS
+RANS_LANES_STATE_WORDS = 2 * RANS_LANES + 2   # sizeof(clc_rans_lanes_state) / 4
+RANS_LANES_ZERO_FREQ, RANS_LANES_OVERFLOW = -1, -2
+
+
+class LanesSegments(C.Structure):
+    _fields_ = [("P", C.c_int), ("n", C.c_int * RANS_LANES_MAX_SEGMENTS)]
+
+
 _i, _l, _f, _d, _sz = C.c_int, C.c_long, C.c_float, C.c_double, C.c_size_t
 _pp = C.POINTER(fp)
 
@@ -272,6 +283,14 @@ SIGNATURES = {
     "clc_gmm_finish": (_i, [fp, _i, _i, _i, fp, _i, _i, _i, _i, fp, _i, fp, _i, fp, fp, fp, _i, fp]),
     "clc_gmm_commit": (_i, [fp, _i, fp, _i, _i, _i, _i, fp, _i, fp]),
     "clc_gmm_decode_step": (_i, [fp, _i, _i, _i, fp, _i, _i, _i, _i, fp, fp, fp, _i, fp, _i, fp]),
+    "clc_rans_lanes_bound": (_l, [_l]),
+    "clc_rans_lanes_encode_host": (_l, [fp, fp, fp, _i, _i, fp, _i, _i, fp, fp, fp, _l, fp]),
+    "clc_rans_lanes_decoder_create": (fp, [fp, fp, _i]),
+    "clc_rans_lanes_decoder_decode": (_l, [fp, fp, _l, fp, _i, _i, fp, fp, fp]),
+    "clc_rans_lanes_decoder_state": (_i, [fp, _i, fp, C.POINTER(C.c_long)]),
+    "clc_rans_lanes_decoder_destroy": (None, [fp]),
+    "clc_rans_lanes_decode_step": (_i, [fp, _l, _i, _i, fp, _i, _i, fp, fp, fp, fp, fp, _i, fp, _l, fp]),
+    "clc_rans_lanes_encode": (_i, [fp, fp, _l, _i, LanesSegments, _i, fp, _i, _i, fp, fp, fp, fp, fp, fp]),
 }
 
 

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import ans, ops
+from .. import ans, lib, ops
 from ..entropy_models import GaussianConditional
 from ..layers import AttentionBlock, CheckerboardMaskedConv2d, Conv2d, conv, conv1x1, conv3x3, deconv
 from ..ops import ACT_NONE, ACT_RELU, CL
@@ -242,19 +242,55 @@ class Elic2022(CompressionModel):
         z_hat = self.entropy_bottleneck.decompress(z_strings, z.size()[-2:])
         return y, self._hyper_synthesis(z_hat), z_strings, z.size()[-2:]
 
+    @staticmethod
+    def _lanes_count(lanes, what):
+        """lanes=None: the one-stream format; else the number W of wave streams per image, refused by name outside 1 .. 16"""
+        if lanes is None:
+            return None
+        if isinstance(lanes, bool) or not isinstance(lanes, int) or not 1 <= lanes <= ans.LANES_MAX_W:
+            raise ValueError(f"Elic2022.{what}: lanes must be between 1 and {ans.LANES_MAX_W} wave streams per image (got {lanes!r})")
+        return lanes
+
+    def _lanes_segments(self, H, W):
+        """the lanes stream's segments: the 2 K passes in scctx_order, n = pixels of the pass x channels of the group"""
+        anchors, others = ckbd_pixels(H, W)
+        return [cnt * c for c in self.groups for cnt in (len(anchors), len(others))]
+
+    def _lanes_encode_device(self, sym, idx, segments, W):
+        """int32 [B, T] device symbols / indexes in stream order -> per image its lanes string: one clc_rans_lanes_encode for the batch,
+        then two device -> host copies (the [B, W] results, the packed words)."""
+        gc = self.gaussian_conditional
+        out, _, result = ops.rans_lanes_encode(sym, idx, segments, W, (gc._quantized_cdf, gc._cdf_length, gc._offset))
+        res = result.cpu().numpy()
+        for b, w in zip(*np.nonzero(res[..., 0] < 0)):
+            why = "a zero-frequency symbol" if res[b, w, 0] == lib.RANS_LANES_ZERO_FREQ else "its region overflowed"
+            raise ValueError(f"compress: image {b}, wave stream {w}: {why} (clc_rans_lanes_encode code {int(res[b, w, 0])})")
+        spans = res.reshape(-1, 2)
+        words = torch.cat([out[f:f + n] for f, n in spans]).cpu().numpy().view(np.uint32)
+        ends = np.cumsum(spans[:, 1])
+        streams = [words[e - n:e].astype("<u4").tobytes() for e, n in zip(ends, spans[:, 1])]
+        return [ans.lanes_pack(streams[b * W:(b + 1) * W]) for b in range(res.shape[0])]
+
     @torch.no_grad()
-    def compress(self, x):
+    def compress(self, x, lanes=None):
+        """lanes=None: the one-stream format.  lanes=W: THE LANES STREAM (clc_amd/ans.py: lanes_pack; include/clc_hip.h), W wave streams
+        of 64 rANS lanes per image, encoded on the device, and "lanes": W in the result; pass the same W to decompress."""
+        Wn = self._lanes_count(lanes, "compress")
         y, params, z_strings, z_size = self._code_inputs(x)
-        cdf, ln, off = self.gaussian_conditional.host_tables()
+        if Wn is None:
+            cdf, ln, off = self.gaussian_conditional.host_tables()
         syms, idxs, _ = self._scctx_encode(y, params)
         B, _, H, W = y.shape
         na, nn_, pix = self._scctx_lists(H, W, y.device)
         order = (pix[:, 0].long() * W + pix[:, 1].long())   # raster positions in the stream's pixel order: anchors, then non-anchors
         flat = lambda ts: torch.cat([t.index_select(1, order).reshape(B, -1) for t in ts], 1)
-        both = torch.stack((flat(syms), flat(idxs))).cpu().numpy()   # the one device -> host copy: [2, B, H*W*M] in stream order
-        y_strings = [ans.encode(np.ascontiguousarray(both[0, i]), np.ascontiguousarray(both[1, i]), cdf, ln, off) for i in range(B)]
         from ..codec import kernel_config
 
+        if Wn is not None:   # the flat buffers stay on the device
+            y_strings = self._lanes_encode_device(flat(syms), flat(idxs), self._lanes_segments(H, W), Wn)
+            return {"strings": [y_strings, z_strings], "shape": z_size, "kernel_config": kernel_config(), "lanes": Wn}
+        both = torch.stack((flat(syms), flat(idxs))).cpu().numpy()   # the one device -> host copy: [2, B, H*W*M] in stream order
+        y_strings = [ans.encode(np.ascontiguousarray(both[0, i]), np.ascontiguousarray(both[1, i]), cdf, ln, off) for i in range(B)]
         return {"strings": [y_strings, z_strings], "shape": z_size, "kernel_config": kernel_config()}
 
     @torch.no_grad()
@@ -306,12 +342,150 @@ class Elic2022(CompressionModel):
                 ops.ar_commit(sym_dev, ws["gp"], c, px, yhk)
         return y_hat
 
+    def _lanes_parse(self, y_strings, W):
+        """-> per image the W wave streams of its lanes string; a header that disagrees with the caller's W is refused"""
+        subs = []
+        for b, blob in enumerate(y_strings):
+            got = ans.lanes_unpack(blob)
+            if len(got) != W:
+                raise ValueError(f"decompress: lanes = {W}, but the header of image {b} says {len(got)} wave streams")
+            subs.append(got)
+        return subs
+
     @torch.no_grad()
-    def decompress(self, strings, shape):
+    def _scctx_decode_lanes(self, subs, params, device_coder=True):
+        """The 2 K passes over lanes streams (subs[b][w]: bytes) -> (y_hat, state).
+        device_coder: one pinned upload of every wave stream's states, spans and words, then per non-empty pass the chain,
+        ar_finish_decode, one clc_rans_lanes_decode_step and ar_commit — stream-ordered launches only, no download, no synchronize, no
+        per-image loop; state is the device's int32 [B, W, 130] (64 x (x low, x high), pos, pad) as the last pass left it.
+        Host coder: the hop per pass of _scctx_decode with one ans.LanesDecoder per image; state is the list of decoders."""
+        params = params.contiguous(memory_format=CL)
+        dev = params.device
+        B, M, (H, W) = params.shape[0], self.M, params.shape[2:]
+        if len(subs) != B:
+            raise ValueError(f"decompress: {len(subs)} y streams for {B} z streams")
+        Wn = len(subs[0])
+        table = self.gaussian_conditional.scale_table
+        na, nn_, pix = self._scctx_lists(H, W, dev)
+        rows = B * max(na, nn_)
+        ws = self._scctx_workspace(rows, dev)
+        filt = self._scctx_filters()
+        y_hat = torch.zeros((B, M, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
+        cmax = max(self.groups)
+        if device_coder:
+            gc = self.gaussian_conditional
+            tables = (gc._quantized_cdf, gc._cdf_length, gc._offset)
+            flat = [np.frombuffer(s, dtype="<u4") for img in subs for s in img]
+            counts = np.array([w.size for w in flat], dtype=np.int64)
+            firsts = np.concatenate(([0], np.cumsum(counts)[:-1]))
+            n_words = int(counts.sum())
+            if n_words >= 1 << 31:
+                raise ValueError(f"decompress: {n_words} stream words in one batch; the spans are int32")
+            # one pinned buffer, one upload: the states, the spans, the words
+            SW, n_st = ops.RANS_LANES_STATE_WORDS, B * Wn
+            host = torch.empty(((SW + 2) * n_st + n_words,), dtype=torch.int32).pin_memory()
+            h = host.numpy().view(np.uint32)
+            st = h[:SW * n_st].reshape(n_st, SW)
+            for i, w in enumerate(flat):
+                st[i, :2 * ans.LANES] = w[:2 * ans.LANES]
+            st[:, 2 * ans.LANES], st[:, 2 * ans.LANES + 1] = 2 * ans.LANES, 0
+            sp = h[SW * n_st:(SW + 2) * n_st].reshape(n_st, 2)
+            sp[:, 0], sp[:, 1] = firsts, counts
+            h[(SW + 2) * n_st:] = np.concatenate(flat)
+            d = torch.empty((host.numel(),), device=dev, dtype=torch.int32)
+            d.copy_(host, non_blocking=True)
+            state, spans, words = d[:SW * n_st].view(B, Wn, SW), d[SW * n_st:(SW + 2) * n_st].view(B, Wn, 2), d[(SW + 2) * n_st:]
+            idx_dev = torch.empty((rows * cmax,), device=dev, dtype=torch.int32)
+            sym_dev = torch.empty((rows * cmax,), device=dev, dtype=torch.int32)
+        else:
+            cdf, ln, off = self.gaussian_conditional.host_tables()
+            decoders = [ans.LanesDecoder(img) for img in subs]
+            idx_host = torch.empty((rows * cmax,), dtype=torch.int32).pin_memory()
+            sym_host = torch.empty((rows * cmax,), dtype=torch.int32).pin_memory()
+            stream = torch.cuda.current_stream(dev)
+        for k, (s, c) in enumerate(zip(self.starts, self.groups)):
+            yhk = y_hat[:, s:s + c]
+            ch = self._channel_ctx(k, y_hat)
+            sp_map = torch.zeros((B, 2 * c, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
+            for lo, cnt in ((0, na), (na, nn_)):
+                if not cnt:
+                    continue
+                px = pix[lo:lo + cnt]
+                if lo:
+                    sp_map = self.spatial_context[k](yhk)
+                n = B * cnt
+                self._scctx_chain(px, B, H, W, params, sp_map, ch, ws, filt[k])
+                if device_coder:
+                    ib, sb = idx_dev[:n * c].view(n, c), sym_dev[:n * c].view(n, c)
+                    ops.ar_finish_decode(ws["gp"], c, px, B, H, W, table, ib)
+                    ops.rans_lanes_decode_step(ib, cnt * c, tables, words, spans, state, sb)
+                    ops.ar_commit(sb, ws["gp"], c, px, yhk)
+                    continue
+                ib = torch.empty((n, c), device=dev, dtype=torch.int32)
+                sb = torch.empty((n, c), device=dev, dtype=torch.int32)
+                ih, sh = idx_host[:n * c].view(n, c), sym_host[:n * c].view(n, c)
+                idx_np, sym_np = ih.numpy(), sh.numpy()
+                ops.ar_finish_decode(ws["gp"], c, px, B, H, W, table, ib)
+                ih.copy_(ib, non_blocking=True)
+                stream.synchronize()   # (also: the previous pass's symbol upload has left sym_host)
+                for b, dd in enumerate(decoders):
+                    sym_np[b * cnt:(b + 1) * cnt] = dd.decode(idx_np[b * cnt:(b + 1) * cnt].reshape(-1), cdf, ln, off).reshape(cnt, c)
+                sb.copy_(sh, non_blocking=True)
+                ops.ar_commit(sb, ws["gp"], c, px, yhk)
+        # (the pinned pages stay pinned until the upload has run: the caching host allocator holds them back until then)
+        return y_hat, (state if device_coder else decoders)
+
+    @staticmethod
+    def _lanes_check(state, subs):
+        """A wave stream decoded to its end leaves every lane at x == 2^31 and pos == its word count (the coder's end-state property);
+        anything else raises, naming per image every wave stream that did not.  (A wrong symbol enters the context of the passes after
+        it, so a damaged wave stream usually takes the image's others out of step with it: the list holds the damaged one, it cannot
+        single it out.)  state: the device's [B, W, 130] tensor — ONE download — or the host coder's list of decoders."""
+        if isinstance(state, torch.Tensor):
+            st = state.cpu().numpy().view(np.uint32)   # the one download of the device path
+            L = 2 * ans.LANES
+            ends = lambda b, w: ((st[b, w, 0:L:2].astype(np.uint64) | (st[b, w, 1:L:2].astype(np.uint64) << np.uint64(32))), int(st[b, w, L]))
+        else:
+            ends = lambda b, w: state[b].state(w)
+        bad = []
+        for b, img in enumerate(subs):
+            off = []
+            for w, blob in enumerate(img):
+                x, pos = ends(b, w)
+                if not (x == np.uint64(1 << 31)).all() or pos != len(blob) // 4:
+                    off.append((w, int((x != np.uint64(1 << 31)).sum()), pos))
+            if off:
+                w, lanes_off, pos = off[0]
+                bad.append(f"image {b}: wave streams {[o[0] for o in off]} did not decode to their end (wave stream {w}: {lanes_off} of 64 lanes "
+                           f"not at 2^31, {pos} of {len(img[w]) // 4} words consumed)")
+        if bad:
+            raise ValueError("decompress: " + "; ".join(bad) + ": the stream is corrupt, truncated or belongs to other parameters")
+
+    @torch.no_grad()
+    def decompress(self, strings, shape, lanes=None, device_coder=True, check=True):
+        """lanes=None: the one-stream format.  lanes=W: the lanes stream of compress(x, lanes=W); its headers are parsed on the host before
+        any device work.  device_coder=True decodes it on the device: no device -> host copy and no synchronize between the upload of the
+        streams and the finished y_hat; check=True adds ONE download of the final coder states, after the synthesis transform has been
+        launched, and raises ValueError naming the image and the wave streams that did not end where a whole stream ends — a check
+        against streams out of step or cut short, NOT a checksum: a changed bit inside an escape's raw payload decodes to another symbol
+        and ends clean.  device_coder=False runs the same format on the host coder (ans.LanesDecoder), a hop per pass: the oracle."""
+        Wn = self._lanes_count(lanes, "decompress")
         assert isinstance(strings, (list, tuple)) and len(strings) == 2
+        if Wn is None:
+            for b, blob in enumerate(strings[0]):
+                if bytes(blob[:4]) == ans.LANES_MAGIC:
+                    raise ValueError(f"decompress: the y string of image {b} is a lanes stream ({ans.LANES_MAGIC!r}); pass lanes= (its header "
+                                     f"says {blob[4] if len(blob) > 4 else '?'} wave streams)")
+            z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
+            y_hat = self._scctx_decode(strings[0], self._hyper_synthesis(z_hat))
+            return {"x_hat": self._synthesis(y_hat).clamp_(0, 1)}
+        subs = self._lanes_parse(strings[0], Wn)
         z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
-        y_hat = self._scctx_decode(strings[0], self._hyper_synthesis(z_hat))
-        return {"x_hat": self._synthesis(y_hat).clamp_(0, 1)}
+        y_hat, state = self._scctx_decode_lanes(subs, self._hyper_synthesis(z_hat), device_coder)
+        x_hat = self._synthesis(y_hat).clamp_(0, 1)
+        if check:
+            self._lanes_check(state, subs)
+        return {"x_hat": x_hat}
 
     def update(self, scale_table=None, force=False):
         if scale_table is None:

@@ -2981,3 +2981,112 @@ def gmm_decode_step(gp, N, K, pix, words, spans, state, y_hat):
         raise ValueError(f"gmm_decode_step: state must be an 8-byte aligned int32 [B, S, 4] = {(B, S, 4)} tensor (got {tuple(state.shape)})")
     _lib.check(_L().clc_gmm_decode_step(gpp, ldg, N, K, pp, P, B, H, W, words.data_ptr(), spans.data_ptr(), state.data_ptr(), S, hp, ldh,
                                         _stream()), "clc_gmm_decode_step")
+
+
+# ------------------------------------------------------------------- lane-interleaved rANS coder on the device (csrc/rans_lanes.hip)
+RANS_LANES_MAX_W = _lib.RANS_LANES_MAX_W
+RANS_LANES_STATE_WORDS = _lib.RANS_LANES_STATE_WORDS
+
+
+def _lanes_tables(tables, who):
+    """(cdfs int32 [rows, stride], cdf_sizes int32 [rows], offsets int32 [rows]) on the device -> their pointers, stride, rows"""
+    cdf, ln, off = tables
+    for t, what in ((cdf, "cdfs"), (ln, "cdf_sizes"), (off, "offsets")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{who}: {what} must be a contiguous int32 device tensor")
+    if cdf.dim() != 2 or cdf.shape[0] < 1 or cdf.shape[1] < 2 or ln.numel() != cdf.shape[0] or off.numel() != cdf.shape[0]:
+        raise ValueError(f"{who}: cdfs must be [rows >= 1, stride >= 2] with one cdf size and one offset per row (got {tuple(cdf.shape)}, "
+                         f"{ln.numel()}, {off.numel()})")
+    return cdf.data_ptr(), int(cdf.shape[1]), int(cdf.shape[0]), ln.data_ptr(), off.data_ptr()
+
+
+def _lanes_w(W, who):
+    if isinstance(W, bool) or not isinstance(W, int) or not 1 <= W <= RANS_LANES_MAX_W:
+        raise ValueError(f"{who}: W must be between 1 and {RANS_LANES_MAX_W} wave streams (got {W!r})")
+    return W
+
+
+def rans_lanes_decode_step(indexes, n, tables, words, spans, state, symbols):
+    """clc_rans_lanes_decode_step: the next segment of n symbols per image of the lanes stream, decoded on the device for the whole batch.
+    indexes / symbols: contiguous int32 device tensors of B equal image blocks of at least n elements (ar_finish_decode's dense rows and
+    what ar_commit takes); tables: (cdfs, cdf_sizes, offsets) int32 on the device; words int32 [m] (every wave stream's 32-bit words),
+    spans int32 [B, W, 2] (first word, word count), state int32 [B, W, RANS_LANES_STATE_WORDS] (64 x (x low, x high), pos, pad: read,
+    advanced and written back).  No copy to the host, no sync: the caller keeps every span inside ``words``."""
+    for t, what in ((indexes, "indexes"), (symbols, "symbols"), (words, "words"), (spans, "spans"), (state, "state")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"rans_lanes_decode_step: {what} must be a contiguous int32 device tensor")
+    if spans.dim() != 3 or spans.shape[2] != 2 or words.dim() != 1 or words.numel() < 1:
+        raise ValueError(f"rans_lanes_decode_step: words must be int32 [m >= 1] and spans int32 [B, W, 2] (got {tuple(words.shape)}, {tuple(spans.shape)})")
+    B, W = int(spans.shape[0]), _lanes_w(int(spans.shape[1]), "rans_lanes_decode_step")
+    if tuple(state.shape) != (B, W, RANS_LANES_STATE_WORDS):
+        raise ValueError(f"rans_lanes_decode_step: state must be int32 [B, W, {RANS_LANES_STATE_WORDS}] = {(B, W, RANS_LANES_STATE_WORDS)} "
+                         f"(got {tuple(state.shape)})")
+    n = int(n)
+    if B < 1 or n < 0 or indexes.numel() % B or symbols.numel() % B or indexes.numel() // B < n or symbols.numel() // B < n:
+        raise ValueError(f"rans_lanes_decode_step: indexes and symbols must hold B = {B} equal image blocks of at least n = {n} elements "
+                         f"(got {indexes.numel()} and {symbols.numel()} elements)")
+    cp, stride, rows, lp, op = _lanes_tables(tables, "rans_lanes_decode_step")
+    if n == 0:   # an empty segment contributes nothing (and an empty tensor has no pointer to hand over)
+        return symbols
+    _lib.check(_L().clc_rans_lanes_decode_step(indexes.data_ptr(), indexes.numel() // B, n, B, cp, stride, rows, lp, op, words.data_ptr(),
+                                               spans.data_ptr(), state.data_ptr(), W, symbols.data_ptr(), symbols.numel() // B, _stream()),
+               "clc_rans_lanes_decode_step")
+    return symbols
+
+
+def rans_lanes_regions(segments, W, B):
+    """-> int32 [B, W, 2] (first word, capacity): back-to-back regions of 128 + 10 n_w words, which hold every wave stream"""
+    import numpy as np
+
+    from .ans import lanes_wave_symbols
+
+    caps = np.array([128 + 10 * n for n in lanes_wave_symbols(segments, W)], dtype=np.int64)
+    firsts = np.concatenate(([0], np.cumsum(np.tile(caps, B))[:-1]))
+    if int(firsts[-1] + caps[-1]) >= 1 << 31:
+        raise ValueError(f"rans_lanes_regions: {int(firsts[-1] + caps[-1])} words of regions in one batch; the regions are int32")
+    return np.stack((firsts, np.tile(caps, B)), axis=1).reshape(B, W, 2).astype(np.int32)
+
+
+def rans_lanes_encode(symbols, indexes, segments, W, tables, out=None, regions=None):
+    """clc_rans_lanes_encode: a whole batch's lanes streams in one launch.  symbols / indexes: contiguous int32 device tensors [B, T] in
+    stream order; segments: the P <= 32 segment lengths (host ints, sum <= T); tables as for rans_lanes_decode_step.  out: int32 [m] device
+    words and regions: HOST int32 [B, W, 2] (first word, capacity) — by default rans_lanes_regions and a buffer of their size.  Every
+    region is checked to lie inside out before the launch.
+    -> (out, regions, result): result int32 [B, W, 2] on the device, (first word, word count) of each wave stream or
+    (RANS_LANES_ZERO_FREQ / RANS_LANES_OVERFLOW, 0)."""
+    import numpy as np
+
+    W = _lanes_w(W, "rans_lanes_encode")
+    for t, what in ((symbols, "symbols"), (indexes, "indexes")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 2:
+            raise ValueError(f"rans_lanes_encode: {what} must be a contiguous int32 [B, T] device tensor")
+    if symbols.shape != indexes.shape or symbols.shape[0] < 1:
+        raise ValueError(f"rans_lanes_encode: symbols and indexes must have one shape [B >= 1, T] (got {tuple(symbols.shape)}, {tuple(indexes.shape)})")
+    B, T = int(symbols.shape[0]), int(symbols.shape[1])
+    segments = [int(n) for n in segments]
+    if len(segments) > _lib.RANS_LANES_MAX_SEGMENTS or any(n < 0 for n in segments) or sum(segments) > T:
+        raise ValueError(f"rans_lanes_encode: at most {_lib.RANS_LANES_MAX_SEGMENTS} segments of non-negative length adding up to at most T = {T} "
+                         f"(got {segments})")
+    if regions is None:
+        regions = rans_lanes_regions(segments, W, B)
+    regions = np.ascontiguousarray(np.asarray(regions, dtype=np.int32))
+    if regions.shape != (B, W, 2):
+        raise ValueError(f"rans_lanes_encode: regions must be int32 [B, W, 2] = {(B, W, 2)} (got {regions.shape})")
+    if out is None:
+        out = torch.empty((int((regions[..., 0].astype(np.int64) + regions[..., 1]).max()),), device=symbols.device, dtype=torch.int32)
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or not out.is_cuda or not out.is_contiguous() or out.dim() != 1:
+        raise ValueError("rans_lanes_encode: out must be a contiguous int32 [m] device tensor")
+    ends = regions[..., 0].astype(np.int64) + regions[..., 1]
+    if (regions < 0).any() or int(ends.max()) > out.numel():
+        raise ValueError(f"rans_lanes_encode: every region must lie inside out ({out.numel()} words; the regions reach word {int(ends.max())}, "
+                         f"their smallest entry is {int(regions.min())})")
+    cp, stride, rows, lp, op = _lanes_tables(tables, "rans_lanes_encode")
+    segs = _lib.LanesSegments()
+    segs.P = len(segments)
+    for i, n in enumerate(segments):
+        segs.n[i] = n
+    reg_dev = torch.from_numpy(regions).to(symbols.device)
+    result = torch.empty((B, W, 2), device=symbols.device, dtype=torch.int32)
+    _lib.check(_L().clc_rans_lanes_encode(symbols.data_ptr(), indexes.data_ptr(), T, B, segs, W, cp, stride, rows, lp, op, out.data_ptr(),
+                                          reg_dev.data_ptr(), result.data_ptr(), _stream()), "clc_rans_lanes_encode")
+    return out, regions, result

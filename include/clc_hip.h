@@ -859,6 +859,86 @@ int clc_gmm_decode_step(const float* gp, int ldg, int N, int K, const int32_t* p
                         const int32_t* spans /* [B][S][2]: first word, word count */, clc_gmm_substream_state* state /* [B][S] */, int S,
                         float* y_hat, int ldh, clc_stream_t stream);
 
+/* ---- the lane-interleaved ("lanes") rANS stream: host coder (csrc/rans_host.cpp) and device coder (csrc/rans_lanes.hip) ----
+ * A table-coded stream (clc_rans_encode's tables: cdfs [n_rows][cdf_stride], cdf_sizes, offsets) re-cut so that one GPU wave codes 64
+ * symbols per step.  An image's symbols are P SEGMENTS of n_p symbols (a model's parallel passes: inside a segment every index is known
+ * before the first symbol is decoded), coded by W WAVE STREAMS, 1 <= W <= 16, of 64 rANS LANES each.
+ *   Placement.  Symbol j of a segment lies in chunk q = j / 64 and lane l = j % 64; chunk q belongs to wave q % W.  A wave takes its
+ *   chunks of a segment in ascending q, one chunk per ROUND, and its rounds run on across the segments.  In a segment's last chunk the
+ *   lanes with j >= n_p are idle: no state change, no word.  A segment with n_p = 0 contributes nothing.
+ *   Per lane the arithmetic is clc_rans_encode's / clc_rans_decoder_decode's: 64-bit state, L = 2^31, 32-bit words, 16-bit precision;
+ *   a symbol outside its row is the row's tail symbol followed by the 4-bit bypass escape — here always ONE count nibble nb <= 8 and
+ *   then the nb payload nibbles of raw, LSB first (raw = -2 v - 1 below the row, 2 (v - max_value) at or above it).
+ *   A wave stream is an array of 32-bit words DEFINED BY THE DECODER'S READS.  It starts with the 64 lane states, 128 words: lane l's low
+ *   word at 2 l, its high word at 2 l + 1; pos starts at 128.  Per round the wave runs SUB-STEPS t = 0, 1, 2, ...; in sub-step t every
+ *   active lane that has a t-th operation performs it:
+ *     operation 0   cf = x & 0xFFFF; s = the largest s <= max_value with cdf[s] <= cf; x = (cdf[s + 1] - cdf[s]) * (x >> 16) + cf - cdf[s];
+ *     operations 1 ..   only for a lane with s == max_value (the tail): a count nibble (v = x & 15, x >>= 4; a second one, added, if the
+ *                   first was 15 — an encoder never writes one), then min(count, 16) payload nibbles, the first 8 of them kept as raw;
+ *                   the symbol is -(raw >> 1) - 1 if raw is odd, else (raw >> 1) + max_value;
+ *     every operation ends with the renorm: if x < 2^31, x = x << 32 | word[pos'] (zero at or past the stream's end).
+ *   WITHIN A SUB-STEP THE LANES THAT RENORMALISE TAKE THE NEXT WORDS IN ASCENDING LANE ORDER (lane l reads word pos + #{renormalising
+ *   lanes below l}; then pos += their number).  The round ends when no lane has an operation left — at most 1 + 2 + 16 sub-steps.
+ *   The decoded symbol is the value + offsets[index].
+ *   The encoder is the exact reverse: every lane starts at x = 2^31; rounds descending, sub-steps descending, lanes descending, words
+ *   written backward (enc_put / enc_put_bits: at most one word per operation, at most 10 operations per symbol); then the 64 states.
+ *   So a wave stream of n_w symbols never exceeds 128 + 10 n_w words (clc_rans_lanes_bound, in bytes), and a stream decoded to its end
+ *   leaves every lane at x == 2^31 and pos == the word count.  (Overhead against the one stream of clc_rans_encode: 512 W bytes of
+ *   states, plus the container's header — clc_amd/ans.py: lanes_pack.)
+ *
+ * HOST (rans_host.cpp), the oracle and the fallback:
+ * clc_rans_lanes_encode_host  one image: symbols / indexes in stream order (the segments back to back), seg_len[P] -> the W wave streams
+ *                    back to back in out, lengths[w] = bytes of stream w; returns the total bytes.  out_cap >= the sum over the waves of
+ *                    clc_rans_lanes_bound(n_w).  Refused by name: W outside 1 .. 16, a negative segment length, an index outside the
+ *                    table, a bad cdf size (below 2 or above cdf_stride), a zero-frequency symbol, a buffer too small.
+ * clc_rans_lanes_decoder_create  from the W wave streams back to back (lengths[w] bytes each; copied).  Refused by name: W outside
+ *                    1 .. 16, a stream shorter than 512 bytes or not a multiple of 4.
+ * clc_rans_lanes_decoder_decode  the NEXT SEGMENT of n symbols -> out[n]; returns n.  The rows are checked (index outside the table, bad
+ *                    cdf size: refused by name) before any state changes.  On a truncated stream the decoder feeds zeros and never reads
+ *                    outside the stream; every loop is bounded.
+ * clc_rans_lanes_decoder_state   wave w's 64 lane states and pos (words consumed so far).
+ *
+ * DEVICE (rans_lanes.hip): one wave per (image, wave stream), lane l of the wave is lane l of the stream; who takes / writes the next
+ * words of a sub-step is a __ballot of the renormalising lanes and a prefix popcount.
+ * clc_rans_lanes_decode_step  ONE segment for the whole batch: indexes[b * ld_idx + j], j < n -> symbols[b * ld_sym + j] (offset added:
+ *                    what clc_ar_commit takes).  Wave stream (b, w) is words[first .. first + count) with (first, count) =
+ *                    spans[(b * W + w) * 2 ..]; state[b * W + w] (the 64 x and pos) is read, advanced and written back, so a stream's
+ *                    segments are decoded by consecutive calls.  A fresh state has x[l] = word 2 l | word 2 l + 1 << 32 and pos = 128.
+ *                    An index outside the table is clamped into it and a cdf size into 2 .. cdf_stride; no word outside
+ *                    [first, first + count) is read (a negative first or count reads nothing) and a word at or past the count is zero;
+ *                    every loop is bounded (the search by the row, the escape by 2 count and 16 payload nibbles).  On every stream the
+ *                    encoders produce, symbols and final states are the host decoder's; other words give wrong symbols and nothing
+ *                    worse.  The caller keeps first + count inside the words buffer.  n == 0 launches nothing.
+ * clc_rans_lanes_encode  a whole batch in one launch: symbols / indexes [b * ld + i] in stream order, the segment lengths by value
+ *                    (P <= 32).  Wave (b, w) writes backward into the region out[first .. first + capacity) with (first, capacity) =
+ *                    regions[(b * W + w) * 2 ..] (128 + 10 n_w words hold every stream) and leaves result[(b * W + w) * 2 ..] =
+ *                    (first word of its stream, word count) — or (CLC_RANS_LANES_ZERO_FREQ, 0) / (CLC_RANS_LANES_OVERFLOW, 0).  Nothing
+ *                    is ever written outside the region; an index outside the table is clamped.  The words are the host encoder's.
+ * Both kernels: stream-ordered, graph-capturable, allocation- and sync-free; no LDS, no barrier, no atomics, no wave waits on another.
+ * Bad arguments are refused by name before any launch. */
+#define CLC_RANS_LANES_MAX_W 16
+#define CLC_RANS_LANES_MAX_SEGMENTS 32
+#define CLC_RANS_LANES_ZERO_FREQ (-1)
+#define CLC_RANS_LANES_OVERFLOW (-2)
+typedef struct { uint64_t x[64]; uint32_t pos; uint32_t pad; } clc_rans_lanes_state;   /* 520 bytes, DEVICE memory */
+typedef struct { int P; int n[CLC_RANS_LANES_MAX_SEGMENTS]; } clc_rans_lanes_segments;
+long clc_rans_lanes_bound(long n_w);   /* bytes */
+long clc_rans_lanes_encode_host(const int32_t* symbols, const int32_t* indexes, const int32_t* seg_len, int P, int W, const int32_t* cdfs,
+                                int cdf_stride, int n_rows, const int32_t* cdf_sizes, const int32_t* offsets, uint8_t* out, long out_cap,
+                                int32_t* lengths /* [W] bytes */);                                  /* HOST */
+typedef struct clc_rans_lanes_decoder clc_rans_lanes_decoder;
+clc_rans_lanes_decoder* clc_rans_lanes_decoder_create(const uint8_t* streams, const int32_t* lengths /* [W] bytes */, int W);   /* HOST, copies */
+long clc_rans_lanes_decoder_decode(clc_rans_lanes_decoder* d, const int32_t* indexes, long n, const int32_t* cdfs, int cdf_stride, int n_rows,
+                                   const int32_t* cdf_sizes, const int32_t* offsets, int32_t* out);   /* HOST */
+int clc_rans_lanes_decoder_state(const clc_rans_lanes_decoder* d, int w, uint64_t* x /* [64] */, long* pos);
+void clc_rans_lanes_decoder_destroy(clc_rans_lanes_decoder* d);
+int clc_rans_lanes_decode_step(const int32_t* indexes, long ld_idx, int n, int B, const int32_t* cdfs, int cdf_stride, int n_rows,
+                               const int32_t* cdf_sizes, const int32_t* offsets, const uint32_t* words, const int32_t* spans /* [B][W][2] */,
+                               clc_rans_lanes_state* state /* [B][W] */, int W, int32_t* symbols, long ld_sym, clc_stream_t stream);
+int clc_rans_lanes_encode(const int32_t* symbols, const int32_t* indexes, long ld, int B, clc_rans_lanes_segments segs, int W,
+                          const int32_t* cdfs, int cdf_stride, int n_rows, const int32_t* cdf_sizes, const int32_t* offsets,
+                          uint32_t* out, const int32_t* regions /* [B][W][2] */, int32_t* result /* [B][W][2] */, clc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
