@@ -9,6 +9,7 @@ Python lists (reference style) or int32 numpy arrays (zero-copy fast path used b
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 
@@ -62,12 +63,68 @@ def encode_direct(triples) -> bytes:
     return buf[:nb].tobytes()
 
 
+class _Container(NamedTuple):
+    """A multi-stream container: one image's independently decodable rANS streams as one string, little endian:
+
+        magic | u8 count | u8 lane byte | 2 x u8 0 | count x u32 byte length | the streams, back to back
+
+    Every stream is whole 32-bit words and at least ``least`` bytes, the coder state it starts with."""
+    name: str       # of the public pair: name_pack / name_unpack
+    magic: bytes
+    letter: str     # the count, in messages
+    noun: str       # one stream, in messages
+    most: int       # streams per image
+    least: int      # bytes of a stream
+    lanes: int      # what header byte 5 must be: the rANS lanes of a stream, or 0 for a third pad byte
+
+
+def stream_count(fmt, n, who, name=None):
+    """-> the int n, the number of streams of one image in container fmt; refused by name (the caller's, or the format's letter)"""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= fmt.most:
+        raise ValueError(f"{who}: {name or fmt.letter} must be between 1 and {fmt.most} {fmt.noun}s (got {n!r})")
+    return int(n)
+
+
+def _pack(fmt, streams) -> bytes:
+    who = fmt.name + "_pack"
+    streams = [bytes(s) for s in streams]
+    stream_count(fmt, len(streams), who)
+    for i, s in enumerate(streams):
+        if len(s) < fmt.least or len(s) % 4:
+            raise ValueError(f"{who}: {fmt.noun} {i} has {len(s)} bytes; a length must be a multiple of 4 and at least {fmt.least}")
+    head = fmt.magic + bytes([len(streams), fmt.lanes, 0, 0]) + np.array([len(s) for s in streams], dtype="<u4").tobytes()
+    return head + b"".join(streams)
+
+
+def _unpack(fmt, blob) -> list:
+    who = fmt.name + "_unpack"
+    blob = bytes(blob)
+    if len(blob) < 8 or blob[:4] != fmt.magic:
+        raise ValueError(f"{who}: bad magic {blob[:4]!r} (a {fmt.name} stream starts with {fmt.magic!r})")
+    n = stream_count(fmt, blob[4], who)
+    pad = 6 if fmt.lanes else 5   # the first pad byte
+    if fmt.lanes and blob[5] != fmt.lanes:
+        raise ValueError(f"{who}: the lane byte must be {fmt.lanes} (got {blob[5]})")
+    if blob[pad:8] != bytes(8 - pad):
+        raise ValueError(f"{who}: non-zero pad byte in the header ({blob[pad:8].hex()})")
+    if len(blob) < 8 + 4 * n:
+        raise ValueError(f"{who}: the lengths do not add up to the blob ({len(blob)} bytes end inside the header of {fmt.letter} = {n})")
+    lengths = [int(m) for m in np.frombuffer(blob, dtype="<u4", count=n, offset=8)]
+    for i, m in enumerate(lengths):
+        if m < fmt.least or m % 4:
+            raise ValueError(f"{who}: {fmt.noun} {i} has length {m}; a length must be a multiple of 4 and at least {fmt.least}")
+    if 8 + 4 * n + sum(lengths) != len(blob):
+        raise ValueError(f"{who}: the lengths do not add up to the blob (header {8 + 4 * n} + {sum(lengths)} != {len(blob)} bytes)")
+    out, at = [], 8 + 4 * n
+    for m in lengths:
+        out.append(blob[at:at + m])
+        at += m
+    return out
+
+
 SPLIT_MAGIC = b"CGS1"
 SPLIT_MAX = 64   # sub-streams per image: one wave each on the device decoder (clc_gmm_decode_step)
-
-
-def _split_length_ok(n):
-    return n >= 8 and n % 4 == 0
+SPLIT_STREAM = _Container("split", SPLIT_MAGIC, "S", "sub-stream", SPLIT_MAX, 8, 0)
 
 
 def split_pack(streams) -> bytes:
@@ -78,55 +135,18 @@ def split_pack(streams) -> bytes:
     Every sub-stream is a whole stream of ``encode_direct`` (32-bit words, at least the two of its final state).  Overhead: 8 + 4 S
     bytes of header plus the 8-byte final state of each sub-stream, 8 + 12 S bytes — 200 per image at S = 16 (the one stream it
     replaces carried one such state)."""
-    streams = [bytes(s) for s in streams]
-    S = len(streams)
-    if not 1 <= S <= SPLIT_MAX:
-        raise ValueError(f"split_pack: S must be between 1 and {SPLIT_MAX} sub-streams (got {S})")
-    for i, s in enumerate(streams):
-        if not _split_length_ok(len(s)):
-            raise ValueError(f"split_pack: sub-stream {i} has {len(s)} bytes; a length must be a multiple of 4 and at least 8")
-    head = SPLIT_MAGIC + bytes([S, 0, 0, 0]) + np.array([len(s) for s in streams], dtype="<u4").tobytes()
-    return head + b"".join(streams)
+    return _pack(SPLIT_STREAM, streams)
 
 
 def split_unpack(blob) -> list:
     """-> the S sub-streams of a ``split_pack`` string; anything malformed is refused by name."""
-    blob = bytes(blob)
-    if len(blob) < 8 or blob[:4] != SPLIT_MAGIC:
-        raise ValueError(f"split_unpack: bad magic {blob[:4]!r} (a split stream starts with {SPLIT_MAGIC!r})")
-    S = blob[4]
-    if not 1 <= S <= SPLIT_MAX:
-        raise ValueError(f"split_unpack: S must be between 1 and {SPLIT_MAX} sub-streams (got {S})")
-    if blob[5:8] != b"\0\0\0":
-        raise ValueError(f"split_unpack: non-zero pad byte in the header ({blob[5:8].hex()})")
-    if len(blob) < 8 + 4 * S:
-        raise ValueError(f"split_unpack: the lengths do not add up to the blob ({len(blob)} bytes end inside the header of S = {S})")
-    lengths = [int(n) for n in np.frombuffer(blob, dtype="<u4", count=S, offset=8)]
-    for i, n in enumerate(lengths):
-        if not _split_length_ok(n):
-            raise ValueError(f"split_unpack: sub-stream {i} has length {n}; a length must be a multiple of 4 and at least 8")
-    if 8 + 4 * S + sum(lengths) != len(blob):
-        raise ValueError(f"split_unpack: the lengths do not add up to the blob (header {8 + 4 * S} + {sum(lengths)} != {len(blob)} bytes)")
-    out, at = [], 8 + 4 * S
-    for n in lengths:
-        out.append(blob[at:at + n])
-        at += n
-    return out
+    return _unpack(SPLIT_STREAM, blob)
 
 
 LANES_MAGIC = b"CLN1"
 LANES = 64          # rANS lanes of a wave stream: one per GPU lane
 LANES_MAX_W = 16    # wave streams per image: one wave each on the device coder (clc_rans_lanes_decode_step / clc_rans_lanes_encode)
-
-
-def _lanes_length_ok(n):
-    return n >= 8 * LANES and n % 4 == 0
-
-
-def _lanes_w(W, who):
-    if isinstance(W, bool) or not isinstance(W, (int, np.integer)) or not 1 <= int(W) <= LANES_MAX_W:
-        raise ValueError(f"{who}: W must be between 1 and {LANES_MAX_W} wave streams (got {W!r})")
-    return int(W)
+LANES_STREAM = _Container("lanes", LANES_MAGIC, "W", "wave stream", LANES_MAX_W, 8 * LANES, LANES)
 
 
 def lanes_pack(streams) -> bytes:
@@ -136,42 +156,12 @@ def lanes_pack(streams) -> bytes:
 
     A wave stream is 32-bit words and starts with its 64 lane states (512 bytes).  Overhead against the one stream of ``encode``:
     8 + 4 W bytes of header plus 512 W bytes of lane states."""
-    streams = [bytes(s) for s in streams]
-    W = len(streams)
-    if not 1 <= W <= LANES_MAX_W:
-        raise ValueError(f"lanes_pack: W must be between 1 and {LANES_MAX_W} wave streams (got {W})")
-    for i, s in enumerate(streams):
-        if not _lanes_length_ok(len(s)):
-            raise ValueError(f"lanes_pack: wave stream {i} has {len(s)} bytes; a length must be a multiple of 4 and at least {8 * LANES}")
-    head = LANES_MAGIC + bytes([W, LANES, 0, 0]) + np.array([len(s) for s in streams], dtype="<u4").tobytes()
-    return head + b"".join(streams)
+    return _pack(LANES_STREAM, streams)
 
 
 def lanes_unpack(blob) -> list:
     """-> the W wave streams of a ``lanes_pack`` string; anything malformed is refused by name."""
-    blob = bytes(blob)
-    if len(blob) < 8 or blob[:4] != LANES_MAGIC:
-        raise ValueError(f"lanes_unpack: bad magic {blob[:4]!r} (a lanes stream starts with {LANES_MAGIC!r})")
-    W = blob[4]
-    if not 1 <= W <= LANES_MAX_W:
-        raise ValueError(f"lanes_unpack: W must be between 1 and {LANES_MAX_W} wave streams (got {W})")
-    if blob[5] != LANES:
-        raise ValueError(f"lanes_unpack: the lane byte must be {LANES} (got {blob[5]})")
-    if blob[6:8] != b"\0\0":
-        raise ValueError(f"lanes_unpack: non-zero pad byte in the header ({blob[6:8].hex()})")
-    if len(blob) < 8 + 4 * W:
-        raise ValueError(f"lanes_unpack: the lengths do not add up to the blob ({len(blob)} bytes end inside the header of W = {W})")
-    lengths = [int(n) for n in np.frombuffer(blob, dtype="<u4", count=W, offset=8)]
-    for i, n in enumerate(lengths):
-        if not _lanes_length_ok(n):
-            raise ValueError(f"lanes_unpack: wave stream {i} has length {n}; a length must be a multiple of 4 and at least {8 * LANES}")
-    if 8 + 4 * W + sum(lengths) != len(blob):
-        raise ValueError(f"lanes_unpack: the lengths do not add up to the blob (header {8 + 4 * W} + {sum(lengths)} != {len(blob)} bytes)")
-    out, at = [], 8 + 4 * W
-    for n in lengths:
-        out.append(blob[at:at + n])
-        at += n
-    return out
+    return _unpack(LANES_STREAM, blob)
 
 
 def lanes_wave_symbols(segments, W):
@@ -188,7 +178,7 @@ def lanes_encode(symbols, indexes, segments, W, cdfs, cdfs_sizes, offsets) -> li
     """One image's symbols / indexes in stream order (the segments back to back) -> its W wave streams (bytes), by the host coder
     (clc_rans_lanes_encode_host): the bytes the device encoder writes."""
     L = _lib.load()
-    W = _lanes_w(W, "lanes_encode")
+    W = stream_count(LANES_STREAM, W, "lanes_encode")
     sym, idx = _i32(symbols).reshape(-1), _i32(indexes).reshape(-1)
     seg = _i32(segments).reshape(-1)
     if sym.size != idx.size:

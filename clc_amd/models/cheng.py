@@ -31,7 +31,8 @@ host coder.  8 + 12 S bytes more per image (200 at S = 16).  Its decoder runs on
 (clc_gmm_decode_step): the whole wavefront pass is stream-ordered launches with no host hop.  The default stays the one-stream format,
 byte for byte.
 
-TrainEngine, graphed_training, CodecEngine and ReferenceBank do not take these models.
+TrainEngine, graphed_training, CodecEngine and ReferenceBank do not take these models.  The host side of the coder — the hop of a
+host-decoded step, the upload image of the device-decoded split stream, its end-state check — is coding.py's.
 """
 from __future__ import annotations
 
@@ -44,6 +45,7 @@ from ..entropy_models import GaussianMixtureConditional
 from ..layers import (AttentionBlock, Conv2d, ResidualBlock, ResidualBlockUpsample, ResidualBlockWithStride, conv3x3, subpel_conv3x3)
 from ..ops import ACT_LRELU, CL
 from .clc import _resize_registered_buffers
+from .coding import HostHop, check_stream_ends, coded_item, device_ends, open_decoders, upload_streams
 from .hyperprior import JointAutoregressiveHierarchicalPriors, ar_schedule
 
 _SYM_BOUND = float(1 << 24)
@@ -173,9 +175,7 @@ class Cheng2020Anchor(JointAutoregressiveHierarchicalPriors):
         name = type(self).__name__
         if self.K == 1:
             raise ValueError(f"{name}.{what}: substreams= needs a mixture model (K > 1); the K = 1 stream is CompressAI's and stays one stream")
-        S = int(substreams)
-        if not 1 <= S <= ans.SPLIT_MAX:
-            raise ValueError(f"{name}.{what}: substreams must be between 1 and {ans.SPLIT_MAX} (got {substreams})")
+        S = ans.stream_count(ans.SPLIT_STREAM, int(substreams), f"{name}.{what}", "substreams")
         if S > self.N:
             raise ValueError(f"{name}.{what}: substreams = {S} > N = {self.N} (channel c belongs to sub-stream c mod S: some would be empty)")
         return S
@@ -190,13 +190,10 @@ class Cheng2020Anchor(JointAutoregressiveHierarchicalPriors):
         y, params, z_strings, z_size = self._code_inputs(x)
         triples, _ = self._gmm_encode(y, params)
         t = triples.cpu().numpy()   # the one device -> host copy
-        from ..codec import kernel_config
-
         if S is None:
-            y_strings = [ans.encode_direct(t[i]) for i in range(t.shape[0])]
-            return {"strings": [y_strings, z_strings], "shape": z_size, "kernel_config": kernel_config()}
+            return coded_item([ans.encode_direct(t[i]) for i in range(t.shape[0])], z_strings, z_size)
         y_strings = [ans.split_pack([ans.encode_direct(t[i][:, s::S, :]) for s in range(S)]) for i in range(t.shape[0])]
-        return {"strings": [y_strings, z_strings], "shape": z_size, "kernel_config": kernel_config(), "substreams": S}
+        return coded_item(y_strings, z_strings, z_size, substreams=S)
 
     @torch.no_grad()
     def _gmm_decode(self, y_strings, params):
@@ -212,19 +209,23 @@ class Cheng2020Anchor(JointAutoregressiveHierarchicalPriors):
         ws = self._gmm_workspace(rows, dev)
         filt = self._ar_filters()
         y_hat = torch.zeros((B, N, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
-        decoders = []
-        for s in y_strings:
-            d = ans.RansDecoder()
-            d.set_stream(s)
-            decoders.append(d)
-        S = ops.GMM_ROW_STRIDE
-        # one pinned buffer per hop: the rows and, behind them, the offsets
-        down_dev = torch.empty((rows * N * (S + 1),), device=dev, dtype=torch.int32)
-        down_host = torch.empty((rows * N * (S + 1),), dtype=torch.int32).pin_memory()
-        sym_dev = torch.empty((rows, N), device=dev, dtype=torch.int32)
-        sym_host = torch.empty((rows, N), dtype=torch.int32).pin_memory()
-        down_np, sym_np = down_host.numpy(), sym_host.numpy()
-        stream = torch.cuda.current_stream(dev)
+        decoders = open_decoders(y_strings)
+
+        def decode(rows_np, offs_np, sym_np):
+            e = sym_np.size // B   # image b's elements of the step: rows b * cnt .. in list order, channels inner
+            for b, d in enumerate(decoders):
+                sym_np[b * e:(b + 1) * e] = d.decode_rows(rows_np[b * e:(b + 1) * e], offs_np[b * e:(b + 1) * e])
+        self._gmm_hops(steps, pix, y_hat, params, ws, filt, decode)
+        return y_hat
+
+    def _gmm_hops(self, steps, pix, y_hat, params, ws, filt, decode):
+        """The host-decoded wavefront pass: per non-empty step the chain, gmm_finish_decode, one hop and gmm_commit.  A hop downloads
+        ONE buffer, the step's rows and behind them its offsets, and uploads the symbols that
+        decode(rows int32 [n N, GMM_ROW_STRIDE], offsets int32 [n N], symbols int32 [n N]) wrote."""
+        (B, N, H, W), K, R = y_hat.shape, self.K, ops.GMM_ROW_STRIDE
+        split = lambda down_np, sym_np: decode(down_np[:sym_np.size * R].reshape(-1, R), down_np[sym_np.size * R:], sym_np)
+        rows = B * max(len(s) for s in steps)
+        hop = HostHop(rows * N * (R + 1), rows * N, y_hat.device)
         off = 0
         for s in steps:
             cnt = len(s)
@@ -232,19 +233,10 @@ class Cheng2020Anchor(JointAutoregressiveHierarchicalPriors):
             px = pix[off:off + cnt]
             off += cnt
             self._ar_chain(px, B, H, W, y_hat, params, ws, filt)
-            rows_dev = down_dev[:n * N * S].view(n, N, S)
-            offs_dev = down_dev[n * N * S:n * N * (S + 1)].view(n, N)
-            ops.gmm_finish_decode(ws["gp"], N, K, px, B, H, W, rows_dev, offs_dev)
-            down_host[:n * N * (S + 1)].copy_(down_dev[:n * N * (S + 1)], non_blocking=True)
-            stream.synchronize()   # (also: the previous step's symbol upload has left sym_host)
-            rows_np = down_np[:n * N * S].reshape(n * N, S)
-            offs_np = down_np[n * N * S:n * N * (S + 1)]
-            e = cnt * N   # image b's elements of the step: rows b * cnt .. in list order, channels inner
-            for b, d in enumerate(decoders):
-                sym_np[b * cnt:(b + 1) * cnt] = d.decode_rows(rows_np[b * e:(b + 1) * e], offs_np[b * e:(b + 1) * e]).reshape(cnt, N)
-            sym_dev[:n].copy_(sym_host[:n], non_blocking=True)
-            ops.gmm_commit(sym_dev[:n], N, px, y_hat)
-        return y_hat
+            down, sym_dev = hop.step(n * N * (R + 1), n * N)
+            ops.gmm_finish_decode(ws["gp"], N, K, px, B, H, W, down[:n * N * R].view(n, N, R), down[n * N * R:].view(n, N))
+            hop.run(split)
+            ops.gmm_commit(sym_dev.view(n, N), N, px, y_hat)
 
     def _split_parse(self, y_strings, S):
         """-> per image the S sub-streams of its split string; a header that disagrees with the caller's S is refused"""
@@ -274,82 +266,32 @@ class Cheng2020Anchor(JointAutoregressiveHierarchicalPriors):
         ws = self._gmm_workspace(rows, dev)
         filt = self._ar_filters()
         y_hat = torch.zeros((B, N, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
-        off = 0
         if device_decoder:
-            flat = [np.frombuffer(s, dtype="<u4") for img in subs for s in img]
-            counts = np.array([w.size for w in flat], dtype=np.int64)
-            firsts = np.concatenate(([0], np.cumsum(counts)[:-1]))
-            n_words = int(counts.sum())
-            if n_words >= 1 << 31:
-                raise ValueError(f"decompress: {n_words} stream words in one batch; the spans are int32")
-            # one pinned buffer, one upload: the states, the spans, the words
-            host = torch.empty((6 * B * S + n_words,), dtype=torch.int32).pin_memory()
-            h = host.numpy().view(np.uint32)
-            st = h[:4 * B * S].reshape(B * S, 4)
-            st[:, 0], st[:, 1], st[:, 2], st[:, 3] = [w[0] for w in flat], [w[1] for w in flat], 2, 0
-            sp = h[4 * B * S:6 * B * S].reshape(B * S, 2)
-            sp[:, 0], sp[:, 1] = firsts, counts
-            h[6 * B * S:] = np.concatenate(flat)
-            d = torch.empty((host.numel(),), device=dev, dtype=torch.int32)
-            d.copy_(host, non_blocking=True)
-            state, spans, words = d[:4 * B * S].view(B, S, 4), d[4 * B * S:6 * B * S].view(B, S, 2), d[6 * B * S:]
+            state, spans, words = upload_streams(subs, 2, dev)   # a sub-stream starts with the two words of its coder state
+            off = 0
             for s in steps:
                 px = pix[off:off + len(s)]
                 off += len(s)
                 self._ar_chain(px, B, H, W, y_hat, params, ws, filt)
                 ops.gmm_decode_step(ws["gp"], N, K, px, words, spans, state, y_hat)
-            # (host's pages stay pinned until the copy has run: the caching host allocator holds them back until then)
             return y_hat, state
-        decoders = []
-        for img in subs:
-            decoders.append([])
-            for s in img:
-                dd = ans.RansDecoder()
-                dd.set_stream(s)
-                decoders[-1].append(dd)
-        R = ops.GMM_ROW_STRIDE
-        down_dev = torch.empty((rows * N * (R + 1),), device=dev, dtype=torch.int32)
-        down_host = torch.empty((rows * N * (R + 1),), dtype=torch.int32).pin_memory()
-        sym_dev = torch.empty((rows, N), device=dev, dtype=torch.int32)
-        sym_host = torch.empty((rows, N), dtype=torch.int32).pin_memory()
-        down_np, sym_np = down_host.numpy(), sym_host.numpy()
-        stream = torch.cuda.current_stream(dev)
-        for s in steps:
-            cnt = len(s)
-            n = B * cnt
-            px = pix[off:off + cnt]
-            off += cnt
-            self._ar_chain(px, B, H, W, y_hat, params, ws, filt)
-            ops.gmm_finish_decode(ws["gp"], N, K, px, B, H, W, down_dev[:n * N * R].view(n, N, R), down_dev[n * N * R:n * N * (R + 1)].view(n, N))
-            down_host[:n * N * (R + 1)].copy_(down_dev[:n * N * (R + 1)], non_blocking=True)
-            stream.synchronize()
-            rows_np = down_np[:n * N * R].reshape(B, cnt, N, R)
-            offs_np = down_np[n * N * R:n * N * (R + 1)].reshape(B, cnt, N)
+        decoders = [open_decoders(img) for img in subs]
+
+        def decode(rows_np, offs_np, sym_np):
+            R = rows_np.shape[1]
+            rows_np, offs_np, sym_np = rows_np.reshape(B, -1, N, R), offs_np.reshape(B, -1, N), sym_np.reshape(B, -1, N)
             for b in range(B):
                 for k, dd in enumerate(decoders[b]):   # sub-stream k's elements of the step: list order, then its channels ascending
                     r = np.ascontiguousarray(rows_np[b, :, k::S]).reshape(-1, R)
                     o = np.ascontiguousarray(offs_np[b, :, k::S]).reshape(-1)
-                    sym_np[b * cnt:(b + 1) * cnt, k::S] = dd.decode_rows(r, o).reshape(cnt, -1)
-            sym_dev[:n].copy_(sym_host[:n], non_blocking=True)
-            ops.gmm_commit(sym_dev[:n], N, px, y_hat)
+                    sym_np[b, :, k::S] = dd.decode_rows(r, o).reshape(sym_np.shape[1], -1)
+        self._gmm_hops(steps, pix, y_hat, params, ws, filt, decode)
         return y_hat, None
 
     @staticmethod
     def _split_check(state, subs):
-        """A sub-stream decoded to its end leaves x == 2^31 and pos == its word count (the coder's end-state property); anything else
-        raises, naming per image every sub-stream that did not.  (A wrong symbol enters the context of the pixels after it, so a damaged
-        sub-stream usually takes the image's others out of step with it: the list holds the damaged one, it cannot single it out.)"""
-        st = state.cpu().numpy().view(np.uint32)   # the one download of the device path
-        bad = []
-        for b, img in enumerate(subs):
-            off = [s for s, blob in enumerate(img)
-                   if (int(st[b, s, 0]), int(st[b, s, 1]), int(st[b, s, 2])) != (1 << 31, 0, len(blob) // 4)]
-            if off:
-                s = off[0]
-                bad.append(f"image {b}: sub-streams {off} did not decode to their end (sub-stream {s}: final state x = "
-                           f"{int(st[b, s, 0]) | int(st[b, s, 1]) << 32:#x}, {int(st[b, s, 2])} of {len(img[s]) // 4} words consumed)")
-        if bad:
-            raise ValueError("decompress: " + "; ".join(bad) + ": the stream is corrupt, truncated or belongs to other parameters")
+        """coding.check_stream_ends over the device's int32 [B, S, 4] state tensor: ONE download"""
+        check_stream_ends(*device_ends(state), [[len(blob) // 4 for blob in img] for img in subs], "sub-stream")
 
     @torch.no_grad()
     def decompress(self, strings, shape, substreams=None, device_decoder=True, check=True):

@@ -1,0 +1,170 @@
+"""What the context-model coders (hyperprior.py, elic.py, cheng.py) share on the host side of their kernels — each decision has one
+owner here:
+
+* THE HOP of a host-decoded step: ``HostHop`` (buffers allocated once; per step one download, one synchronize, the caller's decode, one
+  upload), ``open_decoders`` and ``table_decode``.
+* THE UPLOAD IMAGE of a device-decoded batch, ``[states | spans | words]`` in one pinned int32 buffer: ``stream_image`` (numpy),
+  ``stream_views``, ``upload_streams``; and the end-state rule of a whole stream, ``check_stream_ends`` / ``device_ends``.
+* Small pieces: ``linear_filters``, ``CodeInputs._code_inputs``, ``coded_item``.
+
+The kernels, their order and their arguments stay with the models; the multi-stream container is ans.py's.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .. import ans
+
+
+class HostHop:
+    """The buffers and the protocol of one host-decoded step.  ``step(n, m)`` hands out the device views ``down`` (n int32, for the
+    finish kernel to write) and ``up`` (m int32, for the commit kernel to read); between the two kernels ``run(decode)`` takes down to
+    the host, lets the caller decode it into m int32 and brings those to up.  Device staging buffers, their pinned twins and the numpy
+    views of the twins are allocated once, for the largest step."""
+
+    def __init__(self, down_elems, up_elems, dev):
+        self._down_dev = torch.empty((down_elems,), device=dev, dtype=torch.int32)
+        self._up_dev = torch.empty((up_elems,), device=dev, dtype=torch.int32)
+        self._down_host = torch.empty((down_elems,), dtype=torch.int32).pin_memory()
+        self._up_host = torch.empty((up_elems,), dtype=torch.int32).pin_memory()
+        self._down_np, self._up_np = self._down_host.numpy(), self._up_host.numpy()
+        self._stream = torch.cuda.current_stream(dev)
+        self._sizes = self._cut = None
+
+    def step(self, n_down, n_up):
+        """-> (down, up) of the next run.  The views are kept while the sizes repeat: a tensor slice costs microseconds, mbt2018 hops
+        once per pixel at one size and a wavefront repeats each step size three times."""
+        if self._sizes != (n_down, n_up):
+            self._sizes = (n_down, n_up)
+            self._cut = (self._down_dev[:n_down], self._up_dev[:n_up], self._down_host[:n_down], self._up_host[:n_up],
+                         self._down_np[:n_down], self._up_np[:n_up])
+        return self._cut[0], self._cut[1]
+
+    def run(self, decode):
+        """one device -> host copy, one synchronize, ``decode(down, up)`` on numpy views of the pinned pages, one host -> device copy"""
+        down_dev, up_dev, down_host, up_host, down_np, up_np = self._cut
+        down_host.copy_(down_dev, non_blocking=True)
+        self._stream.synchronize()   # (also: the previous step's upload has left the pinned page that decode is about to overwrite)
+        decode(down_np, up_np)
+        up_dev.copy_(up_host, non_blocking=True)
+
+
+def open_decoders(strings):
+    """one incremental ans.RansDecoder per stream, opened once"""
+    decoders = []
+    for s in strings:
+        d = ans.RansDecoder()
+        d.set_stream(s)
+        decoders.append(d)
+    return decoders
+
+
+def table_decode(decode_fns, tables):
+    """The ``HostHop.run`` callback of a step coded through table indexes.  The step's rows are B equal blocks, image b's pixels in list
+    order with channels inner, which is the order of its stream: block b goes through decode_fns[b](indexes, cdf, sizes, offsets)."""
+    cdf, ln, off = tables
+
+    def decode(idx_np, sym_np):
+        e = idx_np.size // len(decode_fns)
+        for b, fn in enumerate(decode_fns):
+            sym_np[b * e:(b + 1) * e] = fn(idx_np[b * e:(b + 1) * e], cdf, ln, off)
+    return decode
+
+
+def stream_spans(counts):
+    """word counts of a batch's streams -> int64 [n, 2] (first word, word count): back to back from word 0"""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    n_words = int(counts.sum())
+    if n_words >= 1 << 31:
+        raise ValueError(f"decompress: {n_words} stream words in one batch; the spans are int32")
+    return np.stack((np.concatenate(([0], np.cumsum(counts)[:-1])), counts), axis=1)
+
+
+def stream_image(subs, n_state):
+    """The upload image of a device-decoded batch, subs[b][s] the bytes of image b's stream s -> int32 [(n_state + 4) B S + words]:
+
+        B S states of n_state + 2 words | B S spans (first word, word count) | every stream's 32-bit words, back to back
+
+    A state is the stream's first n_state words (its coder's initial state: 2 for a split sub-stream, 128 for a lanes wave stream), then
+    pos = n_state, the next word to read, and a pad word 0."""
+    flat = [np.frombuffer(s, dtype="<u4") for img in subs for s in img]
+    spans = stream_spans([w.size for w in flat])
+    image = np.empty(((n_state + 4) * len(flat) + int(spans[:, 1].sum()),), dtype=np.uint32)
+    state, sp, words = stream_views(image, 1, len(flat), n_state)
+    for i, w in enumerate(flat):
+        state[0, i, :n_state] = w[:n_state]
+    state[0, :, n_state], state[0, :, n_state + 1] = n_state, 0
+    sp[0] = spans
+    np.concatenate(flat, out=words)
+    return image.view(np.int32)
+
+
+def stream_views(image, B, S, n_state):
+    """a stream_image (numpy array or tensor) -> its (state [B, S, n_state + 2], spans [B, S, 2], words) views"""
+    SW, n = n_state + 2, B * S
+    return image[:SW * n].reshape(B, S, SW), image[SW * n:(SW + 2) * n].reshape(B, S, 2), image[(SW + 2) * n:]
+
+
+def upload_streams(subs, n_state, dev):
+    """stream_image through one pinned buffer and one non-blocking copy -> the device's (state, spans, words)"""
+    host = torch.from_numpy(stream_image(subs, n_state)).pin_memory()
+    image = torch.empty((host.numel(),), device=dev, dtype=torch.int32)
+    image.copy_(host, non_blocking=True)
+    # (host's pages stay pinned until the copy has run: the caching host allocator holds them back until then)
+    return stream_views(image, len(subs), len(subs[0]), n_state)
+
+
+def device_ends(state):
+    """the device coder's state tensor int32 [B, S, n_state + 2] -> (x uint64 [B, S, n_state / 2], pos [B, S]): ONE download"""
+    st = state.cpu().numpy().view(np.uint32)
+    n = st.shape[2] - 2
+    return st[..., 0:n:2].astype(np.uint64) | (st[..., 1:n:2].astype(np.uint64) << np.uint64(32)), st[..., n]
+
+
+def check_stream_ends(x, pos, counts, noun):
+    """A stream decoded to its end leaves every coder state at 2^31 and pos == its word count (the coder's end-state property); anything
+    else raises, naming per image every stream that did not.  (A wrong symbol enters the context of what is decoded after it, so a damaged
+    stream usually takes the image's others out of step with it: the list holds the damaged one, it cannot single it out.)
+    x: final states [B, S, states per stream]; pos, counts: words consumed and words held [B, S]; noun: what a stream is called."""
+    x, pos, counts = np.asarray(x, dtype=np.uint64), np.asarray(pos), np.asarray(counts)
+    astray = (x != np.uint64(1 << 31)).sum(axis=2)
+    bad = []
+    for b in range(x.shape[0]):
+        off = [s for s in range(x.shape[1]) if astray[b, s] or pos[b, s] != counts[b, s]]
+        if off:
+            s = off[0]
+            bad.append(f"image {b}: {noun}s {off} did not decode to their end ({noun} {s}: {int(astray[b, s])} of {x.shape[2]} states not at "
+                       f"2^31, {int(pos[b, s])} of {int(counts[b, s])} words consumed)")
+    if bad:
+        raise ValueError("decompress: " + "; ".join(bad) + ": the stream is corrupt, truncated or belongs to other parameters")
+
+
+def linear_filters(layers):
+    """[(filter [N, K] row-major, bias)] of layers 0, 2 and 4 of a Sequential of three 1x1 convolutions and their activations"""
+    out = []
+    for i in (0, 2, 4):
+        w = layers[i].weight.detach()
+        out.append((w.reshape(w.shape[0], w.shape[1]).contiguous(), layers[i].bias.detach().contiguous()))
+    return out
+
+
+def coded_item(y_strings, z_strings, z_size, **extra):
+    """what compress returns"""
+    from ..codec import kernel_config
+
+    return {"strings": [y_strings, z_strings], "shape": z_size, "kernel_config": kernel_config(), **extra}
+
+
+class CodeInputs:
+    """for models with _prep, _analysis, _hyper_analysis, _hyper_synthesis and an entropy_bottleneck"""
+
+    @torch.no_grad()
+    def _code_inputs(self, x):
+        """(y, hyper parameters from the coded z, z streams, z's map size): what the context model's passes start from"""
+        x = self._prep(x)
+        y = self._analysis(x)
+        z = self._hyper_analysis(y)
+        z_strings = self.entropy_bottleneck.compress(z)
+        z_hat = self.entropy_bottleneck.decompress(z_strings, z.size()[-2:])
+        return y, self._hyper_synthesis(z_hat), z_strings, z.size()[-2:]

@@ -19,7 +19,8 @@ batch-invariant routes ``mbt2018-mean`` codes with: a stream written at batch 8 
 STREAM ORDER: one rANS stream per image for y — for k ascending, group k's anchors in raster order, then its non-anchors in raster
 order, channels inner; z as in the other hyperprior models.
 
-TrainEngine, graphed_training, CodecEngine and ReferenceBank do not take this model.
+TrainEngine, graphed_training, CodecEngine and ReferenceBank do not take this model.  The host side of the coder — the hop of a
+host-decoded pass, the upload image of the device-decoded lanes stream, its end-state check — is coding.py's.
 """
 from __future__ import annotations
 
@@ -32,7 +33,9 @@ from ..entropy_models import GaussianConditional
 from ..layers import AttentionBlock, CheckerboardMaskedConv2d, Conv2d, conv, conv1x1, conv3x3, deconv
 from ..ops import ACT_NONE, ACT_RELU, CL
 from .clc import CompressionModel, _resize_registered_buffers, get_scale_table
-from .hyperprior import ckbd_pixels
+from .coding import (CodeInputs, HostHop, check_stream_ends, coded_item, device_ends, linear_filters, open_decoders, table_decode,
+                     upload_streams)
+from .hyperprior import ckbd_lists, ckbd_pixels
 
 
 def scctx_order(H, W, groups):
@@ -77,7 +80,7 @@ def _run(seq, x):
     return x
 
 
-class Elic2022(CompressionModel):
+class Elic2022(CodeInputs, CompressionModel):
     """ELIC, written from the paper (He et al., CVPR 2022); nothing is pinned against any other implementation.  See the module
     docstring for the kernels and the stream order."""
 
@@ -169,25 +172,12 @@ class Elic2022(CompressionModel):
     # ---- the 2 K-pass coder ----
     def _scctx_filters(self):
         """per group the [(filter [N, K] row-major, bias)] of the three aggregation layers"""
-        out = []
-        for agg in self.aggregation:
-            f = []
-            for i in (0, 2, 4):
-                w = agg[i].weight.detach()
-                f.append((w.reshape(w.shape[0], w.shape[1]).contiguous(), agg[i].bias.detach().contiguous()))
-            out.append(f)
-        return out
+        return [linear_filters(agg) for agg in self.aggregation]
 
     def _scctx_workspace(self, rows, dev):
         mk = lambda c: torch.empty((rows, c), device=dev, dtype=torch.float32)
         a0, a1 = self.aggregation[0][0].out_channels, self.aggregation[0][2].out_channels
         return {"h1": mk(a0), "h2": mk(a1), "gp": mk(2 * max(self.groups))}
-
-    @staticmethod
-    def _scctx_lists(H, W, dev):
-        """(number of anchors, number of non-anchors, the uploaded pixel list: anchors first)"""
-        anchors, others = ckbd_pixels(H, W)
-        return len(anchors), len(others), torch.tensor(anchors + others, dtype=torch.int32).reshape(-1, 2).to(dev)
 
     def _scctx_chain(self, px, B, H, W, params, sp, ch, ws, filt):
         """(scales | means) of one group at the listed pixels of every image -> the first 2 c columns of ws["gp"]; three launches.  The K
@@ -210,7 +200,7 @@ class Elic2022(CompressionModel):
         y = y.contiguous(memory_format=CL)
         params = params.contiguous(memory_format=CL)
         dev = y.device
-        na, nn_, pix = self._scctx_lists(H, W, dev)
+        na, nn_, pix = ckbd_lists(H, W, dev)
         ws = self._scctx_workspace(B * max(na, nn_), dev)
         filt = self._scctx_filters()
         table = self.gaussian_conditional.scale_table
@@ -232,24 +222,10 @@ class Elic2022(CompressionModel):
             idxs.append(idx)
         return syms, idxs, y_hat
 
-    @torch.no_grad()
-    def _code_inputs(self, x):
-        """(y, hyper parameters from the coded z, z streams, z's map size): what the passes start from"""
-        x = self._prep(x)
-        y = self._analysis(x)
-        z = self._hyper_analysis(y)
-        z_strings = self.entropy_bottleneck.compress(z)
-        z_hat = self.entropy_bottleneck.decompress(z_strings, z.size()[-2:])
-        return y, self._hyper_synthesis(z_hat), z_strings, z.size()[-2:]
-
     @staticmethod
     def _lanes_count(lanes, what):
         """lanes=None: the one-stream format; else the number W of wave streams per image, refused by name outside 1 .. 16"""
-        if lanes is None:
-            return None
-        if isinstance(lanes, bool) or not isinstance(lanes, int) or not 1 <= lanes <= ans.LANES_MAX_W:
-            raise ValueError(f"Elic2022.{what}: lanes must be between 1 and {ans.LANES_MAX_W} wave streams per image (got {lanes!r})")
-        return lanes
+        return None if lanes is None else ans.stream_count(ans.LANES_STREAM, lanes, f"Elic2022.{what}", "lanes")
 
     def _lanes_segments(self, H, W):
         """the lanes stream's segments: the 2 K passes in scctx_order, n = pixels of the pass x channels of the group"""
@@ -281,17 +257,15 @@ class Elic2022(CompressionModel):
             cdf, ln, off = self.gaussian_conditional.host_tables()
         syms, idxs, _ = self._scctx_encode(y, params)
         B, _, H, W = y.shape
-        na, nn_, pix = self._scctx_lists(H, W, y.device)
+        na, nn_, pix = ckbd_lists(H, W, y.device)
         order = (pix[:, 0].long() * W + pix[:, 1].long())   # raster positions in the stream's pixel order: anchors, then non-anchors
         flat = lambda ts: torch.cat([t.index_select(1, order).reshape(B, -1) for t in ts], 1)
-        from ..codec import kernel_config
-
         if Wn is not None:   # the flat buffers stay on the device
             y_strings = self._lanes_encode_device(flat(syms), flat(idxs), self._lanes_segments(H, W), Wn)
-            return {"strings": [y_strings, z_strings], "shape": z_size, "kernel_config": kernel_config(), "lanes": Wn}
+            return coded_item(y_strings, z_strings, z_size, lanes=Wn)
         both = torch.stack((flat(syms), flat(idxs))).cpu().numpy()   # the one device -> host copy: [2, B, H*W*M] in stream order
         y_strings = [ans.encode(np.ascontiguousarray(both[0, i]), np.ascontiguousarray(both[1, i]), cdf, ln, off) for i in range(B)]
-        return {"strings": [y_strings, z_strings], "shape": z_size, "kernel_config": kernel_config()}
+        return coded_item(y_strings, z_strings, z_size)
 
     @torch.no_grad()
     def _scctx_decode(self, y_strings, params):
@@ -301,22 +275,14 @@ class Elic2022(CompressionModel):
         B, M, (H, W) = params.shape[0], self.M, params.shape[2:]
         if len(y_strings) != B:
             raise ValueError(f"decompress: {len(y_strings)} y streams for {B} z streams")
-        cdf, ln, off = self.gaussian_conditional.host_tables()
         table = self.gaussian_conditional.scale_table
-        na, nn_, pix = self._scctx_lists(H, W, dev)
+        na, nn_, pix = ckbd_lists(H, W, dev)
         rows = B * max(na, nn_)
         ws = self._scctx_workspace(rows, dev)
         filt = self._scctx_filters()
         y_hat = torch.zeros((B, M, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
-        decoders = []
-        for s in y_strings:
-            d = ans.RansDecoder()
-            d.set_stream(s)
-            decoders.append(d)
-        cmax = max(self.groups)
-        idx_host = torch.empty((rows * cmax,), dtype=torch.int32).pin_memory()
-        sym_host = torch.empty((rows * cmax,), dtype=torch.int32).pin_memory()
-        stream = torch.cuda.current_stream(dev)
+        decode = table_decode([d.decode_stream for d in open_decoders(y_strings)], self.gaussian_conditional.host_tables())
+        hop = HostHop(rows * max(self.groups), rows * max(self.groups), dev)
         for k, (s, c) in enumerate(zip(self.starts, self.groups)):
             yhk = y_hat[:, s:s + c]
             ch = self._channel_ctx(k, y_hat)
@@ -327,18 +293,10 @@ class Elic2022(CompressionModel):
                 px = pix[lo:lo + cnt]
                 if lo:
                     sp = self.spatial_context[k](yhk)
-                n = B * cnt
-                idx_dev = torch.empty((n, c), device=dev, dtype=torch.int32)
-                sym_dev = torch.empty((n, c), device=dev, dtype=torch.int32)
-                ih, sh = idx_host[:n * c].view(n, c), sym_host[:n * c].view(n, c)
-                idx_np, sym_np = ih.numpy(), sh.numpy()
+                idx_dev, sym_dev = (t.view(B * cnt, c) for t in hop.step(B * cnt * c, B * cnt * c))
                 self._scctx_chain(px, B, H, W, params, sp, ch, ws, filt[k])
                 ops.ar_finish_decode(ws["gp"], c, px, B, H, W, table, idx_dev)
-                ih.copy_(idx_dev, non_blocking=True)
-                stream.synchronize()   # (also: the previous pass's symbol upload has left sym_host)
-                for b, d in enumerate(decoders):   # rows b * cnt .. of the pass are image b's pixels in list order, channels inner
-                    sym_np[b * cnt:(b + 1) * cnt] = d.decode_stream(idx_np[b * cnt:(b + 1) * cnt].reshape(-1), cdf, ln, off).reshape(cnt, c)
-                sym_dev.copy_(sh, non_blocking=True)
+                hop.run(decode)
                 ops.ar_commit(sym_dev, ws["gp"], c, px, yhk)
         return y_hat
 
@@ -364,45 +322,22 @@ class Elic2022(CompressionModel):
         B, M, (H, W) = params.shape[0], self.M, params.shape[2:]
         if len(subs) != B:
             raise ValueError(f"decompress: {len(subs)} y streams for {B} z streams")
-        Wn = len(subs[0])
         table = self.gaussian_conditional.scale_table
-        na, nn_, pix = self._scctx_lists(H, W, dev)
+        na, nn_, pix = ckbd_lists(H, W, dev)
         rows = B * max(na, nn_)
         ws = self._scctx_workspace(rows, dev)
         filt = self._scctx_filters()
         y_hat = torch.zeros((B, M, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
-        cmax = max(self.groups)
+        gc, cmax = self.gaussian_conditional, max(self.groups)
         if device_coder:
-            gc = self.gaussian_conditional
             tables = (gc._quantized_cdf, gc._cdf_length, gc._offset)
-            flat = [np.frombuffer(s, dtype="<u4") for img in subs for s in img]
-            counts = np.array([w.size for w in flat], dtype=np.int64)
-            firsts = np.concatenate(([0], np.cumsum(counts)[:-1]))
-            n_words = int(counts.sum())
-            if n_words >= 1 << 31:
-                raise ValueError(f"decompress: {n_words} stream words in one batch; the spans are int32")
-            # one pinned buffer, one upload: the states, the spans, the words
-            SW, n_st = ops.RANS_LANES_STATE_WORDS, B * Wn
-            host = torch.empty(((SW + 2) * n_st + n_words,), dtype=torch.int32).pin_memory()
-            h = host.numpy().view(np.uint32)
-            st = h[:SW * n_st].reshape(n_st, SW)
-            for i, w in enumerate(flat):
-                st[i, :2 * ans.LANES] = w[:2 * ans.LANES]
-            st[:, 2 * ans.LANES], st[:, 2 * ans.LANES + 1] = 2 * ans.LANES, 0
-            sp = h[SW * n_st:(SW + 2) * n_st].reshape(n_st, 2)
-            sp[:, 0], sp[:, 1] = firsts, counts
-            h[(SW + 2) * n_st:] = np.concatenate(flat)
-            d = torch.empty((host.numel(),), device=dev, dtype=torch.int32)
-            d.copy_(host, non_blocking=True)
-            state, spans, words = d[:SW * n_st].view(B, Wn, SW), d[SW * n_st:(SW + 2) * n_st].view(B, Wn, 2), d[(SW + 2) * n_st:]
+            state, spans, words = upload_streams(subs, 2 * ans.LANES, dev)   # a wave stream starts with its 64 lane states
             idx_dev = torch.empty((rows * cmax,), device=dev, dtype=torch.int32)
             sym_dev = torch.empty((rows * cmax,), device=dev, dtype=torch.int32)
         else:
-            cdf, ln, off = self.gaussian_conditional.host_tables()
             decoders = [ans.LanesDecoder(img) for img in subs]
-            idx_host = torch.empty((rows * cmax,), dtype=torch.int32).pin_memory()
-            sym_host = torch.empty((rows * cmax,), dtype=torch.int32).pin_memory()
-            stream = torch.cuda.current_stream(dev)
+            decode = table_decode([d.decode for d in decoders], gc.host_tables())
+            hop = HostHop(rows * cmax, rows * cmax, dev)
         for k, (s, c) in enumerate(zip(self.starts, self.groups)):
             yhk = y_hat[:, s:s + c]
             ch = self._channel_ctx(k, y_hat)
@@ -421,45 +356,22 @@ class Elic2022(CompressionModel):
                     ops.rans_lanes_decode_step(ib, cnt * c, tables, words, spans, state, sb)
                     ops.ar_commit(sb, ws["gp"], c, px, yhk)
                     continue
-                ib = torch.empty((n, c), device=dev, dtype=torch.int32)
-                sb = torch.empty((n, c), device=dev, dtype=torch.int32)
-                ih, sh = idx_host[:n * c].view(n, c), sym_host[:n * c].view(n, c)
-                idx_np, sym_np = ih.numpy(), sh.numpy()
+                ib, sb = (t.view(n, c) for t in hop.step(n * c, n * c))
                 ops.ar_finish_decode(ws["gp"], c, px, B, H, W, table, ib)
-                ih.copy_(ib, non_blocking=True)
-                stream.synchronize()   # (also: the previous pass's symbol upload has left sym_host)
-                for b, dd in enumerate(decoders):
-                    sym_np[b * cnt:(b + 1) * cnt] = dd.decode(idx_np[b * cnt:(b + 1) * cnt].reshape(-1), cdf, ln, off).reshape(cnt, c)
-                sb.copy_(sh, non_blocking=True)
+                hop.run(decode)
                 ops.ar_commit(sb, ws["gp"], c, px, yhk)
-        # (the pinned pages stay pinned until the upload has run: the caching host allocator holds them back until then)
         return y_hat, (state if device_coder else decoders)
 
     @staticmethod
     def _lanes_check(state, subs):
-        """A wave stream decoded to its end leaves every lane at x == 2^31 and pos == its word count (the coder's end-state property);
-        anything else raises, naming per image every wave stream that did not.  (A wrong symbol enters the context of the passes after
-        it, so a damaged wave stream usually takes the image's others out of step with it: the list holds the damaged one, it cannot
-        single it out.)  state: the device's [B, W, 130] tensor — ONE download — or the host coder's list of decoders."""
+        """coding.check_stream_ends over every wave stream's 64 lanes.  state: the device's [B, W, 130] tensor — ONE download — or the
+        host coder's list of decoders."""
         if isinstance(state, torch.Tensor):
-            st = state.cpu().numpy().view(np.uint32)   # the one download of the device path
-            L = 2 * ans.LANES
-            ends = lambda b, w: ((st[b, w, 0:L:2].astype(np.uint64) | (st[b, w, 1:L:2].astype(np.uint64) << np.uint64(32))), int(st[b, w, L]))
+            x, pos = device_ends(state)
         else:
-            ends = lambda b, w: state[b].state(w)
-        bad = []
-        for b, img in enumerate(subs):
-            off = []
-            for w, blob in enumerate(img):
-                x, pos = ends(b, w)
-                if not (x == np.uint64(1 << 31)).all() or pos != len(blob) // 4:
-                    off.append((w, int((x != np.uint64(1 << 31)).sum()), pos))
-            if off:
-                w, lanes_off, pos = off[0]
-                bad.append(f"image {b}: wave streams {[o[0] for o in off]} did not decode to their end (wave stream {w}: {lanes_off} of 64 lanes "
-                           f"not at 2^31, {pos} of {len(img[w]) // 4} words consumed)")
-        if bad:
-            raise ValueError("decompress: " + "; ".join(bad) + ": the stream is corrupt, truncated or belongs to other parameters")
+            ends = [[d.state(w) for w in range(len(img))] for d, img in zip(state, subs)]
+            x, pos = [[e[0] for e in img] for img in ends], [[e[1] for e in img] for img in ends]
+        check_stream_ends(x, pos, [[len(blob) // 4 for blob in img] for img in subs], "wave stream")
 
     @torch.no_grad()
     def decompress(self, strings, shape, lanes=None, device_coder=True, check=True):

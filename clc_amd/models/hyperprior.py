@@ -8,7 +8,7 @@ so CompressAI checkpoints load.  CompressAI itself is not a dependency and nothi
 models are checked against a plain-torch restatement of the same definitions (tests/hyperprior_ref.py).
 
 They train through plain autograd and code through the model methods; TrainEngine, graphed_training, CodecEngine and ReferenceBank
-do not take them.
+do not take them.  The host side of the context-model coders — the hop of a host-decoded step, the result item — is coding.py's.
 """
 from __future__ import annotations
 
@@ -21,6 +21,7 @@ from ..entropy_models import EntropyBottleneck, GaussianConditional
 from ..layers import GDN, CheckerboardMaskedConv2d, Conv2d, MaskedConv2d, conv, deconv
 from ..ops import ACT_LRELU, ACT_NONE, ACT_RELU, CL
 from .clc import CompressionModel, _resize_registered_buffers, get_scale_table
+from .coding import CodeInputs, HostHop, coded_item, linear_filters, open_decoders, table_decode
 
 
 class ScaleHyperprior(CompressionModel):
@@ -113,9 +114,7 @@ class ScaleHyperprior(CompressionModel):
         sym = sym.contiguous().cpu().numpy()   # [N, C, H, W]: the element order of CompressAI's symbols[i].reshape(-1)
         idx = idx.contiguous().cpu().numpy()
         y_strings = [ans.encode(sym[i].reshape(-1), idx[i].reshape(-1), cdf, ln, off) for i in range(sym.shape[0])]
-        from ..codec import kernel_config
-
-        return {"strings": [y_strings, z_strings], "shape": z.size()[-2:], "kernel_config": kernel_config()}
+        return coded_item(y_strings, z_strings, z.size()[-2:])
 
     @torch.no_grad()
     def decompress(self, strings, shape):
@@ -189,6 +188,12 @@ def ar_schedule(H, W, order="wavefront"):
     return steps
 
 
+def ckbd_lists(H, W, dev):
+    """(number of anchors, number of non-anchors, the uploaded pixel list: anchors first)"""
+    anchors, others = ckbd_pixels(H, W)
+    return len(anchors), len(others), torch.tensor(anchors + others, dtype=torch.int32).reshape(-1, 2).to(dev)
+
+
 def ckbd_pixels(H, W):
     """(anchors, non-anchors) of an H x W latent under the checkerboard context model, each a raster-ordered list of (h, w): anchors are
     the pixels with (h + w) odd, coded from the hyperprior alone; non-anchors ((h + w) even, (0, 0) among them) are coded from the
@@ -201,7 +206,7 @@ def ckbd_pixels(H, W):
     return anchors, others
 
 
-class JointAutoregressiveHierarchicalPriors(MeanScaleHyperprior):
+class JointAutoregressiveHierarchicalPriors(CodeInputs, MeanScaleHyperprior):
     """Minnen et al. 2018 with the context model (``mbt2018``): the mean-scale hyperprior plus a masked 5x5 convolution over the coded
     latent and a three-layer 1x1 ``entropy_parameters`` net on cat((hyper parameters, context)).
 
@@ -250,11 +255,7 @@ class JointAutoregressiveHierarchicalPriors(MeanScaleHyperprior):
         M = self.M
         cp, ep = self.context_prediction, self.entropy_parameters
         wc = cp.weight.detach().permute(0, 2, 3, 1).reshape(2 * M, 25, M)[:, :12].reshape(2 * M, 12 * M).contiguous()
-        out = [(wc, cp.bias.detach().contiguous())]
-        for i in (0, 2, 4):
-            w = ep[i].weight.detach()
-            out.append((w.reshape(w.shape[0], w.shape[1]).contiguous(), ep[i].bias.detach().contiguous()))
-        return out
+        return [(wc, cp.bias.detach().contiguous())] + linear_filters(ep)
 
     def _ar_workspace(self, rows, dev):
         M = self.M
@@ -297,25 +298,13 @@ class JointAutoregressiveHierarchicalPriors(MeanScaleHyperprior):
         return sym, idx, y_hat
 
     @torch.no_grad()
-    def _code_inputs(self, x):
-        """(y, hyper parameters from the coded z, z streams, z's map size): what the autoregressive pass starts from"""
-        x = self._prep(x)
-        y = self._analysis(x)
-        z = self._hyper_analysis(y)
-        z_strings = self.entropy_bottleneck.compress(z)
-        z_hat = self.entropy_bottleneck.decompress(z_strings, z.size()[-2:])
-        return y, self._hyper_synthesis(z_hat), z_strings, z.size()[-2:]
-
-    @torch.no_grad()
     def compress(self, x, order="wavefront"):
         y, params, z_strings, z_size = self._code_inputs(x)
         cdf, ln, off = self.gaussian_conditional.host_tables()
         sym, idx, _ = self._ar_encode(y, params, order)
         both = torch.stack((sym, idx)).cpu().numpy()   # the one device -> host copy: [2, B, H*W, M], raster pixels, channels inner
         y_strings = [ans.encode(both[0, i].reshape(-1), both[1, i].reshape(-1), cdf, ln, off) for i in range(both.shape[1])]
-        from ..codec import kernel_config
-
-        return {"strings": [y_strings, z_strings], "shape": z_size, "kernel_config": kernel_config()}
+        return coded_item(y_strings, z_strings, z_size)
 
     @torch.no_grad()
     def decompress(self, strings, shape):
@@ -326,32 +315,19 @@ class JointAutoregressiveHierarchicalPriors(MeanScaleHyperprior):
         B, M, (H, W) = params.shape[0], self.M, params.shape[2:]
         if len(strings[0]) != B:
             raise ValueError(f"decompress: {len(strings[0])} y streams for {B} z streams")
-        cdf, ln, off = self.gaussian_conditional.host_tables()
         table = self.gaussian_conditional.scale_table
         steps, pix = self._ar_pixels(ar_schedule(H, W, "raster"), dev)
         ws = self._ar_workspace(B, dev)
         filt = self._ar_filters()
         y_hat = torch.zeros((B, M, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
-        decoders = []
-        for s in strings[0]:
-            d = ans.RansDecoder()
-            d.set_stream(s)
-            decoders.append(d)
-        idx_dev = torch.empty((B, M), device=dev, dtype=torch.int32)
-        sym_dev = torch.empty((B, M), device=dev, dtype=torch.int32)
-        idx_host = torch.empty((B, M), dtype=torch.int32).pin_memory()
-        sym_host = torch.empty((B, M), dtype=torch.int32).pin_memory()
-        idx_np, sym_np = idx_host.numpy(), sym_host.numpy()
-        stream = torch.cuda.current_stream(dev)
+        decode = table_decode([d.decode_stream for d in open_decoders(strings[0])], self.gaussian_conditional.host_tables())
+        hop = HostHop(B * M, B * M, dev)
+        idx_dev, sym_dev = (t.view(B, M) for t in hop.step(B * M, B * M))
         for i in range(len(steps)):
             px = pix[i:i + 1]
             self._ar_chain(px, B, H, W, y_hat, params, ws, filt)
             ops.ar_finish_decode(ws["gp"], M, px, B, H, W, table, idx_dev)
-            idx_host.copy_(idx_dev, non_blocking=True)
-            stream.synchronize()   # (also: the previous pixel's symbol upload has left sym_host)
-            for b, d in enumerate(decoders):
-                sym_np[b] = d.decode_stream(idx_np[b], cdf, ln, off)
-            sym_dev.copy_(sym_host, non_blocking=True)
+            hop.run(decode)
             ops.ar_commit(sym_dev, ws["gp"], M, px, y_hat)
         return {"x_hat": self._synthesis(y_hat).clamp_(0, 1)}
 
@@ -383,10 +359,7 @@ class JointCheckerboardHierarchicalPriors(JointAutoregressiveHierarchicalPriors)
         raise NotImplementedError("JointCheckerboardHierarchicalPriors has no autoregressive pass (mask A): the coder is _ckbd_encode / _ckbd_decode")
 
     # ---- the two-pass coder ----
-    def _ckbd_lists(self, H, W, dev):
-        """(number of anchors, number of non-anchors, the uploaded pixel list: anchors first)"""
-        anchors, others = ckbd_pixels(H, W)
-        return len(anchors), len(others), torch.tensor(anchors + others, dtype=torch.int32).reshape(-1, 2).to(dev)
+    _ckbd_lists = staticmethod(ckbd_lists)
 
     def _ckbd_workspace(self, rows, dev):
         M = self.M
@@ -400,12 +373,7 @@ class JointCheckerboardHierarchicalPriors(JointAutoregressiveHierarchicalPriors)
         ops.ar_linear([("dense", ws["h2"])], px, B, H, W, filt[2][0], filt[2][1], ws["gp"])
 
     def _ckbd_filters(self):
-        ep = self.entropy_parameters
-        out = []
-        for i in (0, 2, 4):
-            w = ep[i].weight.detach()
-            out.append((w.reshape(w.shape[0], w.shape[1]).contiguous(), ep[i].bias.detach().contiguous()))
-        return out
+        return linear_filters(self.entropy_parameters)
 
     @torch.no_grad()
     def _ckbd_encode(self, y, params):
@@ -446,9 +414,7 @@ class JointCheckerboardHierarchicalPriors(JointAutoregressiveHierarchicalPriors)
         order = self._ckbd_order(y.shape[2], y.shape[3])
         y_strings = [ans.encode(np.ascontiguousarray(both[0, i][order]).reshape(-1), np.ascontiguousarray(both[1, i][order]).reshape(-1), cdf, ln, off)
                      for i in range(both.shape[1])]
-        from ..codec import kernel_config
-
-        return {"strings": [y_strings, z_strings], "shape": z_size, "kernel_config": kernel_config()}
+        return coded_item(y_strings, z_strings, z_size)
 
     @torch.no_grad()
     def _ckbd_decode(self, y_strings, params):
@@ -458,24 +424,14 @@ class JointCheckerboardHierarchicalPriors(JointAutoregressiveHierarchicalPriors)
         B, M, (H, W) = params.shape[0], self.M, params.shape[2:]
         if len(y_strings) != B:
             raise ValueError(f"decompress: {len(y_strings)} y streams for {B} z streams")
-        cdf, ln, off = self.gaussian_conditional.host_tables()
         table = self.gaussian_conditional.scale_table
         na, nn_, pix = self._ckbd_lists(H, W, dev)
         rows = B * max(na, nn_)
         ws = self._ckbd_workspace(rows, dev)
         filt = self._ckbd_filters()
         y_hat = torch.zeros((B, M, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
-        decoders = []
-        for s in y_strings:
-            d = ans.RansDecoder()
-            d.set_stream(s)
-            decoders.append(d)
-        idx_dev = torch.empty((rows, M), device=dev, dtype=torch.int32)
-        sym_dev = torch.empty((rows, M), device=dev, dtype=torch.int32)
-        idx_host = torch.empty((rows, M), dtype=torch.int32).pin_memory()
-        sym_host = torch.empty((rows, M), dtype=torch.int32).pin_memory()
-        idx_np, sym_np = idx_host.numpy(), sym_host.numpy()
-        stream = torch.cuda.current_stream(dev)
+        decode = table_decode([d.decode_stream for d in open_decoders(y_strings)], self.gaussian_conditional.host_tables())
+        hop = HostHop(rows * M, rows * M, dev)
         ctx_map = torch.zeros((B, 2 * M, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
         for lo, cnt in ((0, na), (na, nn_)):
             if not cnt:
@@ -483,13 +439,10 @@ class JointCheckerboardHierarchicalPriors(JointAutoregressiveHierarchicalPriors)
             px = pix[lo:lo + cnt]
             if lo:
                 ctx_map = self.context_prediction(y_hat)
+            idx_dev, sym_dev = (t.view(B * cnt, M) for t in hop.step(B * cnt * M, B * cnt * M))
             self._ckbd_chain(px, B, H, W, params, ctx_map, ws, filt)
             ops.ar_finish_decode(ws["gp"], M, px, B, H, W, table, idx_dev)
-            idx_host.copy_(idx_dev, non_blocking=True)
-            stream.synchronize()   # (also: the previous pass's symbol upload has left sym_host)
-            for b, d in enumerate(decoders):   # rows b * cnt .. of the pass are image b's pixels in list order, channels inner
-                sym_np[b * cnt:(b + 1) * cnt] = d.decode_stream(idx_np[b * cnt:(b + 1) * cnt].reshape(-1), cdf, ln, off).reshape(cnt, M)
-            sym_dev.copy_(sym_host, non_blocking=True)
+            hop.run(decode)
             ops.ar_commit(sym_dev, ws["gp"], M, px, y_hat)
         return y_hat
 

@@ -2961,6 +2961,21 @@ def gmm_commit(symbols, N, pix, y_hat):
     _lib.check(_L().clc_gmm_commit(sp, N, pp, P, B, H, W, hp, ldh, _stream()), "clc_gmm_commit")
 
 
+def _coder_streams(words, spans, state, who, letter, state_words, alignment=4):
+    """The stream arguments of a device coder's step, all contiguous int32 device tensors: words [n >= 1], spans [B, S, 2], state
+    [B, S, state_words] at a multiple of ``alignment`` bytes; ``letter`` is what the messages call S.  -> (B, S)"""
+    for t, what in ((words, "words"), (spans, "spans"), (state, "state")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{who}: {what} must be a contiguous int32 device tensor")
+    if spans.dim() != 3 or spans.shape[2] != 2 or words.dim() != 1 or words.numel() < 1:
+        raise ValueError(f"{who}: words must be int32 [n >= 1] and spans int32 [B, {letter}, 2] (got {tuple(words.shape)}, {tuple(spans.shape)})")
+    B, S = int(spans.shape[0]), int(spans.shape[1])
+    if tuple(state.shape) != (B, S, state_words) or state.data_ptr() % alignment:
+        aligned = f"{alignment}-byte aligned " if alignment > 4 else ""
+        raise ValueError(f"{who}: state must be {aligned}int32 [B, {letter}, {state_words}] = {(B, S, state_words)} (got {tuple(state.shape)})")
+    return B, S
+
+
 def gmm_decode_step(gp, N, K, pix, words, spans, state, y_hat):
     """clc_gmm_decode_step: one wavefront step of the split stream's device decoder.  gp [>= B P, >= 3 K N] parameter rows of the step;
     words int32 [n] (every sub-stream's 32-bit words), spans int32 [B, S, 2] (first word, word count), state int32 [B, S, 4]
@@ -2971,14 +2986,9 @@ def gmm_decode_step(gp, N, K, pix, words, spans, state, y_hat):
     if Ch != N:
         raise ValueError(f"gmm_decode_step: y_hat must have N = {N} channels (got {Ch})")
     gpp, ldg = _gmm_gp(gp, B * P, N, K, "gmm_decode_step")
-    for t, what in ((words, "words"), (spans, "spans"), (state, "state")):
-        if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"gmm_decode_step: {what} must be a contiguous int32 device tensor")
-    if spans.dim() != 3 or spans.shape[0] != B or spans.shape[2] != 2 or words.dim() != 1 or words.numel() < 1:
-        raise ValueError(f"gmm_decode_step: words must be int32 [n >= 1] and spans int32 [B = {B}, S, 2] (got {tuple(words.shape)}, {tuple(spans.shape)})")
-    S = int(spans.shape[1])
-    if tuple(state.shape) != (B, S, 4) or state.data_ptr() % 8:
-        raise ValueError(f"gmm_decode_step: state must be an 8-byte aligned int32 [B, S, 4] = {(B, S, 4)} tensor (got {tuple(state.shape)})")
+    Bs, S = _coder_streams(words, spans, state, "gmm_decode_step", "S", 4, alignment=8)
+    if Bs != B:
+        raise ValueError(f"gmm_decode_step: spans must be int32 [B = {B}, S, 2] (got {tuple(spans.shape)})")
     _lib.check(_L().clc_gmm_decode_step(gpp, ldg, N, K, pp, P, B, H, W, words.data_ptr(), spans.data_ptr(), state.data_ptr(), S, hp, ldh,
                                         _stream()), "clc_gmm_decode_step")
 
@@ -3012,15 +3022,11 @@ def rans_lanes_decode_step(indexes, n, tables, words, spans, state, symbols):
     what ar_commit takes); tables: (cdfs, cdf_sizes, offsets) int32 on the device; words int32 [m] (every wave stream's 32-bit words),
     spans int32 [B, W, 2] (first word, word count), state int32 [B, W, RANS_LANES_STATE_WORDS] (64 x (x low, x high), pos, pad: read,
     advanced and written back).  No copy to the host, no sync: the caller keeps every span inside ``words``."""
-    for t, what in ((indexes, "indexes"), (symbols, "symbols"), (words, "words"), (spans, "spans"), (state, "state")):
+    for t, what in ((indexes, "indexes"), (symbols, "symbols")):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
             raise ValueError(f"rans_lanes_decode_step: {what} must be a contiguous int32 device tensor")
-    if spans.dim() != 3 or spans.shape[2] != 2 or words.dim() != 1 or words.numel() < 1:
-        raise ValueError(f"rans_lanes_decode_step: words must be int32 [m >= 1] and spans int32 [B, W, 2] (got {tuple(words.shape)}, {tuple(spans.shape)})")
-    B, W = int(spans.shape[0]), _lanes_w(int(spans.shape[1]), "rans_lanes_decode_step")
-    if tuple(state.shape) != (B, W, RANS_LANES_STATE_WORDS):
-        raise ValueError(f"rans_lanes_decode_step: state must be int32 [B, W, {RANS_LANES_STATE_WORDS}] = {(B, W, RANS_LANES_STATE_WORDS)} "
-                         f"(got {tuple(state.shape)})")
+    B, W = _coder_streams(words, spans, state, "rans_lanes_decode_step", "W", RANS_LANES_STATE_WORDS)
+    _lanes_w(W, "rans_lanes_decode_step")
     n = int(n)
     if B < 1 or n < 0 or indexes.numel() % B or symbols.numel() % B or indexes.numel() // B < n or symbols.numel() // B < n:
         raise ValueError(f"rans_lanes_decode_step: indexes and symbols must hold B = {B} equal image blocks of at least n = {n} elements "

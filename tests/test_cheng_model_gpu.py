@@ -139,6 +139,32 @@ class _count_d2h:
         return False
 
 
+def test_host_hop_is_one_download_and_one_upload(dev):
+    from clc_amd.models.coding import HostHop
+
+    hop = HostHop(16, 16, dev)
+    wrote = torch.arange(16, dtype=torch.int32).reshape(2, 8) * 3 - 7
+    down, up = hop.step(16, 16)
+    down.view(2, 8).copy_(wrote.to(dev))   # what a finish kernel leaves
+    up.fill_(-1)
+    seen = []
+
+    def decode(down_np, up_np):
+        seen.append(down_np.copy())
+        up_np[:] = down_np[::-1] + 100
+
+    with _count_d2h() as c:
+        hop.run(decode)
+    assert c.n == 1 and len(seen) == 1
+    assert seen[0].dtype == np.int32 and seen[0].tolist() == wrote.reshape(-1).tolist()   # the callback saw what the device wrote
+    assert up.cpu().tolist() == (wrote.reshape(-1).flip(0) + 100).tolist()               # the upload region holds what it wrote
+    short_down, short_up = hop.step(8, 4)   # a shorter step moves its own elements only
+    assert short_down.data_ptr() == down.data_ptr() and short_up.data_ptr() == up.data_ptr() and (short_down.numel(), short_up.numel()) == (8, 4)
+    with _count_d2h() as c:
+        hop.run(lambda down_np, up_np: up_np.fill(len(down_np)))
+    assert c.n == 1 and up.cpu().tolist()[:5] == [8, 8, 8, 8, int(wrote.reshape(-1)[11]) + 100]
+
+
 def test_mixture_codec(dev):
     from clc_amd import ans, codec, lib, models
     from clc_amd.models import ar_wavefront_order
