@@ -8,7 +8,7 @@
 //                      K = C*ph*pw) with the normalisation, the Gaussian prior mask (:779-807) and the product fused in
 //                      the epilogue.  The image window of a workgroup (C x ph x (64+pw-1) floats) is staged once in LDS
 //                      and re-used by all K-tiles; patch fragments stream straight from global memory (K-contiguous).
-//   pm_topk            top-k positions per patch, ties -> lowest index (torch.argmax / topk, :105,225)
+//   pm_topk            top-k positions per patch, ties -> lowest index, NaN above +inf (torch.argmax / topk, :105,225)
 //   pm_gather          softmax(value*temperature)-weighted gather of the k best reference patches, re-tiled into an
 //                      image (SI_Wraper :218-240, SI_Finder_at_Image_Domain :106-112)
 // Layout here is the reference's planar NCHW (3-channel images; channels_last would leave 12-byte pixels).
@@ -170,7 +170,19 @@ __global__ void pm_gauss_mask_kernel(float* __restrict__ out, int img_h, int img
   }
 }
 
-// top-k (k <= 8) per patch over npos positions; ties -> lowest index. One workgroup per patch.
+// The one ordering of the top-k search, used by the per-thread scan and by the tree alike: torch.topk / torch.argmax's.
+// NaN ranks above +inf, +inf above every finite value; equal entries (all NaNs count as equal) -> the lower index wins.
+// `(v, i)` goes before `(bv, bi)`?  The start value (-inf, 0x7fffffff) loses against every real entry, a -inf or a NaN included.
+__device__ __forceinline__ bool pm_topk_before(float v, int i, float bv, int bi) {
+  const bool vn = v != v, bn = bv != bv;
+  const bool greater = (vn && !bn) || v > bv;
+  const bool equal = (vn && bn) || v == bv;
+  return greater || (equal && i < bi);
+}
+
+// top-k (k <= 8, k <= npos) per patch over npos positions; ties -> lowest index, NaN above +inf (pm_topk_before). One workgroup per
+// patch.  Every round has at least one position left, and any position beats the start value: every index written is in [0, npos)
+// whatever the floats hold.
 __global__ __launch_bounds__(256) void pm_topk_kernel(const float* __restrict__ corr, int npos, int k, float* __restrict__ val, int* __restrict__ idx) {
   __shared__ float sv[256];
   __shared__ int si[256];
@@ -185,14 +197,14 @@ __global__ __launch_bounds__(256) void pm_topk_kernel(const float* __restrict__ 
       bool skip = false;
       for (int t = 0; t < kk; ++t) skip = skip || (taken_i[t] == i);
       if (skip) continue;
-      if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
+      if (pm_topk_before(v, i, bv, bi)) { bv = v; bi = i; }
     }
     sv[threadIdx.x] = bv; si[threadIdx.x] = bi;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
       if (threadIdx.x < o) {
         const float v2 = sv[threadIdx.x + o]; const int i2 = si[threadIdx.x + o];
-        if (v2 > sv[threadIdx.x] || (v2 == sv[threadIdx.x] && i2 < si[threadIdx.x])) { sv[threadIdx.x] = v2; si[threadIdx.x] = i2; }
+        if (pm_topk_before(v2, i2, sv[threadIdx.x], si[threadIdx.x])) { sv[threadIdx.x] = v2; si[threadIdx.x] = i2; }
       }
       __syncthreads();
     }
@@ -205,6 +217,8 @@ __global__ __launch_bounds__(256) void pm_topk_kernel(const float* __restrict__ 
 
 // out[c][by*ph+dy][bx*pw+dx] = sum_j w_j * y[c][iy_j+dy][ix_j+dx], w = softmax(val*temperature) over the k candidates
 // (temperature < 0 -> k must be 1 and the weight is 1: SI_Finder_at_Image_Domain)
+// Precondition: every idx is a position of the (H-ph+1) x cw map of THIS y, 0 <= idx < (H-ph+1)*cw (pm_topk's output on such a map
+// is); the kernel does not check it.
 __global__ void pm_gather_kernel(const float* __restrict__ y, int C, int H, int W, int ph, int pw, int cw, const float* __restrict__ val,
                                  const int* __restrict__ idx, int k, float temperature, float* __restrict__ out) {
   const int bw = W / pw;

@@ -69,6 +69,10 @@ def SI_Wraper(cross_corr, patch_h, patch_w, patchs_num, y, k=1, temperature=15, 
     y = _chk(y, "SI_Wraper")
     _, C, H, W = y.shape
     assert patchs_num == (H // patch_h) * (W // patch_w) == cross_corr.shape[1]
+    # the gather trusts its indices: in-range positions of a map of another size would point outside y
+    if tuple(cross_corr.shape[2:]) != (H - patch_h + 1, W - patch_w + 1):
+        raise _lib.ClcError(f"SI_Wraper: cross_corr map {tuple(cross_corr.shape[2:])} is not y's "
+                            f"(H - patch_h + 1, W - patch_w + 1) = {(H - patch_h + 1, W - patch_w + 1)}")
     val, idx = _topk(cross_corr, k)
     if is_stack:
         out = torch.empty((1, k * C, H, W), device=y.device, dtype=torch.float32)

@@ -8,7 +8,8 @@ reference frames handed to CLC.forward().  In the reference this runs per sample
 
 Here the bank lives in HBM and a whole batch of queries is answered by one GEMM on the f32-MFMA convolution kernel
 (scores = 2 q.r - |r|^2, the 1x1-convolution path of libclc_hip.so) plus the tie-stable top-k kernel of the patch-matching
-module (clc_pm_topk: equal scores -> lowest index, like a stable sort of the distances).  Clustering itself stays the
+module (clc_pm_topk: equal scores -> lowest index, like a stable sort of the distances; a query that holds a NaN has NaN scores
+only, which rank as equal: its indices are the first rows of the bank, never out of range).  Clustering itself stays the
 reference's own sklearn call (same estimator, same random_state) so that the representatives are the reference's; the
 member-closest-to-centre step runs on the device.  `method="device"` is the opt-in alternative that never leaves the GPU: full-batch
 Lloyd k-means on the kernels of clc_amd.kmeans (its representatives are NOT the reference's).

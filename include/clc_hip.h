@@ -437,7 +437,12 @@ int clc_clm_fuse_bwd(const float* const* feats, const float* const* atts, int M,
  * clc_pm_gauss_mask: create_gaussian_masks(img_h, img_w, ph, pw) -> [P, H-ph+1, W-pw+1]            (:779-807)
  * clc_pm_pearson:    L2_or_pearson_corr(q [P,C,ph,pw], y [C,H,W]) (* mask) -> [P, H-ph+1, W-pw+1]   (:854-910)
  * clc_pm_topk:       top-k positions per patch (values, flat indices), ties -> lowest index       (:105, :225)
- * clc_pm_gather:     SI_Wraper / SI_Finder patch gather + re-tiling; temperature < 0: plain argmax copy (k = 1) */
+ *                    Ordering (torch.topk / torch.argmax): NaN ranks above +inf, +inf above every finite value; equal entries
+ *                    (all NaNs count as equal) -> lowest index first.  1 <= k <= min(8, npos): every index written is in
+ *                    [0, npos) and no index repeats within a row, whatever the floats hold.
+ * clc_pm_gather:     SI_Wraper / SI_Finder patch gather + re-tiling; temperature < 0: plain argmax copy (k = 1)
+ *                    PRECONDITION (not checked on the device): every idx is a flat position of the (H-ph+1) x (W-pw+1) map of
+ *                    this y, 0 <= idx < (H-ph+1)*(W-pw+1); an index outside it reads outside y. */
 int clc_pm_prep(const float* x, float* out, int n_img, int H, int W, float in_scale, clc_stream_t stream);
 int clc_pm_gauss_mask(float* out, int img_h, int img_w, int ph, int pw, clc_stream_t stream);
 size_t clc_pm_pearson_workspace_bytes(int P, int C, int H, int W, int ph, int pw);

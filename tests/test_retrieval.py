@@ -42,6 +42,43 @@ def test_kneighbors_matches_sklearn(dev, n, d, k):
 
 
 @pytest.mark.gpu
+def test_kneighbors_identical_rows_lowest_index_first(dev):
+    """three identical bank rows are at the same distance of any query: they come out lowest row index first (clc_pm_topk's tie rule)"""
+    from clc_amd.retrieval import ReferenceIndex
+
+    bank = _bank(64, 128, 7)
+    bank[20] = bank[41] = bank[5]
+    ix = ReferenceIndex(bank, {i: f"k{i}" for i in range(64)}, n_refs=3, device=dev)
+    dist, idx = ix.kneighbors(bank[41])
+    assert idx.cpu().tolist() == [[5, 20, 41]]
+    assert float(dist.max()) < 0.05
+    assert ix.query(bank[20:21]) == [["k5", "k20", "k41"]]
+
+
+@pytest.mark.gpu
+def test_kneighbors_nan_query_stays_in_range(dev):
+    """a NaN in one query makes its whole score row NaN: clc_pm_topk ranks NaN like torch.topk (above +inf, lowest index first), so the
+    indices stay rows of the bank and query() finds their keys"""
+    from clc_amd.retrieval import ReferenceIndex
+
+    n, k = 64, 4
+    bank, q = _bank(n, 128, 8), _bank(33, 128, 9)
+    q[2, 17] = np.nan
+    keys = {i: f"k{i}" for i in range(n)}
+    ix = ReferenceIndex(bank, keys, n_refs=k, device=dev)
+    _, idx = ix.kneighbors(q)
+    idx = idx.cpu().numpy()
+    assert idx.shape == (33, k) and idx.min() >= 0 and idx.max() < n, idx
+    assert all(len(set(row.tolist())) == k for row in idx)
+    assert idx[2].tolist() == [0, 1, 2, 3]               # every score of that query is NaN: all equal
+    clean = [i for i in range(33) if i != 2]             # the other queries' answers are their own
+    d = ((q[clean, None, :].astype(np.float64) - bank[None].astype(np.float64)) ** 2).sum(-1)
+    assert np.array_equal(idx[clean], np.argsort(d, axis=1, kind="stable")[:, :k])
+    names = ix.query(q)                                  # no KeyError
+    assert names == [[keys[int(j)] for j in row] for row in idx]
+
+
+@pytest.mark.gpu
 def test_cluster_representatives_match_reference_rule(dev):
     """given the clustering (labels, centres), the representatives are the members closest to their centres
     (dataloader_ref_cluster.py:123-133) and the thinned bank answers queries like sklearn on the same representatives."""
