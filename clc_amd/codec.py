@@ -13,6 +13,11 @@ file.  Same bitstreams, re-staged for the MI355X:
               slices < i), so a host decoder forces one device->host->device hop per slice; everything between two hops is one
               captured graph (6 graphs per signature), the hops use pinned buffers, and the images of a batch are decoded in
               parallel (one decoder state per image).
+  lanes=W     the opt-in LANES format of the y string (include/clc_hip.h): W wave streams of 64 rANS lanes per image, the
+              slices as segments in NHWC order.  compress codes y inside its graph (clc_rans_lanes_encode, clc_rans_lanes_pack: two
+              device->host copies, the header with the z symbols and the packed words); decompress is ONE pinned upload and ONE
+              replay of ONE graph with the coder inside every slice step (clc_rans_lanes_decode_gauss): no copy back, no
+              synchronize; check=True adds one download of the coder's end states after the replay is issued.
   container   `pack` / `unpack` / `write_file` / `read_file`: a self-describing byte layout around {"strings", "shape"}
               (the reference only counts len(strings[k][0]), eval_CLC.py:337).
 
@@ -30,6 +35,7 @@ import numpy as np
 import torch
 
 from . import ans, ops
+from .models import coding
 from .ops import CL
 from .refbank import BankMismatch  # noqa: F401  (raised by CodecEngine.decompress(items, bank=...))
 
@@ -264,9 +270,10 @@ class CodecEngine:
         B = pl.slot_idx.shape[0]
         return self.model._ref_from_latents(ops.gather_slots(pl.arena, pl.slot_idx, B, pl.R), pl.R)
 
-    def _build_encoder(self, x, refs, bank=None):
+    def _build_encoder(self, x, refs, bank=None, lanes=None):
         m = self.model
         pl = _Plan()
+        pl.lanes = lanes
         pl.kernel_config = kernel_config()
         pl.x = x.clone()
         pl.refs = [r.clone() for r in refs] if refs is not None else None
@@ -292,9 +299,12 @@ class CodecEngine:
             for i, y_slice in enumerate(y.chunk(S, 1)):
                 mean_support, mu, scale = m._slice_params(i, latent_means, latent_scales, y_hat_slices, ref_features, y_shape)
                 sym, idx, y_hat_slice = m.gaussian_conditional.quantize_and_index(y_slice, mu, scale)
-                syms.append(sym.contiguous())
-                idxs.append(idx.contiguous())
+                # (sym, idx: NCHW views of NHWC int32 buffers — the lanes stream takes them as they lie, the default in NCHW order)
+                syms.append(sym if lanes is not None else sym.contiguous())
+                idxs.append(idx if lanes is not None else idx.contiguous())
                 y_hat_slices.append(m._refine(i, mean_support, y_hat_slice, ref_features))
+            if lanes is not None:
+                return self._lanes_encode(pl, syms, idxs, z_sym.contiguous().reshape(B, -1)), tuple(z.shape[-2:])
             # per image contiguous: [B][slice][C/S][h][w] in the reference's NCHW reshape(-1) order
             ys = torch.stack(syms, dim=1).reshape(B, -1)
             yi = torch.stack(idxs, dim=1).reshape(B, -1)
@@ -303,11 +313,35 @@ class CodecEngine:
 
         pl.graph, (pl.packed, pl.zshape) = self._capture(run)
         pl.run = run
+        if lanes is not None:
+            pl.small_host = torch.empty(pl.packed[0].shape, dtype=torch.int32).pin_memory()
+            pl.words_host = None   # pinned, grown to the largest total seen
+            C = self.zc
+            pl.zidx = np.ascontiguousarray(np.broadcast_to(np.arange(C, dtype=np.int32).reshape(C, 1, 1), (C,) + pl.zshape)).reshape(-1)
+            return pl
         pl.host = torch.empty(pl.packed.shape, dtype=torch.int32).pin_memory()
         pl.ny = (pl.packed.shape[1] - self.zc * pl.zshape[0] * pl.zshape[1]) // 2
         C = self.zc
         pl.zidx = np.ascontiguousarray(np.broadcast_to(np.arange(C, dtype=np.int32).reshape(C, 1, 1), (C,) + pl.zshape)).reshape(-1)
         return pl
+
+    def _lanes_encode(self, pl, syms, idxs, zs):
+        """inside the encoder's graph: the slices' NHWC symbol / index buffers stacked to [B][T], clc_rans_lanes_encode over the slices as
+        segments, clc_rans_lanes_pack -> (small = [B W counts | total | z symbols], the packed words)"""
+        gc = self.model.gaussian_conditional
+        B, W = zs.shape[0], pl.lanes
+        flat = lambda ts: torch.cat([t.permute(0, 2, 3, 1).reshape(B, -1) for t in ts], dim=1)   # (views of the NHWC int32 buffers)
+        ys, yi = flat(syms), flat(idxs)
+        segments = [int(t[0].numel()) for t in syms]
+        if getattr(pl, "regions", None) is None:   # (outside the capture: the first warm-up pass)
+            pl.regions = ops.rans_lanes_regions(segments, W, B)
+            pl.regions_dev = torch.from_numpy(pl.regions).to(zs.device)
+        out, _, result = ops.rans_lanes_encode(ys, yi, segments, W, (gc._quantized_cdf, gc._cdf_length, gc._offset), regions=pl.regions,
+                                               regions_dev=pl.regions_dev)
+        small = torch.empty((B * W + 1 + zs.numel(),), device=zs.device, dtype=torch.int32)
+        packed, _ = ops.rans_lanes_pack(out, result, header=small[:B * W + 1])
+        small[B * W + 1:].copy_(zs.reshape(-1))
+        return small, packed
 
     def _bank_model(self, bank):
         m = self.model
@@ -317,21 +351,25 @@ class CodecEngine:
             raise ValueError("CodecEngine: the bank was built for another model")
 
     @torch.no_grad()
-    def compress(self, x, ref_frames: Optional[Sequence[torch.Tensor]] = None, *, ref_keys=None, bank=None, image_hw=None) -> List[dict]:
+    def compress(self, x, ref_frames: Optional[Sequence[torch.Tensor]] = None, *, ref_keys=None, bank=None, image_hw=None,
+                 lanes=None) -> List[dict]:
         """x [B,3,H,W] (H, W multiples of 128 after eval.pad) -> one {"strings": [[y], [z]], "shape"} per image.
         Bank path (clc_amd.refbank.ReferenceBank): ref_keys = one list of R bank keys per image, image_hw = the size the references are
         resized to before padding (default: x's); the latents come from the bank's cache and the results carry `ref_ids` (indexes into
-        bank.keys), `bank_id` and `image_hw` besides, which pack_item() writes as a version-3 container."""
+        bank.keys), `bank_id` and `image_hw` besides, which pack_item() writes as a version-3 container.
+        lanes=W (1 .. 16): the y strings in the lanes format, coded on the device inside the graph; the results carry "lanes": W, which
+        decompress must be given.  The z strings are the default's."""
+        Wn = coding.lanes_count(lanes, "CodecEngine.compress")
         if bank is not None or ref_keys is not None:
-            return self._compress_bank(x, ref_frames, ref_keys, bank, image_hw)
+            return self._compress_bank(x, ref_frames, ref_keys, bank, image_hw, Wn)
         refs = list(ref_frames) if ref_frames else None
         if not getattr(self.model, "use_ref", True) or not hasattr(self.model, "ref_encoder"):
             refs = None
-        sig = self._sig(x, refs)
-        pl = self._plan(self._enc, sig, lambda: self._build_encoder(x, refs))
+        sig = self._sig(x, refs) if Wn is None else self._sig(x, refs) + (("lanes", Wn),)
+        pl = self._plan(self._enc, sig, lambda: self._build_encoder(x, refs, lanes=Wn))
         return self._run_encoder(pl, x, refs)
 
-    def _compress_bank(self, x, ref_frames, ref_keys, bank, image_hw):
+    def _compress_bank(self, x, ref_frames, ref_keys, bank, image_hw, lanes=None):
         if bank is None or ref_keys is None or ref_frames:
             raise ValueError("CodecEngine.compress: the bank path takes ref_keys AND bank, and no ref_frames")
         self._bank_model(bank)
@@ -343,8 +381,8 @@ class CodecEngine:
         if ((hw[0] + 127) // 128 * 128, (hw[1] + 127) // 128 * 128) != tuple(x.shape[-2:]):
             raise ValueError(f"CodecEngine.compress: image_hw {hw} does not pad to the input's size {tuple(x.shape[-2:])}")
         arena, slots = bank.lookup(rows, hw)
-        sig = (tuple(x.shape), len(rows[0]), bank, kernel_config())
-        pl = self._plan(self._enc, sig, lambda: self._build_encoder(x, None, (arena, slots)))
+        sig = (tuple(x.shape), len(rows[0]), bank, kernel_config()) + (() if lanes is None else (("lanes", lanes),))
+        pl = self._plan(self._enc, sig, lambda: self._build_encoder(x, None, (arena, slots), lanes=lanes))
         self._set_slots(pl, arena, slots)
         outs = self._run_encoder(pl, x, None)
         for o, r in zip(outs, rows):
@@ -361,6 +399,8 @@ class CodecEngine:
             pl.graph.replay()
         else:
             pl.packed, _ = pl.run()
+        if pl.lanes is not None:
+            return self._finish_lanes_encoder(pl, t0)
         pl.host.copy_(pl.packed, non_blocking=True)
         torch.cuda.current_stream().synchronize()        # the ONE device->host hop of the encoder
         t1 = time.perf_counter()
@@ -378,7 +418,121 @@ class CodecEngine:
         # (a replayed graph holds the kernels of the state it was CAPTURED under: plans are keyed by it, see _sig)
         return [{"strings": [[ys], [zs]], "shape": torch.Size(pl.zshape), "kernel_config": pl.kernel_config} for ys, zs in streams]
 
+    def _finish_lanes_encoder(self, pl, t0):
+        """the host half of compress(lanes=W): the header copy (counts, total, z symbols), the copy of `total` words, the containers"""
+        small, packed = pl.packed
+        B, W = pl.x.shape[0], pl.lanes
+        stream = torch.cuda.current_stream()
+        pl.small_host.copy_(small, non_blocking=True)
+        stream.synchronize()
+        head = pl.small_host.numpy()
+        total = int(head[B * W])
+        if total > packed.numel():
+            raise ValueError(f"compress: the wave streams hold {total} words, the packed buffer {packed.numel()}")
+        if pl.words_host is None or pl.words_host.numel() < total:
+            pl.words_host = torch.empty((max(total, 1) * 5 // 4 + 1024,), dtype=torch.int32).pin_memory()
+        if (head[:B * W] >= 0).all():
+            pl.words_host[:total].copy_(packed[:total], non_blocking=True)
+            stream.synchronize()
+        t1 = time.perf_counter()
+        ys = coding.lanes_strings(head, pl.words_host.numpy()[:total], B, W)   # (raises by name on a negative code)
+        ecdf, eln, eoff = self.model.entropy_bottleneck.host_tables()
+        zsym = head[B * W + 1:].reshape(B, -1)
+        enc_z = lambda b: ans.encode(zsym[b], pl.zidx, ecdf, eln, eoff)
+        zs = list(self.pool.map(enc_z, range(B))) if B > 1 else [enc_z(0)]
+        self.last = {"op": "compress", "device_ms": (t1 - t0) * 1e3, "rans_ms": (time.perf_counter() - t1) * 1e3, "hops": 2, "lanes": W}
+        return [{"strings": [[y], [z]], "shape": torch.Size(pl.zshape), "kernel_config": pl.kernel_config, "lanes": W} for y, z in zip(ys, zs)]
+
     # ---------------------------------------------------------------- decoder
+    def _build_decoder_lanes(self, B, zshape, refs, dev, W, cap_words, bank=None):
+        """The lanes decoder: ONE graph — hyper-synthesis, per slice the parameter nets, clc_rans_lanes_decode_gauss and the refinement,
+        the synthesis transform — over a plan-owned upload image [states | spans | cap_words words] at a fixed device address."""
+        m = self.model
+        S = m.num_slices
+        pl = _Plan()
+        pl.lanes, pl.cap_words = W, int(cap_words)
+        pl.refs = [r.clone() for r in refs] if refs is not None else None
+        if bank is not None:
+            self._bank_slots(pl, *bank)
+        pl.z_in = torch.zeros((B, self.zc) + tuple(zshape), dtype=torch.int32, device=dev)
+        pl.z_host = torch.empty(pl.z_in.shape, dtype=torch.int32).pin_memory()
+        n_state = 2 * ans.LANES
+        size = (n_state + 4) * B * W + pl.cap_words
+        pl.image = torch.zeros((size,), dtype=torch.int32, device=dev)   # (all zero: empty spans, which read nothing)
+        pl.image_host = torch.zeros((size,), dtype=torch.int32).pin_memory()
+        pl.state, pl.spans, pl.words = coding.stream_views(pl.image, B, W, n_state)
+        y_shape = [zshape[0] * 4, zshape[1] * 4]
+        gc = m.gaussian_conditional
+        tables = (gc._quantized_cdf, gc._cdf_length, gc._offset)
+
+        @torch.no_grad()
+        def run():
+            ref = self._bank_features(pl) if bank is not None else m._ref(pl.refs)
+            med = m.entropy_bottleneck._get_medians().reshape(1, -1, 1, 1)
+            z_hat = (pl.z_in.float() + med).contiguous(memory_format=CL)
+            ls = m.h_scale_s(z_hat)
+            lm = m.h_mean_s(z_hat)
+            y_hat = []
+            for i in range(S):
+                mean_support, mu, scale = m._slice_params(i, lm, ls, y_hat, ref, y_shape)
+                y_hat_slice = ops.rans_lanes_decode_gauss(scale, mu, gc.scale_table, tables, pl.words, pl.spans, pl.state)
+                y_hat.append(m._refine(i, mean_support, y_hat_slice, ref))
+            return m.g_s(torch.cat(y_hat, dim=1)).clamp_(0, 1)
+
+        pl.graph, pl.out = self._capture(run)
+        pl.run = run
+        return pl
+
+    lanes_words_slack = 1.5   # a lanes decoder plan's words buffer holds this multiple of what the batch that built it needed
+
+    def _decompress_lanes(self, items, pl_for, W, check):
+        """decompress(lanes=W) behind the argument checks; pl_for(cap_words, rebuild) -> the plan"""
+        m = self.model
+        B = len(items)
+        tm = time.perf_counter()
+        subs = coding.lanes_parse([it["strings"][0][0] for it in items], W)   # the headers, before any device work
+        image = coding.stream_image(subs, 2 * ans.LANES)
+        head = (2 * ans.LANES + 4) * B * W
+        need = image.size - head
+        pl = pl_for(max(need, int(need * self.lanes_words_slack)), False)
+        rebuilt = False
+        if getattr(pl, "uploaded", None) is not None:
+            pl.uploaded.synchronize()   # the previous call's uploads (not its graph) may still be reading the pinned pages written below
+        if need > pl.cap_words:   # never truncated: a larger buffer, a new graph
+            pl = pl_for(max(need, int(need * self.lanes_words_slack)), True)
+            rebuilt = True
+        ecdf, eln, eoff = m.entropy_bottleneck.host_tables()
+        C = self.zc
+        zshape = tuple(pl.z_in.shape[2:])
+        zidx = np.ascontiguousarray(np.broadcast_to(np.arange(C, dtype=np.int32).reshape(C, 1, 1), (C,) + zshape)).reshape(-1)
+        zh = pl.z_host.numpy()
+
+        def dec_z(b):
+            zh[b] = ans.decode(items[b]["strings"][1][0], zidx, ecdf, eln, eoff).reshape(zh.shape[1:])
+
+        if B > 1:
+            list(self.pool.map(dec_z, range(B)))
+        else:
+            dec_z(0)
+        t_rans = time.perf_counter() - tm
+        tm = time.perf_counter()
+        pl.image_host.numpy()[:image.size] = image
+        pl.z_in.copy_(pl.z_host, non_blocking=True)
+        pl.image[:image.size].copy_(pl.image_host[:image.size], non_blocking=True)   # THE upload: states, spans, words
+        if getattr(pl, "uploaded", None) is None:
+            pl.uploaded = torch.cuda.Event()
+        pl.uploaded.record()
+        if pl.graph is not None:
+            pl.graph.replay()
+            res = pl.out.clone()
+        else:
+            res = pl.run()
+        self.last = {"op": "decompress", "device_ms": 0.0, "rans_ms": t_rans * 1e3, "hops": 1 if check else 0, "lanes": W,
+                     "tail_issue_ms": (time.perf_counter() - tm) * 1e3, "plan_rebuilt": rebuilt}
+        if check:   # ONE download, after everything has been issued
+            coding.lanes_check(pl.state, subs)
+        return res
+
     def _build_decoder(self, B, zshape, refs, dev, bank=None):
         m = self.model
         S = m.num_slices
@@ -462,11 +616,23 @@ class CodecEngine:
         return rows, hw
 
     @torch.no_grad()
-    def decompress(self, items: Sequence[dict], ref_frames: Optional[Sequence[torch.Tensor]] = None, *, bank=None) -> torch.Tensor:
+    def decompress(self, items: Sequence[dict], ref_frames: Optional[Sequence[torch.Tensor]] = None, *, bank=None, lanes=None,
+                   check=True) -> torch.Tensor:
         """items: outputs of compress() (or unpack_item()ed containers, whose kernel-config tag is checked here) for B images of one shape -> x_hat [B,3,H,W] clamped to [0,1].
         bank: decode items of the bank path without reference tensors: their ref ids name the bank's keys (BankMismatch for another
-        bank's id), the bank prepares and encodes (or finds cached) the references itself."""
+        bank's id), the bank prepares and encodes (or finds cached) the references itself.
+        lanes=W: the items of compress(lanes=W).  Their headers are parsed and z is decoded on the host; then one pinned upload and ONE
+        graph replay, no copy back, no synchronize (self.last["hops"] == 0).  check=True (default; lanes only) downloads the coder's end
+        states once, after the replay is issued, and raises ValueError naming the image and the wave streams that did not end where a
+        whole stream ends (hops == 1).  Refused by name: lanes outside 1 .. 16 or other than an item's "lanes" / header, a lanes
+        string without lanes=, a default string with it."""
         m = self.model
+        Wn = coding.lanes_count(lanes, "CodecEngine.decompress")
+        for k, it in enumerate(items):
+            if it.get("lanes") is not None and it["lanes"] != Wn:
+                raise ValueError(f"decompress: item {k} was coded with lanes = {it['lanes']}, the call says lanes = {Wn}")
+        if Wn is None:
+            coding.refuse_lanes_strings([it["strings"][0][0] for it in items])
         for k, it in enumerate(items):      # items that came out of a container carry its header: refuse another kernel generation's
             if it.get("meta") is not None:
                 check_kernel_config(it["meta"], f"item {k}")
@@ -482,6 +648,14 @@ class CodecEngine:
             rows, hw = self._bank_rows(items, bank, zshape)
             arena, slots = bank.lookup(rows, hw)
             sig = (B, zshape, len(rows[0]), bank, kernel_config())
+            if Wn is not None:
+                def pl_for(cap, rebuild):
+                    if rebuild:
+                        self._dec.pop(sig + (("lanes", Wn),), None)
+                    pl = self._plan(self._dec, sig + (("lanes", Wn),), lambda: self._build_decoder_lanes(B, zshape, None, dev, Wn, cap, (arena, slots)))
+                    self._set_slots(pl, arena, slots)
+                    return pl
+                return self._decompress_lanes(items, pl_for, Wn, check)
             pl = self._plan(self._dec, sig, lambda: self._build_decoder(B, zshape, None, dev, (arena, slots)))
             self._set_slots(pl, arena, slots)
             refs = None
@@ -490,6 +664,16 @@ class CodecEngine:
             if not getattr(m, "use_ref", True) or not hasattr(m, "ref_encoder"):
                 refs = None
             sig = (B, zshape, None if refs is None else tuple(tuple(r.shape) for r in refs), kernel_config())
+            if Wn is not None:
+                def pl_for(cap, rebuild):
+                    if rebuild:
+                        self._dec.pop(sig + (("lanes", Wn),), None)
+                    pl = self._plan(self._dec, sig + (("lanes", Wn),), lambda: self._build_decoder_lanes(B, zshape, refs, dev, Wn, cap))
+                    if refs is not None:
+                        for d, r in zip(pl.refs, refs):
+                            d.copy_(r, non_blocking=True)
+                    return pl
+                return self._decompress_lanes(items, pl_for, Wn, check)
             pl = self._plan(self._dec, sig, lambda: self._build_decoder(B, zshape, refs, dev))
         if refs is not None:
             for d, r in zip(pl.refs, refs):

@@ -7,7 +7,8 @@
 // escape; the symbol update, renorm and get_bits of clc_rans_decoder_decode), and the host coder of the same format
 // (clc_rans_lanes_encode_host, clc_rans_lanes_decoder_*) is the oracle: same words, same symbols, same final states.
 //
-// No LDS, no barrier, no atomics, no wave waits on another; every loop is bounded by a constant or by the symbol count.
+// No atomics, no wave waits on another; every loop is bounded by a constant or by the symbol count.  The two kernels of the table-coded
+// stream use no LDS and no barrier; rans_lanes_decode_gauss_kernel keeps the scale table in LDS (one barrier before its first round).
 #include "common.h"
 
 namespace {
@@ -217,6 +218,224 @@ __global__ __launch_bounds__(64) void rans_lanes_encode_kernel(const LanesEncArg
   }
 }
 
+// ---- the slice step of the Gaussian-conditional models: index, decode, de-quantise in one launch ----
+// rans_lanes_decode_kernel with the row index formed here (quantize_build_indexes_kernel's, entropy.hip) and the symbol leaving as
+// y_hat = (float)symbol + mu.  The coder's part is that kernel's, statement for statement: it is repeated, not shared, so that the
+// kernel of the table-coded stream keeps its code.
+constexpr float kScaleBound = 0.11f;
+constexpr int kMaxScales = 256;
+
+struct LanesGaussArgs {
+  const float* scale; long ldsc;
+  const float* mu; long ldmu;
+  int C, n, W;
+  const float* table; int n_scales;
+  LanesTables t;
+  const uint32_t* words;
+  const int32_t* spans;
+  uint32_t* state;
+  float* y_hat; long ldh;
+  int32_t* symbols; long ld_sym;   // symbols may be null
+};
+
+__global__ __launch_bounds__(64) void rans_lanes_decode_gauss_kernel(const LanesGaussArgs a) {
+  __shared__ float tb[kMaxScales];
+  const int lane = threadIdx.x;
+  const int ns1 = a.n_scales - 1;
+  for (int i = lane; i < ns1; i += kLanes) tb[i] = a.table[i];
+  __syncthreads();
+  const int wid = blockIdx.x;   // (b, w)
+  const int b = wid / a.W, w = wid - b * a.W;
+  const int first = a.spans[2 * wid], cnt = a.spans[2 * wid + 1];
+  const uint32_t* wp = a.words + (first > 0 ? first : 0);
+  const uint32_t count = (first >= 0 && cnt > 0) ? (uint32_t)cnt : 0u;   // (a negative first or count reads nothing)
+  uint32_t* st = a.state + (long)kStateWords * wid;
+  uint64_t x = (uint64_t)st[2 * lane] | ((uint64_t)st[2 * lane + 1] << 32);
+  uint32_t pos = st[2 * kLanes];
+  const long row0 = (long)b * (a.n / a.C);   // the image's first row of the [rows][C] maps
+  const unsigned long long below = (1ull << lane) - 1ull;
+  const int chunks = (a.n + kLanes - 1) / kLanes;
+  auto take = [&](bool need) {
+    const unsigned long long m = __ballot(need);
+    if (need) {
+      const uint32_t i = pos + (uint32_t)__popcll(m & below);
+      const uint32_t v = i < count ? wp[i] : 0u;
+      x = (x << 32) | v;
+    }
+    pos += (uint32_t)__popcll(m);
+  };
+  // A round's row does not depend on the coder state, but finding it is a chain of its own — the scale's load, a search of up to eight
+  // dependent LDS reads, the loads of cdf size and offset — and one wave alone hides none of it behind anything.  So the wave's rounds
+  // run in GROUPS of kGroup: at a group's last round the indexes of the next group's rounds are searched together (kGroup independent
+  // searches, step by step side by side, so that one LDS latency serves them all) from scales that were loaded a whole group earlier,
+  // and the scales of the group after that are requested.  Per round what is left is the (size, offset, mu) fetch one round ahead, as
+  // in rans_lanes_decode_kernel.
+  constexpr int kGroup = 4;
+  int top = 1;   // the largest power of two <= ns1
+  while (2 * top <= ns1) top *= 2;
+  // (pixel, channel) of a lane's symbol advance by a constant from one of the wave's rounds to the next: no division inside the loop
+  const int step_p = (a.W * kLanes) / a.C, step_c = (a.W * kLanes) % a.C;
+  struct Place { int p, c; };
+  auto advance = [&](Place& at) {
+    at.p += step_p; at.c += step_c;
+    if (at.c >= a.C) { at.c -= a.C; at.p += 1; }
+  };
+  const int j0 = w * kLanes + lane;   // (< 2^10 + 64)
+  Place ahead = {j0 / a.C, j0 % a.C}, row = ahead;   // of the next round load_scales / fetch_row is called for
+  float sc[kGroup] = {};
+  auto load_scales = [&](int q0) {   // the scales of rounds q0, q0 + W, ...: called for consecutive groups
+#pragma unroll
+    for (int g = 0; g < kGroup; ++g) {
+      const long q = (long)q0 + (long)g * a.W;
+      const long j = q * kLanes + lane;
+      sc[g] = 0.f;
+      if (q < chunks && j < a.n) sc[g] = a.scale[(row0 + ahead.p) * a.ldsc + ahead.c];
+      advance(ahead);
+    }
+  };
+  // n_scales - 1 - #{k < n_scales - 1: sg <= table[k]}.  Over a non-decreasing table the k that do NOT count are a prefix, and its
+  // length is the index: the largest pos with !(sg <= table[pos - 1]), built from the top bit down.  (A NaN scale: every pos, ns1.)
+  auto search = [&]() -> uint32_t {   // -> the kGroup indexes, a byte each
+    float sg[kGroup];
+    int pos[kGroup];
+#pragma unroll
+    for (int g = 0; g < kGroup; ++g) { sg[g] = fmaxf(sc[g], kScaleBound); pos[g] = 0; }
+#pragma unroll 1
+    for (int step = top; step >= 1; step >>= 1) {
+#pragma unroll
+      for (int g = 0; g < kGroup; ++g) {
+        const int t = pos[g] + step;
+        const float e = tb[(t < ns1 ? t : ns1) - 1];
+        if (t <= ns1 && !(sg[g] <= e)) pos[g] = t;
+      }
+    }
+    uint32_t pack = 0;
+#pragma unroll
+    for (int g = 0; g < kGroup; ++g) pack |= (uint32_t)pos[g] << (8 * g);
+    return pack;
+  };
+  int ci_next = 0, size_next = 2, off_next = 0;
+  long at_next = 0;
+  float mu_next = 0.f;
+  auto fetch_row = [&](int q, int index) {   // called for consecutive rounds
+    const long j = (long)q * kLanes + lane;
+    if (q < chunks && j < a.n) {
+      const long r = row0 + row.p;
+      const int c = row.c;
+      ci_next = clamp_int(index, 0, a.t.n_rows - 1);   // an index outside the cdf table is clamped into it
+      size_next = clamp_int(a.t.cdf_sizes[ci_next], 2, a.t.cdf_stride);
+      off_next = a.t.offsets[ci_next];
+      mu_next = a.mu[r * a.ldmu + c];
+      at_next = r * a.ldh + c;
+    }
+    advance(row);
+  };
+  load_scales(w);
+  uint32_t pack = search();
+  load_scales(w + kGroup * a.W);
+  fetch_row(w, (int)(pack & 255u));
+  int g = 0;   // the round's place in its group
+#pragma unroll 1
+  for (int q = w; q < chunks; q += a.W) {
+    const long j = (long)q * kLanes + lane;
+    const bool active = j < a.n;
+    const int ci = ci_next, size = size_next, off = off_next;
+    const long at = at_next;
+    const float m_ = mu_next;
+    g = (g + 1) & (kGroup - 1);
+    if (g == 0) {   // (uniform) the next round opens a group
+      pack = search();
+      load_scales(q + a.W + kGroup * a.W);
+    }
+    fetch_row(q + a.W, (int)((pack >> (8 * g)) & 255u));
+    const int32_t* cdf = a.t.cdfs + (long)ci * a.t.cdf_stride;
+    const int maxv = size - 2;
+    int s = 0;
+    if (active) {
+      const uint32_t cf = (uint32_t)x & 0xFFFFu;
+      int lo = 0, hi = maxv;
+#pragma unroll 1
+      for (int it = 0; it < 32 && lo < hi; ++it) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((uint32_t)cdf[mid] <= cf) lo = mid; else hi = mid - 1;
+      }
+      s = lo;
+      const uint32_t start = (uint32_t)cdf[s], freq = (uint32_t)(cdf[s + 1] - cdf[s]);
+      x = (uint64_t)freq * (x >> 16) + cf - start;
+    }
+    take(active && x < kL);
+    const bool esc = active && s == maxv;
+    uint32_t value = (uint32_t)s;
+    if (__ballot(esc)) {
+      int nb = 0, base = 2;
+      uint32_t raw = 0;
+#pragma unroll 1
+      for (int t = 1; t < 19; ++t) {
+        const bool cnt_op = esc && (t == 1 || (t == 2 && nb == 15));
+        const int k = t - base;
+        const bool pay_op = esc && !cnt_op && t >= 2 && k < (nb < 16 ? nb : 16);
+        const bool op = cnt_op || pay_op;
+        if (!__ballot(op)) break;
+        const uint32_t v = (uint32_t)x & 15u;
+        if (op) x >>= 4;
+        take(op && x < kL);
+        if (cnt_op) { nb += (int)v; if (t == 2) base = 3; }
+        if (pay_op && k < 8) raw |= v << (4 * k);
+      }
+      if (esc) value = (raw & 1u) ? ~(raw >> 1) : (raw >> 1) + (uint32_t)maxv;
+    }
+    if (active) {
+      const int32_t sym = (int32_t)(value + (uint32_t)off);
+      a.y_hat[at] = (float)sym + m_;
+      if (a.symbols) a.symbols[(long)b * a.ld_sym + j] = sym;
+    }
+  }
+  st[2 * lane] = (uint32_t)x;
+  st[2 * lane + 1] = (uint32_t)(x >> 32);
+  if (lane == 0) st[2 * kLanes] = pos;
+}
+
+// ---- the encoder's wave streams, back to back ----
+struct LanesPackArgs {
+  const uint32_t* words; long n_words;
+  const int32_t* result;   // [B][W][2]: first word, count — or (code < 0, 0)
+  int n_streams;
+  uint32_t* packed; long capacity;
+  int32_t* header;         // [n_streams + 1]: counts (negative codes as they are), total
+};
+
+__device__ __forceinline__ long wave_sum(long v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, kLanes);
+  return v;
+}
+
+__global__ __launch_bounds__(64) void rans_lanes_pack_kernel(const LanesPackArgs a) {
+  const int lane = threadIdx.x;
+  const int wid = blockIdx.x;
+  auto count_of = [&](int i) -> long {
+    const int f = a.result[2 * i], c = a.result[2 * i + 1];
+    return (f >= 0 && c > 0) ? (long)c : 0l;   // (a code carries no words)
+  };
+  // the wave's own prefix over the counts before it: no wave reads what another wrote
+  long before = 0;
+  for (int i = lane; i < wid; i += kLanes) before += count_of(i);
+  before = wave_sum(before);
+  const int first = a.result[2 * wid];
+  const long cnt = count_of(wid);
+  for (long i = lane; i < cnt; i += kLanes) {
+    const long src = (long)first + i, dst = before + i;
+    if (dst < a.capacity && src < a.n_words) a.packed[dst] = a.words[src];
+  }
+  if (lane == 0) a.header[wid] = first < 0 ? first : (int32_t)cnt;
+  if (wid == 0) {   // (uniform per wave) the total, reported whether or not it fits
+    long total = 0;
+    for (int i = lane; i < a.n_streams; i += kLanes) total += count_of(i);
+    total = wave_sum(total);
+    if (lane == 0) a.header[a.n_streams] = (int32_t)(total < 0x7fffffffl ? total : 0x7fffffffl);
+  }
+}
+
 bool lanes_tables_ok(const int32_t* cdfs, int cdf_stride, int n_rows, const int32_t* cdf_sizes, const int32_t* offsets) {
   return cdfs && cdf_sizes && offsets && cdf_stride >= 2 && n_rows >= 1;
 }
@@ -268,6 +487,48 @@ extern "C" int clc_rans_lanes_encode(const int32_t* symbols, const int32_t* inde
   a.t = {cdfs, cdf_stride, n_rows, cdf_sizes, offsets};
   a.out = out; a.regions = regions; a.result = result; a.W = W; a.segs = segs;
   hipLaunchKernelGGL(rans_lanes_encode_kernel, dim3(B * W), dim3(kLanes), 0, ST, a);
+  CLC_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int clc_rans_lanes_decode_gauss(const float* scale, long ldsc, const float* mu, long ldmu, int C, int n, int B, const float* scale_table,
+                                           int n_scales, const int32_t* cdfs, int cdf_stride, int n_rows, const int32_t* cdf_sizes,
+                                           const int32_t* offsets, const uint32_t* words, const int32_t* spans, clc_rans_lanes_state* state, int W,
+                                           float* y_hat, long ldh, int32_t* symbols, long ld_sym, clc_stream_t stream) {
+  CLC_CHECK(scale && mu && scale_table && words && spans && state && y_hat, "clc_rans_lanes_decode_gauss: null pointer");
+  CLC_CHECK(cdfs && cdf_sizes && offsets, "clc_rans_lanes_decode_gauss: null table pointer");
+  CLC_CHECK(cdf_stride >= 2 && n_rows >= 1, "clc_rans_lanes_decode_gauss: the table needs cdf_stride >= 2 and n_rows >= 1 (got %d, %d)", cdf_stride, n_rows);
+  CLC_CHECK(n_scales > 1 && n_scales <= kMaxScales, "clc_rans_lanes_decode_gauss: n_scales must be between 2 and %d (got %d)", kMaxScales, n_scales);
+  CLC_CHECK(W >= 1 && W <= CLC_RANS_LANES_MAX_W, "clc_rans_lanes_decode_gauss: W must be between 1 and %d waves (got %d)", CLC_RANS_LANES_MAX_W, W);
+  CLC_CHECK(n >= 0 && B > 0, "clc_rans_lanes_decode_gauss: n must not be negative and B must be positive (got %d, %d)", n, B);
+  CLC_CHECK(n < (1 << 30), "clc_rans_lanes_decode_gauss: n must be below 2^30 symbols per image (got %d)", n);
+  CLC_CHECK(C > 0 && n % C == 0, "clc_rans_lanes_decode_gauss: n must be whole rows of C > 0 channels (got n = %d, C = %d)", n, C);
+  CLC_CHECK(ldsc >= C && ldmu >= C && ldh >= C, "clc_rans_lanes_decode_gauss: ldsc, ldmu or ldh < C");
+  CLC_CHECK(!symbols || ld_sym >= n, "clc_rans_lanes_decode_gauss: ld_sym < n");
+  CLC_CHECK((long)B * W < (1l << 24), "clc_rans_lanes_decode_gauss: B * W must be below 2^24");
+  if (n == 0) return 0;   // an empty segment contributes nothing
+  LanesGaussArgs a = {};
+  a.scale = scale; a.ldsc = ldsc; a.mu = mu; a.ldmu = ldmu; a.C = C; a.n = n; a.W = W;
+  a.table = scale_table; a.n_scales = n_scales;
+  a.t = {cdfs, cdf_stride, n_rows, cdf_sizes, offsets};
+  a.words = words; a.spans = spans; a.state = reinterpret_cast<uint32_t*>(state);
+  a.y_hat = y_hat; a.ldh = ldh; a.symbols = symbols; a.ld_sym = ld_sym;
+  hipLaunchKernelGGL(rans_lanes_decode_gauss_kernel, dim3(B * W), dim3(kLanes), 0, ST, a);
+  CLC_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int clc_rans_lanes_pack(const uint32_t* words, long n_words, const int32_t* result, int B, int W, uint32_t* packed, long capacity,
+                                   int32_t* header, clc_stream_t stream) {
+  CLC_CHECK(words && result && packed && header, "clc_rans_lanes_pack: null pointer");
+  CLC_CHECK(W >= 1 && W <= CLC_RANS_LANES_MAX_W, "clc_rans_lanes_pack: W must be between 1 and %d waves (got %d)", CLC_RANS_LANES_MAX_W, W);
+  CLC_CHECK(B > 0, "clc_rans_lanes_pack: B must be positive (got %d)", B);
+  CLC_CHECK((long)B * W < (1l << 24), "clc_rans_lanes_pack: B * W must be below 2^24");
+  CLC_CHECK(n_words >= 0 && n_words < (1l << 31), "clc_rans_lanes_pack: n_words must be between 0 and 2^31 - 1 (got %ld)", n_words);
+  CLC_CHECK(capacity >= 0 && capacity < (1l << 31), "clc_rans_lanes_pack: capacity must be between 0 and 2^31 - 1 words (got %ld)", capacity);
+  LanesPackArgs a = {};
+  a.words = words; a.n_words = n_words; a.result = result; a.n_streams = B * W; a.packed = packed; a.capacity = capacity; a.header = header;
+  hipLaunchKernelGGL(rans_lanes_pack_kernel, dim3(B * W), dim3(kLanes), 0, ST, a);
   CLC_LAUNCH_CHECK();
   return 0;
 }

@@ -29,6 +29,7 @@ from ..entropy_models import EntropyBottleneck, GaussianConditional
 from ..layers import (GELU, ConvTransBlock, Conv2d, ResidualBlockUpsample, ResidualBlockWithStride, SWAtten, conv1x1,
                       conv3x3, subpel_conv3x3)
 from ..ops import ACT_GELU, ACT_HALFTANH, ACT_NONE, CL
+from . import coding
 
 SCALES_MIN, SCALES_MAX, SCALES_LEVELS = 0.11, 256, 64
 CODEC_GRAPH = os.environ.get("CLC_CODEC_GRAPH", "1") != "0"   # compress() / decompress() of one image on captured hipGraph segments
@@ -361,16 +362,38 @@ class _SliceCodec(CompressionModel):
         return eng
 
     @torch.no_grad()
-    def compress(self, x, ref_frames=None):
+    def compress(self, x, ref_frames=None, lanes=None):
+        """lanes=None: the reference's one-stream format.  lanes=W (1 .. 16): THE LANES STREAM (include/clc_hip.h) — the y
+        string of every image is W wave streams of 64 rANS lanes, the slices as segments in NHWC order, coded on the device; the result
+        carries "lanes": W and one y string per image; pass the same W to decompress.  The z strings are the default's."""
+        Wn = coding.lanes_count(lanes, f"{type(self).__name__}.compress")
         if x.shape[0] == 1:
             eng = self._codec_engine(x)
             if eng is not None:
+                if Wn is not None:
+                    o = eng.compress(self._prep(x), ref_frames, lanes=Wn)[0]
+                    return {"strings": o["strings"], "shape": o["shape"], "kernel_config": o["kernel_config"], "lanes": Wn}
                 o = eng.compress(self._prep(x), ref_frames)[0]
                 return {"strings": o["strings"], "shape": o["shape"], "kernel_config": o["kernel_config"]}
+        if Wn is not None:
+            return self._compress_eager(x, ref_frames, lanes=Wn)
         return self._compress_eager(x, ref_frames)
 
     @torch.no_grad()
-    def decompress(self, strings, shape, ref_frames=None):
+    def decompress(self, strings, shape, ref_frames=None, lanes=None, device_coder=True, check=True):
+        """lanes=W: the strings of compress(x, lanes=W); their headers are parsed on the host before any device work.  device_coder=True
+        decodes on the device with the coder inside the slice step (one image: ONE upload and one replay of one graph, no copy back, no
+        synchronize); check=True adds ONE download of the coder's end states after everything is issued and raises ValueError naming the
+        image and the wave streams that did not end where a whole stream ends (not a checksum).  device_coder=False decodes the same
+        format with one ans.LanesDecoder per image and a hop per slice: the oracle and the fallback."""
+        Wn = coding.lanes_count(lanes, f"{type(self).__name__}.decompress")
+        if Wn is not None:
+            if device_coder and len(strings[1]) == 1:
+                eng = self._codec_engine(next(self.parameters()))
+                if eng is not None:
+                    return {"x_hat": eng.decompress([{"strings": strings, "shape": shape}], ref_frames, lanes=Wn, check=check)}
+            return self._decompress_eager(strings, shape, ref_frames, lanes=Wn, device_coder=device_coder, check=check)
+        coding.refuse_lanes_strings(strings[0])
         if len(strings[1]) == 1:
             eng = self._codec_engine(next(self.parameters()))
             if eng is not None:
@@ -378,7 +401,8 @@ class _SliceCodec(CompressionModel):
         return self._decompress_eager(strings, shape, ref_frames)
 
     @torch.no_grad()
-    def _compress_eager(self, x, ref_frames=None):
+    def _compress_eager(self, x, ref_frames=None, lanes=None):
+        Wn = coding.lanes_count(lanes, f"{type(self).__name__}.compress")
         x = self._prep(x)
         ref_features = self._ref(ref_frames)
         y = self.g_a(x)
@@ -399,6 +423,9 @@ class _SliceCodec(CompressionModel):
             y_hat_slices.append(self._refine(i, mean_support, y_hat_slice, ref_features))
         from ..codec import kernel_config
 
+        if Wn is not None:
+            return {"strings": [self._encode_y_lanes(sym_parts, idx_parts, Wn), z_strings], "shape": z.size()[-2:],
+                    "kernel_config": kernel_config(), "lanes": Wn}
         # (`kernel_config`: beyond the reference's two keys — which kernel state encoded, for clc_amd.codec.pack_item)
         return {"strings": [self._encode_y(sym_parts, idx_parts), z_strings], "shape": z.size()[-2:], "kernel_config": kernel_config()}
 
@@ -410,8 +437,63 @@ class _SliceCodec(CompressionModel):
         idx_all = torch.stack([s.contiguous() for s in idx_parts]).cpu().numpy().reshape(-1)
         return [ans.encode(sym_all, idx_all, cdf, cdf_len, off)]
 
+    def _encode_y_lanes(self, sym_parts, idx_parts, W):
+        """Per-slice int32 symbol / index tensors (NCHW views of NHWC buffers) -> one lanes string per image: the slices are the
+        segments, each in the order it lies in memory; one clc_rans_lanes_encode and one clc_rans_lanes_pack for the batch, then two
+        device -> host copies (the header, the packed words)."""
+        gc = self.gaussian_conditional
+        B = sym_parts[0].shape[0]
+        flat = lambda ts: torch.cat([t.permute(0, 2, 3, 1).reshape(B, -1) for t in ts], dim=1)
+        out, _, result = ops.rans_lanes_encode(flat(sym_parts), flat(idx_parts), [int(t[0].numel()) for t in sym_parts], W,
+                                               (gc._quantized_cdf, gc._cdf_length, gc._offset))
+        packed, header = ops.rans_lanes_pack(out, result)
+        head = header.cpu().numpy()
+        total = int(head[B * W])
+        words = packed[:total].cpu().numpy() if (head[:B * W] >= 0).all() else np.zeros(0, np.int32)
+        return coding.lanes_strings(head, words, B, W)
+
     @torch.no_grad()
-    def _decompress_eager(self, strings, shape, ref_frames=None):
+    def _decompress_lanes_eager(self, strings, shape, ref_frames, W, device_coder, check):
+        subs = coding.lanes_parse(strings[0], W)   # the headers, before any device work
+        if len(subs) != len(strings[1]):
+            raise ValueError(f"decompress: {len(subs)} y streams for {len(strings[1])} z streams")
+        ref_features = self._ref(ref_frames)
+        z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
+        latent_scales = self.h_scale_s(z_hat)
+        latent_means = self.h_mean_s(z_hat)
+        B, dev = z_hat.shape[0], z_hat.device
+        y_shape = [z_hat.shape[2] * 4, z_hat.shape[3] * 4]
+        Cs = self.M // self.num_slices
+        n = y_shape[0] * y_shape[1] * Cs
+        gc = self.gaussian_conditional
+        if device_coder:
+            tables = (gc._quantized_cdf, gc._cdf_length, gc._offset)
+            state, spans, words = coding.upload_streams(subs, 2 * ans.LANES, dev)
+        else:
+            state = [ans.LanesDecoder(img) for img in subs]
+            decode = coding.table_decode([d.decode for d in state], gc.host_tables())
+            hop = coding.HostHop(B * n, B * n, dev)
+        y_hat_slices = []
+        for i in range(self.num_slices):
+            mean_support, mu, scale = self._slice_params(i, latent_means, latent_scales, y_hat_slices, ref_features, y_shape)
+            if device_coder:
+                y_hat_slice = ops.rans_lanes_decode_gauss(scale, mu, gc.scale_table, tables, words, spans, state)
+            else:
+                down, up = hop.step(B * n, B * n)
+                down.copy_(gc.build_indexes(scale).permute(0, 2, 3, 1).reshape(-1))   # NHWC: the segment's order
+                hop.run(decode)
+                y_hat_slice = up.view(B, y_shape[0], y_shape[1], Cs).permute(0, 3, 1, 2).float() + mu
+            y_hat_slices.append(self._refine(i, mean_support, y_hat_slice, ref_features))
+        x_hat = self.g_s(torch.cat(y_hat_slices, dim=1)).clamp_(0, 1)
+        if check:
+            coding.lanes_check(state, subs)
+        return {"x_hat": x_hat}
+
+    @torch.no_grad()
+    def _decompress_eager(self, strings, shape, ref_frames=None, lanes=None, device_coder=True, check=True):
+        Wn = coding.lanes_count(lanes, f"{type(self).__name__}.decompress")
+        if Wn is not None:
+            return self._decompress_lanes_eager(strings, shape, ref_frames, Wn, device_coder, check)
         ref_features = self._ref(ref_frames)
         z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
         latent_scales = self.h_scale_s(z_hat)
@@ -541,11 +623,11 @@ class TCM(_SliceCodec):
     def forward(self, x, ref_frames=None):
         return super().forward(x, None)
 
-    def compress(self, x, ref_frames=None):
-        return super().compress(x, None)
+    def compress(self, x, ref_frames=None, lanes=None):
+        return super().compress(x, None, lanes=lanes)
 
-    def decompress(self, strings, shape, ref_frames=None):
-        return super().decompress(strings, shape, None)
+    def decompress(self, strings, shape, ref_frames=None, lanes=None, device_coder=True, check=True):
+        return super().decompress(strings, shape, None, lanes=lanes, device_coder=device_coder, check=check)
 
     def update(self, scale_table=None, force=False):
         if scale_table is None:

@@ -5,6 +5,8 @@ owner here:
   upload), ``open_decoders`` and ``table_decode``.
 * THE UPLOAD IMAGE of a device-decoded batch, ``[states | spans | words]`` in one pinned int32 buffer: ``stream_image`` (numpy),
   ``stream_views``, ``upload_streams``; and the end-state rule of a whole stream, ``check_stream_ends`` / ``device_ends``.
+* THE LANES STRINGS of the slice models (CLC, TCM; model and CodecEngine): ``lanes_count``, ``lanes_parse``, ``refuse_lanes_strings``,
+  ``lanes_strings``, ``lanes_check``.
 * Small pieces: ``linear_filters``, ``CodeInputs._code_inputs``, ``coded_item``.
 
 The kernels, their order and their arguments stay with the models; the multi-stream container is ans.py's.
@@ -138,6 +140,58 @@ def check_stream_ends(x, pos, counts, noun):
                        f"2^31, {int(pos[b, s])} of {int(counts[b, s])} words consumed)")
     if bad:
         raise ValueError("decompress: " + "; ".join(bad) + ": the stream is corrupt, truncated or belongs to other parameters")
+
+
+def lanes_count(lanes, who):
+    """lanes=None: the one-stream format; else the number W of wave streams per image, refused by name outside 1 .. 16"""
+    return None if lanes is None else ans.stream_count(ans.LANES_STREAM, lanes, who, "lanes")
+
+
+def lanes_parse(y_strings, W):
+    """-> per image the W wave streams of its lanes string; a header that disagrees with the caller's W is refused.  Host only."""
+    subs = []
+    for b, blob in enumerate(y_strings):
+        got = ans.lanes_unpack(blob)
+        if len(got) != W:
+            raise ValueError(f"decompress: lanes = {W}, but the header of image {b} says {len(got)} wave streams")
+        subs.append(got)
+    return subs
+
+
+def refuse_lanes_strings(y_strings):
+    """the one-stream decoder was handed a lanes string: refused by name before any device work"""
+    for b, blob in enumerate(y_strings):
+        if bytes(blob[:4]) == ans.LANES_MAGIC:
+            raise ValueError(f"decompress: the y string of image {b} is a lanes stream ({ans.LANES_MAGIC!r}); pass lanes= (its header "
+                             f"says {blob[4] if len(blob) > 4 else '?'} wave streams)")
+
+
+def lanes_strings(header, words, B, W):
+    """What ops.rans_lanes_pack left, on the host — header int32 [B W + 1] (counts or negative codes, total) and the packed words — ->
+    per image its lanes string.  A negative code raises by name."""
+    from .. import lib
+
+    counts = np.asarray(header[:B * W]).reshape(B, W)
+    for b, w in zip(*np.nonzero(counts < 0)):
+        why = "a zero-frequency symbol" if counts[b, w] == lib.RANS_LANES_ZERO_FREQ else "its region overflowed"
+        raise ValueError(f"compress: image {b}, wave stream {w}: {why} (clc_rans_lanes_encode code {int(counts[b, w])})")
+    words = np.asarray(words).view(np.uint32)
+    if int(counts.sum()) != int(header[B * W]) or words.size < int(counts.sum()):
+        raise ValueError(f"compress: the packed wave streams hold {words.size} words, their header counts {int(counts.sum())} (total {int(header[B * W])})")
+    ends = np.cumsum(counts.reshape(-1))
+    streams = [words[e - n:e].astype("<u4").tobytes() for e, n in zip(ends, counts.reshape(-1))]
+    return [ans.lanes_pack(streams[b * W:(b + 1) * W]) for b in range(B)]
+
+
+def lanes_check(state, subs):
+    """check_stream_ends over every wave stream's 64 lanes.  state: the device's [B, W, 130] tensor — ONE download — or the host coder's
+    list of ans.LanesDecoder."""
+    if isinstance(state, torch.Tensor):
+        x, pos = device_ends(state)
+    else:
+        ends = [[d.state(w) for w in range(len(img))] for d, img in zip(state, subs)]
+        x, pos = [[e[0] for e in img] for img in ends], [[e[1] for e in img] for img in ends]
+    check_stream_ends(x, pos, [[len(blob) // 4 for blob in img] for img in subs], "wave stream")
 
 
 def linear_filters(layers):

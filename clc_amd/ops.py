@@ -3053,11 +3053,12 @@ def rans_lanes_regions(segments, W, B):
     return np.stack((firsts, np.tile(caps, B)), axis=1).reshape(B, W, 2).astype(np.int32)
 
 
-def rans_lanes_encode(symbols, indexes, segments, W, tables, out=None, regions=None):
+def rans_lanes_encode(symbols, indexes, segments, W, tables, out=None, regions=None, regions_dev=None):
     """clc_rans_lanes_encode: a whole batch's lanes streams in one launch.  symbols / indexes: contiguous int32 device tensors [B, T] in
     stream order; segments: the P <= 32 segment lengths (host ints, sum <= T); tables as for rans_lanes_decode_step.  out: int32 [m] device
     words and regions: HOST int32 [B, W, 2] (first word, capacity) — by default rans_lanes_regions and a buffer of their size.  Every
-    region is checked to lie inside out before the launch.
+    region is checked to lie inside out before the launch.  regions_dev: the caller's device copy of `regions` (int32 [B, W, 2]), which
+    spares the upload — a captured graph passes one.
     -> (out, regions, result): result int32 [B, W, 2] on the device, (first word, word count) of each wave stream or
     (RANS_LANES_ZERO_FREQ / RANS_LANES_OVERFLOW, 0)."""
     import numpy as np
@@ -3091,8 +3092,91 @@ def rans_lanes_encode(symbols, indexes, segments, W, tables, out=None, regions=N
     segs.P = len(segments)
     for i, n in enumerate(segments):
         segs.n[i] = n
-    reg_dev = torch.from_numpy(regions).to(symbols.device)
+    if regions_dev is None:
+        reg_dev = torch.from_numpy(regions).to(symbols.device)
+    else:
+        reg_dev = regions_dev
+        if (not isinstance(reg_dev, torch.Tensor) or reg_dev.dtype != torch.int32 or not reg_dev.is_cuda or not reg_dev.is_contiguous()
+                or tuple(reg_dev.shape) != (B, W, 2)):
+            raise ValueError(f"rans_lanes_encode: regions_dev must be a contiguous int32 [B, W, 2] = {(B, W, 2)} device tensor")
     result = torch.empty((B, W, 2), device=symbols.device, dtype=torch.int32)
     _lib.check(_L().clc_rans_lanes_encode(symbols.data_ptr(), indexes.data_ptr(), T, B, segs, W, cp, stride, rows, lp, op, out.data_ptr(),
                                           reg_dev.data_ptr(), result.data_ptr(), _stream()), "clc_rans_lanes_encode")
     return out, regions, result
+
+
+def rans_lanes_decode_gauss(scale, mu, scale_table, tables, words, spans, state, y_hat=None, symbols=None):
+    """clc_rans_lanes_decode_gauss: the next segment of the lanes stream for a Gaussian-conditional slice — what quantize_build_indexes'
+    index half, rans_lanes_decode_step, the int -> float conversion and the add of the mean do, in one launch.  scale / mu: float maps
+    [B, C, H, W] stored pixel-major (any leading dimension); the segment holds each image's n = H W C symbols, pixels in raster order with
+    channels inner.  scale_table: the non-decreasing float table [2 .. 256] of the indexes; tables, words, spans, state as for
+    rans_lanes_decode_step.  y_hat: a pixel-major float [B, C, H, W] map to write (default: a new one); symbols: an optional contiguous
+    int32 device tensor of B equal blocks of at least n elements that receives the decoded symbols.  -> y_hat = symbols + mu."""
+    who = "rans_lanes_decode_gauss"
+    for t, what in ((scale, "scale"), (mu, "mu")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.dim() != 4:
+            raise ValueError(f"{who}: {what} must be a float32 [B, C, H, W] device tensor")
+    if scale.shape != mu.shape:
+        raise ValueError(f"{who}: scale and mu must have one shape (got {tuple(scale.shape)}, {tuple(mu.shape)})")
+    if (not isinstance(scale_table, torch.Tensor) or scale_table.dtype != torch.float32 or not scale_table.is_cuda
+            or not scale_table.is_contiguous() or not 2 <= scale_table.numel() <= 256):
+        raise ValueError(f"{who}: scale_table must be a contiguous float32 device tensor of 2 .. 256 entries")
+    B, W = _coder_streams(words, spans, state, who, "W", RANS_LANES_STATE_WORDS)
+    _lanes_w(W, who)
+    if scale.shape[0] != B:
+        raise ValueError(f"{who}: spans must be int32 [B = {scale.shape[0]}, W, 2] (got {tuple(spans.shape)})")
+    cp, stride, rows, lp, op = _lanes_tables(tables, who)
+    scale, sp, N, H, Wd, Cc, ldsc = nhwc(scale)
+    mu, mp, *_a, ldmu = nhwc(mu)
+    n = H * Wd * Cc
+    if n >= 1 << 31:
+        raise ValueError(f"{who}: {n} symbols per image; the segment length is an int")
+    if y_hat is None:
+        y_hat = new_act(N, Cc, H, Wd, scale)
+    if not isinstance(y_hat, torch.Tensor) or y_hat.dtype != torch.float32 or not y_hat.is_cuda or tuple(y_hat.shape) != (N, Cc, H, Wd):
+        raise ValueError(f"{who}: y_hat must be a float32 device tensor of scale's shape {(N, Cc, H, Wd)}")
+    yh, hp, *_b, ldh = nhwc(y_hat)
+    if yh.data_ptr() != y_hat.data_ptr() or yh.stride() != y_hat.stride():
+        raise ValueError(f"{who}: y_hat must be stored pixel-major (strides {y_hat.stride()})")
+    symp, lds = None, 0
+    if symbols is not None:
+        if (not isinstance(symbols, torch.Tensor) or symbols.dtype != torch.int32 or not symbols.is_cuda or not symbols.is_contiguous()
+                or symbols.numel() % B or symbols.numel() // B < n):
+            raise ValueError(f"{who}: symbols must be a contiguous int32 device tensor of B = {B} equal image blocks of at least n = {n} elements")
+        symp, lds = symbols.data_ptr(), symbols.numel() // B
+    if n == 0:
+        return y_hat
+    _lib.check(_L().clc_rans_lanes_decode_gauss(sp, ldsc, mp, ldmu, Cc, n, B, scale_table.data_ptr(), scale_table.numel(), cp, stride, rows, lp,
+                                                op, words.data_ptr(), spans.data_ptr(), state.data_ptr(), W, hp, ldh, symp, lds, _stream()),
+               "clc_rans_lanes_decode_gauss")
+    return y_hat
+
+
+def rans_lanes_pack(out, result, capacity=None, packed=None, header=None):
+    """clc_rans_lanes_pack: rans_lanes_encode's wave streams back to back.  out: its int32 [m] words; result: its int32 [B, W, 2] device
+    tensor.  packed: a contiguous int32 [>= capacity] device buffer (default: a new one of `capacity` words, itself by default m);
+    header: int32 [B W + 1] on the device (default: a new one).  -> (packed, header): header[:B W] the word counts in (b, w) order, a
+    negative code as it is, header[B W] the total; nothing is written at or past `capacity` words, a larger total is only reported."""
+    who = "rans_lanes_pack"
+    for t, what in ((out, "out"), (result, "result")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{who}: {what} must be a contiguous int32 device tensor")
+    if out.dim() != 1 or result.dim() != 3 or result.shape[2] != 2 or result.shape[0] < 1:
+        raise ValueError(f"{who}: out must be int32 [m] and result int32 [B, W, 2] (got {tuple(out.shape)}, {tuple(result.shape)})")
+    B, W = int(result.shape[0]), _lanes_w(int(result.shape[1]), who)
+    if capacity is None:
+        capacity = out.numel() if packed is None else packed.numel()
+    capacity = int(capacity)
+    if packed is None:
+        packed = torch.empty((max(capacity, 1),), device=out.device, dtype=torch.int32)
+    if header is None:
+        header = torch.empty((B * W + 1,), device=out.device, dtype=torch.int32)
+    for t, what in ((packed, "packed"), (header, "header")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
+            raise ValueError(f"{who}: {what} must be a contiguous int32 [m] device tensor")
+    if not 0 <= capacity <= packed.numel() or header.numel() < B * W + 1:
+        raise ValueError(f"{who}: capacity must lie inside packed ({capacity} of {packed.numel()} words) and header hold B W + 1 = {B * W + 1} "
+                         f"entries (got {header.numel()})")
+    _lib.check(_L().clc_rans_lanes_pack(out.data_ptr(), out.numel(), result.data_ptr(), B, W, packed.data_ptr(), capacity, header.data_ptr(),
+                                        _stream()), "clc_rans_lanes_pack")
+    return packed, header

@@ -919,8 +919,27 @@ int clc_gmm_decode_step(const float* gp, int ldg, int N, int K, const int32_t* p
  *                    regions[(b * W + w) * 2 ..] (128 + 10 n_w words hold every stream) and leaves result[(b * W + w) * 2 ..] =
  *                    (first word of its stream, word count) — or (CLC_RANS_LANES_ZERO_FREQ, 0) / (CLC_RANS_LANES_OVERFLOW, 0).  Nothing
  *                    is ever written outside the region; an index outside the table is clamped.  The words are the host encoder's.
- * Both kernels: stream-ordered, graph-capturable, allocation- and sync-free; no LDS, no barrier, no atomics, no wave waits on another.
- * Bad arguments are refused by name before any launch. */
+ *
+ * THE LANES STREAM OF THE SLICE MODELS (CLC, TCM; CodecEngine / model.compress(..., lanes=W)): the y string of an image is the same
+ * container (clc_amd/ans.py: lanes_pack, magic CLN1) with P = num_slices segments in slice order; segment i holds the slice's
+ * n = h w (M / num_slices) symbols in the order they lie in memory, pixels in raster order with channels inner (NHWC) — the order
+ * clc_quantize_build_indexes writes its int32 buffers in, NOT the NCHW order of the default one-stream format.  The z string stays the
+ * default stream.
+ * clc_rans_lanes_decode_gauss  clc_rans_lanes_decode_step for a Gaussian-conditional slice, fused with what surrounds it: ONE segment for
+ *                    the whole batch from the slice's scale and mu maps, float [rows = B n / C][C] with leading dimensions ldsc, ldmu >= C.
+ *                    Symbol j of image b is row b (n / C) + j / C, channel j % C; its index is clc_quantize_build_indexes's, bit for bit
+ *                    (sg = max(scale, 0.11); n_scales - 1 - #{k < n_scales - 1: sg <= scale_table[k]}, found by a search: scale_table
+ *                    must be non-decreasing, 2 <= n_scales <= 256), formed ahead of the coder's dependent chain (four rounds at a time); it writes
+ *                    y_hat[r ldh + c] = (float)symbol + mu[r ldmu + c] and, when symbols is not null, symbols[b ld_sym + j].  Words,
+ *                    spans, state, the clamps, the bounds of every loop and what is never read are clc_rans_lanes_decode_step's.
+ *                    n must be whole rows (n % C == 0) and below 2^30; n == 0 launches nothing.  The scale table lies in LDS (1 KiB, one barrier).
+ * clc_rans_lanes_pack  the encoder's wave streams back to back: reads result [B][W][2] of clc_rans_lanes_encode and copies stream (b, w),
+ *                    words[first .. first + count), to packed at the sum of the counts before it, in (b, w) order; header[b W + w] = its
+ *                    count, or its negative code as it is (a code copies nothing and counts as 0), header[B W] = the total.  Each wave
+ *                    forms its own prefix over the counts, so no wave depends on another's output.  No word is stored at or past
+ *                    `capacity` and none is read at or past n_words: a total beyond the capacity is reported and the copy stops there.
+ * All kernels: stream-ordered, graph-capturable, allocation- and sync-free; no atomics, no wave waits on another; no LDS and no barrier
+ * but for the scale table of clc_rans_lanes_decode_gauss.  Bad arguments are refused by name before any launch. */
 #define CLC_RANS_LANES_MAX_W 16
 #define CLC_RANS_LANES_MAX_SEGMENTS 32
 #define CLC_RANS_LANES_ZERO_FREQ (-1)
@@ -943,6 +962,13 @@ int clc_rans_lanes_decode_step(const int32_t* indexes, long ld_idx, int n, int B
 int clc_rans_lanes_encode(const int32_t* symbols, const int32_t* indexes, long ld, int B, clc_rans_lanes_segments segs, int W,
                           const int32_t* cdfs, int cdf_stride, int n_rows, const int32_t* cdf_sizes, const int32_t* offsets,
                           uint32_t* out, const int32_t* regions /* [B][W][2] */, int32_t* result /* [B][W][2] */, clc_stream_t stream);
+int clc_rans_lanes_decode_gauss(const float* scale, long ldsc, const float* mu, long ldmu, int C, int n, int B, const float* scale_table,
+                                int n_scales, const int32_t* cdfs, int cdf_stride, int n_rows, const int32_t* cdf_sizes,
+                                const int32_t* offsets, const uint32_t* words, const int32_t* spans /* [B][W][2] */,
+                                clc_rans_lanes_state* state /* [B][W] */, int W, float* y_hat, long ldh, int32_t* symbols /* or NULL */,
+                                long ld_sym, clc_stream_t stream);
+int clc_rans_lanes_pack(const uint32_t* words, long n_words, const int32_t* result /* [B][W][2] */, int B, int W, uint32_t* packed,
+                        long capacity, int32_t* header /* [B W + 1] */, clc_stream_t stream);
 
 #ifdef __cplusplus
 }
