@@ -31,8 +31,9 @@ host coder.  8 + 12 S bytes more per image (200 at S = 16).  Its decoder runs on
 (clc_gmm_decode_step): the whole wavefront pass is stream-ordered launches with no host hop.  The default stays the one-stream format,
 byte for byte.
 
-TrainEngine, graphed_training, CodecEngine and ReferenceBank do not take these models.  The host side of the coder — the hop of a
-host-decoded step, the upload image of the device-decoded split stream, its end-state check — is coding.py's.
+TrainEngine, graphed_training, CodecEngine and ReferenceBank do not take these models.  The walk over the wavefront's steps is
+``mbt2018``'s (_ar_walk), for both decoders.  The host side of the coder — the start of a decoder's loop, the hop of a host-decoded step,
+the upload image of the device-decoded split stream, its parser and its end-state check — is coding.py's.
 """
 from __future__ import annotations
 
@@ -45,7 +46,7 @@ from ..entropy_models import GaussianMixtureConditional
 from ..layers import (AttentionBlock, Conv2d, ResidualBlock, ResidualBlockUpsample, ResidualBlockWithStride, conv3x3, subpel_conv3x3)
 from ..ops import ACT_LRELU, CL
 from .clc import _resize_registered_buffers
-from .coding import HostHop, check_stream_ends, coded_item, device_ends, open_decoders, upload_streams
+from .coding import HostHop, coded_item, decoder_start, open_decoders, stream_check, stream_parse, upload_streams
 from .hyperprior import JointAutoregressiveHierarchicalPriors, ar_schedule
 
 _SYM_BOUND = float(1 << 24)
@@ -195,28 +196,26 @@ class Cheng2020Anchor(JointAutoregressiveHierarchicalPriors):
         y_strings = [ans.split_pack([ans.encode_direct(t[i][:, s::S, :]) for s in range(S)]) for i in range(t.shape[0])]
         return coded_item(y_strings, z_strings, z_size, substreams=S)
 
+    def _gmm_start(self, n_streams, params):
+        """what both decoders open with -> (steps, pix, y_hat, params, ws, filt): the arguments of _ar_walk over the wavefront"""
+        params, y_hat = decoder_start(params, n_streams, self.N)
+        steps, pix = self._ar_pixels(ar_schedule(y_hat.shape[2], y_hat.shape[3], "wavefront"), y_hat.device)
+        ws = self._gmm_workspace(y_hat.shape[0] * max(len(s) for s in steps), y_hat.device)
+        return steps, pix, y_hat, params, ws, self._ar_filters()
+
     @torch.no_grad()
     def _gmm_decode(self, y_strings, params):
         """The wavefront pass of decompress -> y_hat: per non-empty step, for the whole batch, one row download, one incremental decode
         per image on a decoder opened once, one symbol upload."""
-        params = params.contiguous(memory_format=CL)
-        dev = params.device
-        B, N, K, (H, W) = params.shape[0], self.N, self.K, params.shape[2:]
-        if len(y_strings) != B:
-            raise ValueError(f"decompress: {len(y_strings)} y streams for {B} z streams")
-        steps, pix = self._ar_pixels(ar_schedule(H, W, "wavefront"), dev)
-        rows = B * max(len(s) for s in steps)
-        ws = self._gmm_workspace(rows, dev)
-        filt = self._ar_filters()
-        y_hat = torch.zeros((B, N, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
+        start = self._gmm_start(len(y_strings), params)
         decoders = open_decoders(y_strings)
 
         def decode(rows_np, offs_np, sym_np):
-            e = sym_np.size // B   # image b's elements of the step: rows b * cnt .. in list order, channels inner
+            e = sym_np.size // len(decoders)   # image b's elements of the step: rows b * cnt .. in list order, channels inner
             for b, d in enumerate(decoders):
                 sym_np[b * e:(b + 1) * e] = d.decode_rows(rows_np[b * e:(b + 1) * e], offs_np[b * e:(b + 1) * e])
-        self._gmm_hops(steps, pix, y_hat, params, ws, filt, decode)
-        return y_hat
+        self._gmm_hops(*start, decode)
+        return start[2]   # y_hat
 
     def _gmm_hops(self, steps, pix, y_hat, params, ws, filt, decode):
         """The host-decoded wavefront pass: per non-empty step the chain, gmm_finish_decode, one hop and gmm_commit.  A hop downloads
@@ -226,27 +225,12 @@ class Cheng2020Anchor(JointAutoregressiveHierarchicalPriors):
         split = lambda down_np, sym_np: decode(down_np[:sym_np.size * R].reshape(-1, R), down_np[sym_np.size * R:], sym_np)
         rows = B * max(len(s) for s in steps)
         hop = HostHop(rows * N * (R + 1), rows * N, y_hat.device)
-        off = 0
-        for s in steps:
-            cnt = len(s)
+        for cnt, px, gp in self._ar_walk(steps, pix, y_hat, params, ws, filt):
             n = B * cnt
-            px = pix[off:off + cnt]
-            off += cnt
-            self._ar_chain(px, B, H, W, y_hat, params, ws, filt)
             down, sym_dev = hop.step(n * N * (R + 1), n * N)
-            ops.gmm_finish_decode(ws["gp"], N, K, px, B, H, W, down[:n * N * R].view(n, N, R), down[n * N * R:].view(n, N))
+            ops.gmm_finish_decode(gp, N, K, px, B, H, W, down[:n * N * R].view(n, N, R), down[n * N * R:].view(n, N))
             hop.run(split)
             ops.gmm_commit(sym_dev.view(n, N), N, px, y_hat)
-
-    def _split_parse(self, y_strings, S):
-        """-> per image the S sub-streams of its split string; a header that disagrees with the caller's S is refused"""
-        subs = []
-        for b, blob in enumerate(y_strings):
-            got = ans.split_unpack(blob)
-            if len(got) != S:
-                raise ValueError(f"decompress: substreams = {S}, but the header of image {b} says {len(got)} sub-streams")
-            subs.append(got)
-        return subs
 
     @torch.no_grad()
     def _gmm_decode_split(self, subs, params, device_decoder=True):
@@ -255,25 +239,13 @@ class Cheng2020Anchor(JointAutoregressiveHierarchicalPriors):
         one clc_gmm_decode_step — stream-ordered launches only, no download, no synchronize, no per-image loop; state is the device's
         int32 [B, S, 4] (x low, x high, pos, pad) as the last step left it.
         Host decoder: the hop per step of _gmm_decode with one RansDecoder per (image, sub-stream); state is None."""
-        params = params.contiguous(memory_format=CL)
-        dev = params.device
-        B, N, K, (H, W) = params.shape[0], self.N, self.K, params.shape[2:]
-        if len(subs) != B:
-            raise ValueError(f"decompress: {len(subs)} y streams for {B} z streams")
-        S = len(subs[0])
-        steps, pix = self._ar_pixels(ar_schedule(H, W, "wavefront"), dev)
-        rows = B * max(len(s) for s in steps)
-        ws = self._gmm_workspace(rows, dev)
-        filt = self._ar_filters()
-        y_hat = torch.zeros((B, N, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
+        start = self._gmm_start(len(subs), params)
+        y_hat = start[2]
+        B, N, S = y_hat.shape[0], self.N, len(subs[0])
         if device_decoder:
-            state, spans, words = upload_streams(subs, 2, dev)   # a sub-stream starts with the two words of its coder state
-            off = 0
-            for s in steps:
-                px = pix[off:off + len(s)]
-                off += len(s)
-                self._ar_chain(px, B, H, W, y_hat, params, ws, filt)
-                ops.gmm_decode_step(ws["gp"], N, K, px, words, spans, state, y_hat)
+            state, spans, words = upload_streams(subs, 2, y_hat.device)   # a sub-stream starts with the two words of its coder state
+            for _, px, gp in self._ar_walk(*start):
+                ops.gmm_decode_step(gp, N, self.K, px, words, spans, state, y_hat)
             return y_hat, state
         decoders = [open_decoders(img) for img in subs]
 
@@ -285,13 +257,8 @@ class Cheng2020Anchor(JointAutoregressiveHierarchicalPriors):
                     r = np.ascontiguousarray(rows_np[b, :, k::S]).reshape(-1, R)
                     o = np.ascontiguousarray(offs_np[b, :, k::S]).reshape(-1)
                     sym_np[b, :, k::S] = dd.decode_rows(r, o).reshape(sym_np.shape[1], -1)
-        self._gmm_hops(steps, pix, y_hat, params, ws, filt, decode)
+        self._gmm_hops(*start, decode)
         return y_hat, None
-
-    @staticmethod
-    def _split_check(state, subs):
-        """coding.check_stream_ends over the device's int32 [B, S, 4] state tensor: ONE download"""
-        check_stream_ends(*device_ends(state), [[len(blob) // 4 for blob in img] for img in subs], "sub-stream")
 
     @torch.no_grad()
     def decompress(self, strings, shape, substreams=None, device_decoder=True, check=True):
@@ -309,12 +276,12 @@ class Cheng2020Anchor(JointAutoregressiveHierarchicalPriors):
             z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
             y_hat = self._gmm_decode(strings[0], self._hyper_synthesis(z_hat))
             return {"x_hat": self._synthesis(y_hat).clamp_(0, 1)}
-        subs = self._split_parse(strings[0], S)
+        subs = stream_parse(ans.SPLIT_STREAM, strings[0], S, "substreams")
         z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
         y_hat, state = self._gmm_decode_split(subs, self._hyper_synthesis(z_hat), device_decoder)
         x_hat = self._synthesis(y_hat).clamp_(0, 1)
         if check and state is not None:
-            self._split_check(state, subs)
+            stream_check(ans.SPLIT_STREAM, state, subs)
         return {"x_hat": x_hat}
 
 

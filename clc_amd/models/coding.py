@@ -1,12 +1,16 @@
 """What the context-model coders (hyperprior.py, elic.py, cheng.py) share on the host side of their kernels — each decision has one
-owner here (DESIGN 23):
+owner here (DESIGN 23, 26):
 
 * THE HOP of a host-decoded step: ``HostHop`` (buffers allocated once; per step one download, one synchronize, the caller's decode, one
   upload), ``open_decoders`` and ``table_decode``.
+* WHERE A TABLE-CODED STEP'S SYMBOLS COME FROM, between the finish kernel and the commit kernel: ``HostSymbols`` (a hop to host
+  decoders) and ``DeviceLanesSymbols`` (the device's lanes decoder, no hop), one interface: ``views``, ``decode``, ``state``.
+* THE START of a decoder's pass loop: ``decoder_start`` (parameters channels-last, the batch refusal, the zeroed y_hat).
 * THE UPLOAD IMAGE of a device-decoded batch, ``[states | spans | words]`` in one pinned int32 buffer: ``stream_image`` (numpy),
   ``stream_views``, ``upload_streams``; and the end-state rule of a whole stream, ``check_stream_ends`` / ``device_ends``.
-* THE LANES STRINGS of the slice models (CLC, TCM; model and CodecEngine): ``lanes_count``, ``lanes_parse``, ``refuse_lanes_strings``,
-  ``lanes_strings``, ``lanes_check``.
+* THE MULTI-STREAM STRINGS of a batch, for either container of ans.py: ``stream_parse`` and ``stream_check``; for the lanes stream
+  (elic2022, CLC, TCM; model and CodecEngine) also ``lanes_count``, ``lanes_parse``, ``refuse_lanes_strings``, ``lanes_strings``,
+  ``lanes_check``.
 * Small pieces: ``linear_filters``, ``CodeInputs._code_inputs``, ``coded_item``.
 
 The kernels, their order and their arguments stay with the models; the multi-stream container is ans.py's.
@@ -16,7 +20,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .. import ans
+from .. import ans, ops
+from ..ops import CL
 
 
 class HostHop:
@@ -72,6 +77,52 @@ def table_decode(decode_fns, tables):
         for b, fn in enumerate(decode_fns):
             sym_np[b * e:(b + 1) * e] = fn(idx_np[b * e:(b + 1) * e], cdf, ln, off)
     return decode
+
+
+class HostSymbols:
+    """A table-coded step's symbols from the host: one hop to ``decode_fns`` (table_decode's, one per image).  ``state`` is what
+    stream_check takes when the last step is done: the caller's decoders."""
+
+    def __init__(self, decode_fns, tables, most, dev, state=None):
+        self._decode, self.state = table_decode(decode_fns, tables), state
+        self._hop = HostHop(most, most, dev)   # most: the elements of the largest step
+
+    def views(self, n, c):
+        """-> (indexes, symbols) int32 [n, c] of a step of n rows x c channels: the finish kernel writes the first, commit reads the second"""
+        idx, sym = self._hop.step(n * c, n * c)
+        return idx.view(n, c), sym.view(n, c)
+
+    def decode(self, idx, sym, per_image):
+        """the step whose views were cut last: its indexes down, its symbols up (HostHop.run)"""
+        self._hop.run(self._decode)
+
+
+class DeviceLanesSymbols:
+    """A table-coded step's symbols from the device's lanes decoder: every wave stream's states, spans and words uploaded once, then one
+    clc_rans_lanes_decode_step per step — no download, no synchronize.  ``state`` is the device's int32 [B, W, 130] (64 x (x low, x
+    high), pos, pad) as the last step left it.  tables: the DEVICE's (cdf, lengths, offsets)."""
+
+    def __init__(self, subs, tables, most, dev):
+        self._tables = tables
+        self.state, self._spans, self._words = upload_streams(subs, 2 * ans.LANES, dev)   # a wave stream starts with its 64 lane states
+        self._idx = torch.empty((most,), device=dev, dtype=torch.int32)
+        self._sym = torch.empty((most,), device=dev, dtype=torch.int32)
+
+    def views(self, n, c):
+        return self._idx[:n * c].view(n, c), self._sym[:n * c].view(n, c)
+
+    def decode(self, idx, sym, per_image):
+        ops.rans_lanes_decode_step(idx, per_image, self._tables, self._words, self._spans, self.state, sym)
+
+
+def decoder_start(params, n_streams, M):
+    """What a decoder's pass loop opens with -> (the hyper parameters channels-last, y_hat [B, M, H, W] zeroed and channels-last); a
+    batch of y streams that is not the z streams' is refused."""
+    params = params.contiguous(memory_format=CL)
+    B, (H, W) = params.shape[0], params.shape[2:]
+    if n_streams != B:
+        raise ValueError(f"decompress: {n_streams} y streams for {B} z streams")
+    return params, torch.zeros((B, M, H, W), device=params.device, dtype=torch.float32).contiguous(memory_format=CL)
 
 
 def stream_spans(counts):
@@ -147,15 +198,21 @@ def lanes_count(lanes, who):
     return None if lanes is None else ans.stream_count(ans.LANES_STREAM, lanes, who, "lanes")
 
 
-def lanes_parse(y_strings, W):
-    """-> per image the W wave streams of its lanes string; a header that disagrees with the caller's W is refused.  Host only."""
+def stream_parse(fmt, y_strings, n, keyword):
+    """-> per image the n streams of its string in container fmt (ans.SPLIT_STREAM, ans.LANES_STREAM); a header that disagrees with the
+    caller's ``keyword=n`` is refused.  Host only."""
     subs = []
     for b, blob in enumerate(y_strings):
-        got = ans.lanes_unpack(blob)
-        if len(got) != W:
-            raise ValueError(f"decompress: lanes = {W}, but the header of image {b} says {len(got)} wave streams")
+        got = ans._unpack(fmt, blob)
+        if len(got) != n:
+            raise ValueError(f"decompress: {keyword} = {n}, but the header of image {b} says {len(got)} {fmt.noun}s")
         subs.append(got)
     return subs
+
+
+def lanes_parse(y_strings, W):
+    """stream_parse of lanes strings under ``lanes=W``"""
+    return stream_parse(ans.LANES_STREAM, y_strings, W, "lanes")
 
 
 def refuse_lanes_strings(y_strings):
@@ -183,15 +240,20 @@ def lanes_strings(header, words, B, W):
     return [ans.lanes_pack(streams[b * W:(b + 1) * W]) for b in range(B)]
 
 
-def lanes_check(state, subs):
-    """check_stream_ends over every wave stream's 64 lanes.  state: the device's [B, W, 130] tensor — ONE download — or the host coder's
-    list of ans.LanesDecoder."""
+def stream_check(fmt, state, subs):
+    """check_stream_ends over every state of every stream of container fmt.  state: the device coder's [B, S, n_state + 2] tensor — ONE
+    download — or the host coder's list of ans.LanesDecoder."""
     if isinstance(state, torch.Tensor):
         x, pos = device_ends(state)
     else:
         ends = [[d.state(w) for w in range(len(img))] for d, img in zip(state, subs)]
         x, pos = [[e[0] for e in img] for img in ends], [[e[1] for e in img] for img in ends]
-    check_stream_ends(x, pos, [[len(blob) // 4 for blob in img] for img in subs], "wave stream")
+    check_stream_ends(x, pos, [[len(blob) // 4 for blob in img] for img in subs], fmt.noun)
+
+
+def lanes_check(state, subs):
+    """stream_check over every wave stream's 64 lanes"""
+    stream_check(ans.LANES_STREAM, state, subs)
 
 
 def linear_filters(layers):

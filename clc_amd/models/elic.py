@@ -19,8 +19,10 @@ batch-invariant routes ``mbt2018-mean`` codes with: a stream written at batch 8 
 STREAM ORDER: one rANS stream per image for y — for k ascending, group k's anchors in raster order, then its non-anchors in raster
 order, channels inner; z as in the other hyperprior models.
 
-TrainEngine, graphed_training, CodecEngine and ReferenceBank do not take this model.  The host side of the coder — the hop of a
-host-decoded pass, the upload image of the device-decoded lanes stream, its end-state check — is coding.py's.
+TrainEngine, graphed_training, CodecEngine and ReferenceBank do not take this model.  Owners: the schedule of the 2 K passes is
+_scctx_passes, for encoder and decoder; the decoder's loop is _scctx_decode_from, over a source of symbols.  The host side of the
+coder is coding.py's: the start of the decoder's loop, the sources (a hop to the host's one-stream or lanes decoder,
+the device's lanes decoder on one upload image), and the lanes strings — count, parser, refusal, assembly, end-state check.
 """
 from __future__ import annotations
 
@@ -28,13 +30,13 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import ans, lib, ops
+from .. import ans, ops
 from ..entropy_models import GaussianConditional
 from ..layers import AttentionBlock, CheckerboardMaskedConv2d, Conv2d, conv, conv1x1, conv3x3, deconv
 from ..ops import ACT_NONE, ACT_RELU, CL
 from .clc import CompressionModel, _resize_registered_buffers, get_scale_table
-from .coding import (CodeInputs, HostHop, check_stream_ends, coded_item, device_ends, linear_filters, open_decoders, table_decode,
-                     upload_streams)
+from .coding import (CodeInputs, DeviceLanesSymbols, HostSymbols, coded_item, decoder_start, lanes_check, lanes_count, lanes_parse,
+                     lanes_strings, linear_filters, open_decoders, refuse_lanes_strings)
 from .hyperprior import ckbd_lists, ckbd_pixels
 
 
@@ -191,6 +193,28 @@ class Elic2022(CodeInputs, CompressionModel):
     def _channel_ctx(self, k, y_hat):
         return _run(self.channel_context[k], y_hat[:, :self.starts[k]]).contiguous(memory_format=CL) if k else None
 
+    def _scctx_passes(self, params, y_hat):
+        """THE SCHEDULE, for encoder and decoder alike: groups ascending x (anchors, non-anchors); an empty pass is skipped.  The channel
+        context of group k is computed once, over the groups before it; pass A reads a zero spatial map, pass B the spatial context of
+        the anchors that pass A committed.  Per pass the chain, then (group, its pixel list, the group's channels of y_hat, its
+        (scales | means) rows) to the caller's body, which finishes the pass into y_hat before the next one reads it."""
+        B, _, H, W = y_hat.shape
+        na, nn_, pix = ckbd_lists(H, W, y_hat.device)
+        ws, filt = self._scctx_workspace(B * max(na, nn_), y_hat.device), self._scctx_filters()
+        for k, (s, c) in enumerate(zip(self.starts, self.groups)):
+            yhk = y_hat[:, s:s + c]
+            ch = self._channel_ctx(k, y_hat)
+            for lo, cnt in ((0, na), (na, nn_)):
+                if not cnt:
+                    continue
+                if lo:
+                    sp = self.spatial_context[k](yhk)
+                else:
+                    sp = torch.zeros((B, 2 * c, H, W), device=y_hat.device, dtype=torch.float32).contiguous(memory_format=CL)
+                px = pix[lo:lo + cnt]
+                self._scctx_chain(px, B, H, W, params, sp, ch, ws, filt[k])
+                yield k, px, yhk, ws["gp"]
+
     @torch.no_grad()
     def _scctx_encode(self, y, params):
         """The 2 K passes of compress -> (per group symbols int32 [B, H*W, c_k], per group indexes int32 [B, H*W, c_k], y_hat), the buffers
@@ -199,33 +223,14 @@ class Elic2022(CodeInputs, CompressionModel):
         B, M, H, W = y.shape
         y = y.contiguous(memory_format=CL)
         params = params.contiguous(memory_format=CL)
-        dev = y.device
-        na, nn_, pix = ckbd_lists(H, W, dev)
-        ws = self._scctx_workspace(B * max(na, nn_), dev)
-        filt = self._scctx_filters()
         table = self.gaussian_conditional.scale_table
         y_hat = torch.zeros_like(y, memory_format=CL)
-        syms, idxs = [], []
-        for k, (s, c) in enumerate(zip(self.starts, self.groups)):
-            sym = torch.empty((B, H * W, c), device=dev, dtype=torch.int32)
-            idx = torch.empty((B, H * W, c), device=dev, dtype=torch.int32)
-            yk, yhk = y[:, s:s + c], y_hat[:, s:s + c]
-            ch = self._channel_ctx(k, y_hat)
-            if na:
-                zero_sp = torch.zeros((B, 2 * c, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
-                self._scctx_chain(pix[:na], B, H, W, params, zero_sp, ch, ws, filt[k])
-                ops.ar_finish_encode(ws["gp"], c, pix[:na], yk, yhk, table, sym, idx)
-            sp = self.spatial_context[k](yhk)
-            self._scctx_chain(pix[na:], B, H, W, params, sp, ch, ws, filt[k])
-            ops.ar_finish_encode(ws["gp"], c, pix[na:], yk, yhk, table, sym, idx)
-            syms.append(sym)
-            idxs.append(idx)
+        yks = [y[:, s:s + c] for s, c in zip(self.starts, self.groups)]
+        syms = [torch.empty((B, H * W, c), device=y.device, dtype=torch.int32) for c in self.groups]
+        idxs = [torch.empty((B, H * W, c), device=y.device, dtype=torch.int32) for c in self.groups]
+        for k, px, yhk, gp in self._scctx_passes(params, y_hat):
+            ops.ar_finish_encode(gp, self.groups[k], px, yks[k], yhk, table, syms[k], idxs[k])
         return syms, idxs, y_hat
-
-    @staticmethod
-    def _lanes_count(lanes, what):
-        """lanes=None: the one-stream format; else the number W of wave streams per image, refused by name outside 1 .. 16"""
-        return None if lanes is None else ans.stream_count(ans.LANES_STREAM, lanes, f"Elic2022.{what}", "lanes")
 
     def _lanes_segments(self, H, W):
         """the lanes stream's segments: the 2 K passes in scctx_order, n = pixels of the pass x channels of the group"""
@@ -234,24 +239,20 @@ class Elic2022(CodeInputs, CompressionModel):
 
     def _lanes_encode_device(self, sym, idx, segments, W):
         """int32 [B, T] device symbols / indexes in stream order -> per image its lanes string: one clc_rans_lanes_encode for the batch,
-        then two device -> host copies (the [B, W] results, the packed words)."""
+        then two device -> host copies (the [B, W] results, the packed words); the host half is coding.lanes_strings, which raises by
+        name on a negative code."""
         gc = self.gaussian_conditional
         out, _, result = ops.rans_lanes_encode(sym, idx, segments, W, (gc._quantized_cdf, gc._cdf_length, gc._offset))
-        res = result.cpu().numpy()
-        for b, w in zip(*np.nonzero(res[..., 0] < 0)):
-            why = "a zero-frequency symbol" if res[b, w, 0] == lib.RANS_LANES_ZERO_FREQ else "its region overflowed"
-            raise ValueError(f"compress: image {b}, wave stream {w}: {why} (clc_rans_lanes_encode code {int(res[b, w, 0])})")
-        spans = res.reshape(-1, 2)
-        words = torch.cat([out[f:f + n] for f, n in spans]).cpu().numpy().view(np.uint32)
-        ends = np.cumsum(spans[:, 1])
-        streams = [words[e - n:e].astype("<u4").tobytes() for e, n in zip(ends, spans[:, 1])]
-        return [ans.lanes_pack(streams[b * W:(b + 1) * W]) for b in range(res.shape[0])]
+        res = result.cpu().numpy()   # [B, W, 2]: (first word, word count), or (a negative code, 0)
+        words = torch.cat([out[f:f + n] for f, n in res.reshape(-1, 2)]).cpu().numpy()   # (a code's span is empty)
+        header = np.append(np.where(res[..., 0] < 0, res[..., 0], res[..., 1]).reshape(-1), res[..., 1].sum())
+        return lanes_strings(header, words, res.shape[0], W)
 
     @torch.no_grad()
     def compress(self, x, lanes=None):
         """lanes=None: the one-stream format.  lanes=W: THE LANES STREAM (clc_amd/ans.py: lanes_pack; include/clc_hip.h), W wave streams
         of 64 rANS lanes per image, encoded on the device, and "lanes": W in the result; pass the same W to decompress."""
-        Wn = self._lanes_count(lanes, "compress")
+        Wn = lanes_count(lanes, "Elic2022.compress")
         y, params, z_strings, z_size = self._code_inputs(x)
         if Wn is None:
             cdf, ln, off = self.gaussian_conditional.host_tables()
@@ -267,48 +268,30 @@ class Elic2022(CodeInputs, CompressionModel):
         y_strings = [ans.encode(np.ascontiguousarray(both[0, i]), np.ascontiguousarray(both[1, i]), cdf, ln, off) for i in range(B)]
         return coded_item(y_strings, z_strings, z_size)
 
+    def _scctx_decode_from(self, source, params, y_hat):
+        """The 2 K passes of decompress over a source of symbols (coding.HostSymbols, coding.DeviceLanesSymbols): per non-empty pass
+        the chain, ar_finish_decode, the source's step and ar_commit."""
+        B, _, H, W = y_hat.shape
+        table = self.gaussian_conditional.scale_table
+        for k, px, yhk, gp in self._scctx_passes(params, y_hat):
+            c, cnt = self.groups[k], px.shape[0]
+            idx, sym = source.views(B * cnt, c)
+            ops.ar_finish_decode(gp, c, px, B, H, W, table, idx)
+            source.decode(idx, sym, cnt * c)
+            ops.ar_commit(sym, gp, c, px, yhk)
+        return y_hat
+
+    def _scctx_most(self, y_hat):
+        """the elements of the largest pass: the non-anchors ((0, 0) is one) of the widest group"""
+        return y_hat.shape[0] * ((y_hat.shape[2] * y_hat.shape[3] + 1) // 2) * max(self.groups)
+
     @torch.no_grad()
     def _scctx_decode(self, y_strings, params):
         """The 2 K passes of decompress -> y_hat: per pass one index download, one incremental decode per image, one symbol upload."""
-        params = params.contiguous(memory_format=CL)
-        dev = params.device
-        B, M, (H, W) = params.shape[0], self.M, params.shape[2:]
-        if len(y_strings) != B:
-            raise ValueError(f"decompress: {len(y_strings)} y streams for {B} z streams")
-        table = self.gaussian_conditional.scale_table
-        na, nn_, pix = ckbd_lists(H, W, dev)
-        rows = B * max(na, nn_)
-        ws = self._scctx_workspace(rows, dev)
-        filt = self._scctx_filters()
-        y_hat = torch.zeros((B, M, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
-        decode = table_decode([d.decode_stream for d in open_decoders(y_strings)], self.gaussian_conditional.host_tables())
-        hop = HostHop(rows * max(self.groups), rows * max(self.groups), dev)
-        for k, (s, c) in enumerate(zip(self.starts, self.groups)):
-            yhk = y_hat[:, s:s + c]
-            ch = self._channel_ctx(k, y_hat)
-            sp = torch.zeros((B, 2 * c, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
-            for lo, cnt in ((0, na), (na, nn_)):
-                if not cnt:
-                    continue
-                px = pix[lo:lo + cnt]
-                if lo:
-                    sp = self.spatial_context[k](yhk)
-                idx_dev, sym_dev = (t.view(B * cnt, c) for t in hop.step(B * cnt * c, B * cnt * c))
-                self._scctx_chain(px, B, H, W, params, sp, ch, ws, filt[k])
-                ops.ar_finish_decode(ws["gp"], c, px, B, H, W, table, idx_dev)
-                hop.run(decode)
-                ops.ar_commit(sym_dev, ws["gp"], c, px, yhk)
-        return y_hat
-
-    def _lanes_parse(self, y_strings, W):
-        """-> per image the W wave streams of its lanes string; a header that disagrees with the caller's W is refused"""
-        subs = []
-        for b, blob in enumerate(y_strings):
-            got = ans.lanes_unpack(blob)
-            if len(got) != W:
-                raise ValueError(f"decompress: lanes = {W}, but the header of image {b} says {len(got)} wave streams")
-            subs.append(got)
-        return subs
+        params, y_hat = decoder_start(params, len(y_strings), self.M)
+        fns = [d.decode_stream for d in open_decoders(y_strings)]
+        source = HostSymbols(fns, self.gaussian_conditional.host_tables(), self._scctx_most(y_hat), y_hat.device)
+        return self._scctx_decode_from(source, params, y_hat)
 
     @torch.no_grad()
     def _scctx_decode_lanes(self, subs, params, device_coder=True):
@@ -317,61 +300,14 @@ class Elic2022(CodeInputs, CompressionModel):
         ar_finish_decode, one clc_rans_lanes_decode_step and ar_commit — stream-ordered launches only, no download, no synchronize, no
         per-image loop; state is the device's int32 [B, W, 130] (64 x (x low, x high), pos, pad) as the last pass left it.
         Host coder: the hop per pass of _scctx_decode with one ans.LanesDecoder per image; state is the list of decoders."""
-        params = params.contiguous(memory_format=CL)
-        dev = params.device
-        B, M, (H, W) = params.shape[0], self.M, params.shape[2:]
-        if len(subs) != B:
-            raise ValueError(f"decompress: {len(subs)} y streams for {B} z streams")
-        table = self.gaussian_conditional.scale_table
-        na, nn_, pix = ckbd_lists(H, W, dev)
-        rows = B * max(na, nn_)
-        ws = self._scctx_workspace(rows, dev)
-        filt = self._scctx_filters()
-        y_hat = torch.zeros((B, M, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
-        gc, cmax = self.gaussian_conditional, max(self.groups)
+        params, y_hat = decoder_start(params, len(subs), self.M)
+        gc, most = self.gaussian_conditional, self._scctx_most(y_hat)
         if device_coder:
-            tables = (gc._quantized_cdf, gc._cdf_length, gc._offset)
-            state, spans, words = upload_streams(subs, 2 * ans.LANES, dev)   # a wave stream starts with its 64 lane states
-            idx_dev = torch.empty((rows * cmax,), device=dev, dtype=torch.int32)
-            sym_dev = torch.empty((rows * cmax,), device=dev, dtype=torch.int32)
+            source = DeviceLanesSymbols(subs, (gc._quantized_cdf, gc._cdf_length, gc._offset), most, y_hat.device)
         else:
             decoders = [ans.LanesDecoder(img) for img in subs]
-            decode = table_decode([d.decode for d in decoders], gc.host_tables())
-            hop = HostHop(rows * cmax, rows * cmax, dev)
-        for k, (s, c) in enumerate(zip(self.starts, self.groups)):
-            yhk = y_hat[:, s:s + c]
-            ch = self._channel_ctx(k, y_hat)
-            sp_map = torch.zeros((B, 2 * c, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
-            for lo, cnt in ((0, na), (na, nn_)):
-                if not cnt:
-                    continue
-                px = pix[lo:lo + cnt]
-                if lo:
-                    sp_map = self.spatial_context[k](yhk)
-                n = B * cnt
-                self._scctx_chain(px, B, H, W, params, sp_map, ch, ws, filt[k])
-                if device_coder:
-                    ib, sb = idx_dev[:n * c].view(n, c), sym_dev[:n * c].view(n, c)
-                    ops.ar_finish_decode(ws["gp"], c, px, B, H, W, table, ib)
-                    ops.rans_lanes_decode_step(ib, cnt * c, tables, words, spans, state, sb)
-                    ops.ar_commit(sb, ws["gp"], c, px, yhk)
-                    continue
-                ib, sb = (t.view(n, c) for t in hop.step(n * c, n * c))
-                ops.ar_finish_decode(ws["gp"], c, px, B, H, W, table, ib)
-                hop.run(decode)
-                ops.ar_commit(sb, ws["gp"], c, px, yhk)
-        return y_hat, (state if device_coder else decoders)
-
-    @staticmethod
-    def _lanes_check(state, subs):
-        """coding.check_stream_ends over every wave stream's 64 lanes.  state: the device's [B, W, 130] tensor — ONE download — or the
-        host coder's list of decoders."""
-        if isinstance(state, torch.Tensor):
-            x, pos = device_ends(state)
-        else:
-            ends = [[d.state(w) for w in range(len(img))] for d, img in zip(state, subs)]
-            x, pos = [[e[0] for e in img] for img in ends], [[e[1] for e in img] for img in ends]
-        check_stream_ends(x, pos, [[len(blob) // 4 for blob in img] for img in subs], "wave stream")
+            source = HostSymbols([d.decode for d in decoders], gc.host_tables(), most, y_hat.device, state=decoders)
+        return self._scctx_decode_from(source, params, y_hat), source.state
 
     @torch.no_grad()
     def decompress(self, strings, shape, lanes=None, device_coder=True, check=True):
@@ -381,22 +317,19 @@ class Elic2022(CodeInputs, CompressionModel):
         launched, and raises ValueError naming the image and the wave streams that did not end where a whole stream ends — a check
         against streams out of step or cut short, NOT a checksum: a changed bit inside an escape's raw payload decodes to another symbol
         and ends clean.  device_coder=False runs the same format on the host coder (ans.LanesDecoder), a hop per pass: the oracle."""
-        Wn = self._lanes_count(lanes, "decompress")
+        Wn = lanes_count(lanes, "Elic2022.decompress")
         assert isinstance(strings, (list, tuple)) and len(strings) == 2
         if Wn is None:
-            for b, blob in enumerate(strings[0]):
-                if bytes(blob[:4]) == ans.LANES_MAGIC:
-                    raise ValueError(f"decompress: the y string of image {b} is a lanes stream ({ans.LANES_MAGIC!r}); pass lanes= (its header "
-                                     f"says {blob[4] if len(blob) > 4 else '?'} wave streams)")
+            refuse_lanes_strings(strings[0])
             z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
             y_hat = self._scctx_decode(strings[0], self._hyper_synthesis(z_hat))
             return {"x_hat": self._synthesis(y_hat).clamp_(0, 1)}
-        subs = self._lanes_parse(strings[0], Wn)
+        subs = lanes_parse(strings[0], Wn)
         z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
         y_hat, state = self._scctx_decode_lanes(subs, self._hyper_synthesis(z_hat), device_coder)
         x_hat = self._synthesis(y_hat).clamp_(0, 1)
         if check:
-            self._lanes_check(state, subs)
+            lanes_check(state, subs)
         return {"x_hat": x_hat}
 
     def update(self, scale_table=None, force=False):

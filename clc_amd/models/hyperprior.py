@@ -8,7 +8,9 @@ so CompressAI checkpoints load.  CompressAI itself is not a dependency and nothi
 models are checked against a plain-torch restatement of the same definitions (tests/hyperprior_ref.py).
 
 They train through plain autograd and code through the model methods; TrainEngine, graphed_training, CodecEngine and ReferenceBank
-do not take them.  The host side of the context-model coders — the hop of a host-decoded step, the result item — is coding.py's.
+do not take them.  The host side of the context-model coders — the start of a decoder's pass loop, the symbols of a host-decoded step,
+the result item — is coding.py's; ``mbt2018`` and ``mbt2018-checkerboard`` each state their schedule once (_ar_passes, _ckbd_passes) and
+share one encoder loop and one decoder loop over it (_encode_passes, _decode_passes).
 """
 from __future__ import annotations
 
@@ -21,7 +23,7 @@ from ..entropy_models import EntropyBottleneck, GaussianConditional
 from ..layers import GDN, CheckerboardMaskedConv2d, Conv2d, MaskedConv2d, conv, deconv
 from ..ops import ACT_LRELU, ACT_NONE, ACT_RELU, CL
 from .clc import CompressionModel, _resize_registered_buffers, get_scale_table
-from .coding import CodeInputs, HostHop, coded_item, linear_filters, open_decoders, table_decode
+from .coding import CodeInputs, HostSymbols, coded_item, decoder_start, linear_filters, open_decoders
 
 
 class ScaleHyperprior(CompressionModel):
@@ -274,28 +276,64 @@ class JointAutoregressiveHierarchicalPriors(CodeInputs, MeanScaleHyperprior):
         steps = [s for s in steps if s]
         return steps, torch.tensor([p for s in steps for p in s], dtype=torch.int32).reshape(-1, 2).to(dev)
 
+    def _ar_walk(self, steps, pix, y_hat, params, ws, filt):
+        """One walk over the steps of a schedule, for encoders and decoders alike: per step the chain over its pixels, then
+        (pixels of the step, its pixel list, its (scales | means) rows) to the caller's body, which finishes the step into y_hat
+        before the next one reads it.  One slice per step and nothing else on the host: mbt2018's decoder takes one step per pixel."""
+        (B, _, H, W), gp, off = y_hat.shape, ws["gp"], 0
+        for s in steps:
+            cnt = len(s)
+            px = pix[off:off + cnt]
+            off += cnt
+            self._ar_chain(px, B, H, W, y_hat, params, ws, filt)
+            yield cnt, px, gp
+
+    def _ar_passes(self, params, y_hat, order):
+        """THE SCHEDULE of mbt2018: the non-empty steps of ar_schedule(H, W, order).  The encoder takes whole wavefront steps, the
+        decoder must follow the stream: one raster pixel per step."""
+        B, _, H, W = y_hat.shape
+        steps, pix = self._ar_pixels(ar_schedule(H, W, order), y_hat.device)
+        ws = self._ar_workspace(B * max(len(s) for s in steps), y_hat.device)
+        return self._ar_walk(steps, pix, y_hat, params, ws, self._ar_filters())
+
     @torch.no_grad()
-    def _ar_encode(self, y, params, order="wavefront"):
-        """The autoregressive pass of compress -> (symbols int32 [B, H*W, M], indexes int32 [B, H*W, M], y_hat): all launches on the current
-        stream, no host sync.  The schedule decides the order of computation only; the buffers are in raster order either way."""
-        ops._require_gpu(y, "mbt2018 compress")
+    def _encode_passes(self, who, y, params, passes, *schedule):
+        """The encoder of a table-coded model over its schedule ``passes(params, y_hat, *schedule)`` -> (symbols int32 [B, H*W, M],
+        indexes int32 [B, H*W, M], y_hat): all launches on the current stream, no host sync.  The schedule decides the order of
+        computation only; the buffers are in raster order either way."""
+        ops._require_gpu(y, f"{who} compress")
         B, M, H, W = y.shape
         y = y.contiguous(memory_format=CL)
         params = params.contiguous(memory_format=CL)
-        steps, pix = self._ar_pixels(ar_schedule(H, W, order), y.device)
-        ws = self._ar_workspace(B * max(len(s) for s in steps), y.device)
-        filt = self._ar_filters()
         table = self.gaussian_conditional.scale_table
         y_hat = torch.zeros_like(y, memory_format=CL)
         sym = torch.empty((B, H * W, M), device=y.device, dtype=torch.int32)
         idx = torch.empty((B, H * W, M), device=y.device, dtype=torch.int32)
-        off = 0
-        for s in steps:
-            px = pix[off:off + len(s)]
-            self._ar_chain(px, B, H, W, y_hat, params, ws, filt)
-            ops.ar_finish_encode(ws["gp"], M, px, y, y_hat, table, sym, idx)
-            off += len(s)
+        for _, px, gp in passes(params, y_hat, *schedule):
+            ops.ar_finish_encode(gp, M, px, y, y_hat, table, sym, idx)
         return sym, idx, y_hat
+
+    @torch.no_grad()
+    def _decode_passes(self, y_strings, params, most, passes, *schedule):
+        """The decoder of a table-coded model over its schedule -> y_hat: per step one index download, one incremental decode per
+        image on a decoder opened once, one symbol upload.  most: the pixels of the schedule's largest step."""
+        params, y_hat = decoder_start(params, len(y_strings), self.M)
+        B, M, H, W = y_hat.shape
+        gc = self.gaussian_conditional
+        table = gc.scale_table
+        src = HostSymbols([d.decode_stream for d in open_decoders(y_strings)], gc.host_tables(), B * most * M, y_hat.device)
+        cut = None
+        for cnt, px, gp in passes(params, y_hat, *schedule):
+            if cnt != cut:   # the views are cut when the step's size changes: once for mbt2018's pixel per step, whatever the latent
+                cut, (idx, sym) = cnt, src.views(B * cnt, M)
+            ops.ar_finish_decode(gp, M, px, B, H, W, table, idx)
+            src.decode(idx, sym, cnt * M)
+            ops.ar_commit(sym, gp, M, px, y_hat)
+        return y_hat
+
+    def _ar_encode(self, y, params, order="wavefront"):
+        """The autoregressive pass of compress: _encode_passes over the steps of ``order``"""
+        return self._encode_passes("mbt2018", y, params, self._ar_passes, order)
 
     @torch.no_grad()
     def compress(self, x, order="wavefront"):
@@ -310,25 +348,7 @@ class JointAutoregressiveHierarchicalPriors(CodeInputs, MeanScaleHyperprior):
     def decompress(self, strings, shape):
         assert isinstance(strings, (list, tuple)) and len(strings) == 2
         z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
-        params = self._hyper_synthesis(z_hat).contiguous(memory_format=CL)
-        dev = params.device
-        B, M, (H, W) = params.shape[0], self.M, params.shape[2:]
-        if len(strings[0]) != B:
-            raise ValueError(f"decompress: {len(strings[0])} y streams for {B} z streams")
-        table = self.gaussian_conditional.scale_table
-        steps, pix = self._ar_pixels(ar_schedule(H, W, "raster"), dev)
-        ws = self._ar_workspace(B, dev)
-        filt = self._ar_filters()
-        y_hat = torch.zeros((B, M, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
-        decode = table_decode([d.decode_stream for d in open_decoders(strings[0])], self.gaussian_conditional.host_tables())
-        hop = HostHop(B * M, B * M, dev)
-        idx_dev, sym_dev = (t.view(B, M) for t in hop.step(B * M, B * M))
-        for i in range(len(steps)):
-            px = pix[i:i + 1]
-            self._ar_chain(px, B, H, W, y_hat, params, ws, filt)
-            ops.ar_finish_decode(ws["gp"], M, px, B, H, W, table, idx_dev)
-            hop.run(decode)
-            ops.ar_commit(sym_dev, ws["gp"], M, px, y_hat)
+        y_hat = self._decode_passes(strings[0], self._hyper_synthesis(z_hat), 1, self._ar_passes, "raster")
         return {"x_hat": self._synthesis(y_hat).clamp_(0, 1)}
 
 
@@ -375,29 +395,27 @@ class JointCheckerboardHierarchicalPriors(JointAutoregressiveHierarchicalPriors)
     def _ckbd_filters(self):
         return linear_filters(self.entropy_parameters)
 
-    @torch.no_grad()
+    def _ckbd_passes(self, params, y_hat):
+        """THE SCHEDULE of the checkerboard model, for encoder and decoder alike: the anchors, then the non-anchors; an empty pass is
+        skipped.  Pass 1 reads a zero context map, pass 2 the context layer over the anchors that pass 1 committed.  Per pass the
+        chain, then (pixels of the pass, its pixel list, its (scales | means) rows) to the caller's body."""
+        B, M, H, W = y_hat.shape
+        na, nn_, pix = self._ckbd_lists(H, W, y_hat.device)
+        ws, filt = self._ckbd_workspace(B * max(na, nn_), y_hat.device), self._ckbd_filters()
+        for lo, cnt in ((0, na), (na, nn_)):
+            if not cnt:
+                continue
+            if lo:
+                ctx_map = self.context_prediction(y_hat)
+            else:
+                ctx_map = torch.zeros((B, 2 * M, H, W), device=y_hat.device, dtype=torch.float32).contiguous(memory_format=CL)
+            px = pix[lo:lo + cnt]
+            self._ckbd_chain(px, B, H, W, params, ctx_map, ws, filt)
+            yield cnt, px, ws["gp"]
+
     def _ckbd_encode(self, y, params):
-        """The two passes of compress -> (symbols int32 [B, H*W, M], indexes int32 [B, H*W, M], y_hat), the buffers in raster order: all
-        launches on the current stream, no host sync."""
-        ops._require_gpu(y, "mbt2018-checkerboard compress")
-        B, M, H, W = y.shape
-        y = y.contiguous(memory_format=CL)
-        params = params.contiguous(memory_format=CL)
-        na, nn_, pix = self._ckbd_lists(H, W, y.device)
-        ws = self._ckbd_workspace(B * max(na, nn_), y.device)
-        filt = self._ckbd_filters()
-        table = self.gaussian_conditional.scale_table
-        y_hat = torch.zeros_like(y, memory_format=CL)
-        sym = torch.empty((B, H * W, M), device=y.device, dtype=torch.int32)
-        idx = torch.empty((B, H * W, M), device=y.device, dtype=torch.int32)
-        if na:
-            ctx_map = torch.zeros((B, 2 * M, H, W), device=y.device, dtype=torch.float32).contiguous(memory_format=CL)
-            self._ckbd_chain(pix[:na], B, H, W, params, ctx_map, ws, filt)
-            ops.ar_finish_encode(ws["gp"], M, pix[:na], y, y_hat, table, sym, idx)
-        ctx_map = self.context_prediction(y_hat)
-        self._ckbd_chain(pix[na:], B, H, W, params, ctx_map, ws, filt)
-        ops.ar_finish_encode(ws["gp"], M, pix[na:], y, y_hat, table, sym, idx)
-        return sym, idx, y_hat
+        """The two passes of compress: _encode_passes over _ckbd_passes"""
+        return self._encode_passes("mbt2018-checkerboard", y, params, self._ckbd_passes)
 
     @staticmethod
     def _ckbd_order(H, W):
@@ -416,35 +434,9 @@ class JointCheckerboardHierarchicalPriors(JointAutoregressiveHierarchicalPriors)
                      for i in range(both.shape[1])]
         return coded_item(y_strings, z_strings, z_size)
 
-    @torch.no_grad()
     def _ckbd_decode(self, y_strings, params):
-        """The two passes of decompress -> y_hat: per pass one index download, one incremental decode per image, one symbol upload."""
-        params = params.contiguous(memory_format=CL)
-        dev = params.device
-        B, M, (H, W) = params.shape[0], self.M, params.shape[2:]
-        if len(y_strings) != B:
-            raise ValueError(f"decompress: {len(y_strings)} y streams for {B} z streams")
-        table = self.gaussian_conditional.scale_table
-        na, nn_, pix = self._ckbd_lists(H, W, dev)
-        rows = B * max(na, nn_)
-        ws = self._ckbd_workspace(rows, dev)
-        filt = self._ckbd_filters()
-        y_hat = torch.zeros((B, M, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
-        decode = table_decode([d.decode_stream for d in open_decoders(y_strings)], self.gaussian_conditional.host_tables())
-        hop = HostHop(rows * M, rows * M, dev)
-        ctx_map = torch.zeros((B, 2 * M, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
-        for lo, cnt in ((0, na), (na, nn_)):
-            if not cnt:
-                continue
-            px = pix[lo:lo + cnt]
-            if lo:
-                ctx_map = self.context_prediction(y_hat)
-            idx_dev, sym_dev = (t.view(B * cnt, M) for t in hop.step(B * cnt * M, B * cnt * M))
-            self._ckbd_chain(px, B, H, W, params, ctx_map, ws, filt)
-            ops.ar_finish_decode(ws["gp"], M, px, B, H, W, table, idx_dev)
-            hop.run(decode)
-            ops.ar_commit(sym_dev, ws["gp"], M, px, y_hat)
-        return y_hat
+        """The two passes of decompress -> y_hat: _decode_passes over _ckbd_passes, whose larger pass is the non-anchors ((0, 0) is one)"""
+        return self._decode_passes(y_strings, params, (params.shape[2] * params.shape[3] + 1) // 2, self._ckbd_passes)
 
     @torch.no_grad()
     def decompress(self, strings, shape):

@@ -56,6 +56,8 @@ def test_split_bytes_and_the_default_beside_them(coded):
 
 
 def test_device_decode_is_exact_and_hop_free(coded):
+    from clc_amd.models import coding
+
     p, split, plain = coded["p"], coded["split"], coded["plain"]
     H, W = 8, 12
     counts = {}
@@ -67,7 +69,7 @@ def test_device_decode_is_exact_and_hop_free(coded):
     print(f"device decoder: {counts[False]} device -> host copies with check=False, {counts[True]} with check=True")
     assert counts == {False: 0, True: 1}
     # the pass itself: no copy, and the encoder's y_hat bit for bit; every sub-stream at its end
-    subs = p._split_parse(split["strings"][0], S_)
+    subs = coding.stream_parse(coded["ans"].SPLIT_STREAM, split["strings"][0], S_, "substreams")
     with _count_d2h() as c:
         y_hat, state = p._gmm_decode_split(subs, coded["params"])
     assert c.n == 0

@@ -1,7 +1,8 @@
 """The host-side pieces the context-model coders share (clc_amd/models/coding.py) and the one container implementation behind
 ans.split_pack / ans.lanes_pack, where no GPU is needed: the upload image of a device-decoded batch against a plain-loop restatement
 (a split batch at n_state = 2, a lanes batch at n_state = 128, unequal lengths, one stream that is its state alone), the int32 refusal
-from word counts alone, the end-state check under both nouns, and the two containers' own magic and limits.
+from word counts alone, the end-state check under both nouns, the two containers' own magic and limits, and the one batch parser
+over both.
 """
 import numpy as np
 import pytest
@@ -81,13 +82,19 @@ def test_container_parameterisation():
     """one implementation, two formats: each pair keeps its own magic, largest count and least length"""
     from clc_amd import ans
 
-    table = [(ans.split_pack, ans.split_unpack, ans.SPLIT_MAGIC, "S", 64, "sub-stream", 8),
-             (ans.lanes_pack, ans.lanes_unpack, ans.LANES_MAGIC, "W", 16, "wave stream", 512)]
+    from clc_amd.models import coding
+
+    table = [(ans.split_pack, ans.split_unpack, ans.SPLIT_MAGIC, "S", 64, "sub-stream", 8, ans.SPLIT_STREAM, "substreams"),
+             (ans.lanes_pack, ans.lanes_unpack, ans.LANES_MAGIC, "W", 16, "wave stream", 512, ans.LANES_STREAM, "lanes")]
     blobs = []
-    for pack, unpack, magic, letter, most, noun, least in table:
+    for pack, unpack, magic, letter, most, noun, least, fmt, keyword in table:
         streams = [bytes([i]) * (least + 4 * i) for i in range(most)]
         blob = pack(streams)   # the largest count is accepted: S = 64 by split, W = 16 by lanes
         assert blob[:4] == magic and blob[4] == most and unpack(blob) == streams
+        # the models' parser of a batch, one for both containers: the caller's keyword and the format's noun in its refusal
+        assert coding.stream_parse(fmt, [blob, pack(streams[:2])][:1], most, keyword) == [streams]
+        with pytest.raises(ValueError, match=rf"^decompress: {keyword} = {most}, but the header of image 1 says 2 {noun}s$"):
+            coding.stream_parse(fmt, [blob, pack(streams[:2])], most, keyword)
         with pytest.raises(ValueError, match=rf"_pack: {letter} must be between 1 and {most} {noun}s \(got {most + 1}\)"):
             pack(streams + streams[:1])
         with pytest.raises(ValueError, match=rf"_pack: {noun} 1 has {least - 4} bytes; a length must be a multiple of 4 and at least {least}$"):

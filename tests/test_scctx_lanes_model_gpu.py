@@ -74,6 +74,7 @@ def test_bytes_are_the_host_encoder_s(model, coded):
 
 def test_x_hat_and_y_hat_from_every_decoder(model, coded):
     from clc_amd import ans
+    from clc_amd.models import coding
 
     lanes, default = coded["lanes"], coded["default"]
     want = model._synthesis(coded["y_hat"]).clamp(0, 1)
@@ -81,7 +82,7 @@ def test_x_hat_and_y_hat_from_every_decoder(model, coded):
     for device_coder in (True, False):
         y_hat, state = model._scctx_decode_lanes(subs, coded["params"], device_coder)
         assert torch.equal(y_hat, coded["y_hat"]), device_coder
-        model._lanes_check(state, subs)   # every wave stream ended at (2^31 x 64, its word count)
+        coding.lanes_check(state, subs)   # every wave stream ended at (2^31 x 64, its word count)
         for check in (True, False):
             out = model.decompress(lanes["strings"], lanes["shape"], lanes=LANES_W, device_coder=device_coder, check=check)
             assert sorted(out) == ["x_hat"] and torch.equal(out["x_hat"], want), (device_coder, check)

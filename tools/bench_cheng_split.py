@@ -31,7 +31,8 @@ if not torch.cuda.is_available():
     sys.exit("bench_cheng_split.py measures on the GPU: none found")
 dev = torch.device("cuda:0")
 
-from clc_amd import models
+from clc_amd import ans, models
+from clc_amd.models import coding
 from clc_amd.recipe import apply_weight_recipe, synthetic_image
 
 K, N = 3, 192
@@ -121,7 +122,7 @@ for h, w in ((256, 256), (512, 768)):
             case.setdefault("y_bytes_over_default", {})[f"S{S}"] = n / nplain
         # the hop-free pass alone, device time by events
         params = net._hyper_synthesis(net.entropy_bottleneck.decompress(plain["strings"][1], plain["shape"]))
-        subs = net._split_parse(split[S_GATE]["strings"][0], S_GATE)
+        subs = coding.stream_parse(ans.SPLIT_STREAM, split[S_GATE]["strings"][0], S_GATE, "substreams")
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev = []
         for _ in range(3):

@@ -34,6 +34,7 @@ if not torch.cuda.is_available():
 dev = torch.device("cuda:0")
 
 from clc_amd import models
+from clc_amd.models import coding
 from clc_amd.recipe import apply_weight_recipe, synthetic_image
 
 W_HOST, W_DEVICE, W_GATE = 4, (1, 4, 16), 4
@@ -132,7 +133,7 @@ for h, w in ((256, 256), (512, 768)):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         case["y_pass_event_ms"] = {}
         for W in W_DEVICE:
-            subs = net._lanes_parse(lanes[W]["strings"][0], W)
+            subs = coding.lanes_parse(lanes[W]["strings"][0], W)
             ev = []
             for _ in range(3):
                 torch.cuda.synchronize()
