@@ -155,7 +155,14 @@ def lanes_pack(streams) -> bytes:
         b"CLN1" | u8 W | u8 64 | 2 x u8 0 | W x u32 byte length | the W wave streams, back to back
 
     A wave stream is 32-bit words and starts with its 64 lane states (512 bytes).  Overhead against the one stream of ``encode``:
-    8 + 4 W bytes of header plus 512 W bytes of lane states."""
+    8 + 4 W bytes of header plus 512 W bytes of lane states.
+
+    What the SEGMENTS of an image are is the model's: elic2022's 2 K passes, the slices of CLC / TCM in NHWC order, and for the two
+    context models of models/hyperprior.py the dependent steps of their schedule — mbt2018: the non-empty steps of
+    ar_schedule(H, W, "wavefront") in ascending t = w + 3 h, inside a step its pixels in ascending h, channels inner (ar_lanes_order;
+    W + 3 (H - 1) segments at most, so its device encoder reads the lengths from memory: clc_rans_lanes_encode_list);
+    mbt2018-checkerboard: the anchors, then the non-anchors, each in raster order with channels inner.  The container does not record
+    the segments; encoder and decoder derive them from the latent's size."""
     return _pack(LANES_STREAM, streams)
 
 

@@ -9,6 +9,10 @@
 //
 // No atomics, no wave waits on another; every loop is bounded by a constant or by the symbol count.  The two kernels of the table-coded
 // stream use no LDS and no barrier; rans_lanes_decode_gauss_kernel keeps the scale table in LDS (one barrier before its first round).
+//
+// Two kernels are templates over the one thing their entries differ in.  The encoder reads its segment lengths from a by-value struct
+// (clc_rans_lanes_encode, P <= 32) or from device memory (clc_rans_lanes_encode_list, any P).  The Gaussian step lands a (row, channel)
+// in a dense [rows][ldh] map (clc_rans_lanes_decode_gauss) or, through a pixel list, in an NHWC latent (clc_ar_lanes_decode).
 #include "common.h"
 
 namespace {
@@ -120,6 +124,9 @@ __global__ __launch_bounds__(64) void rans_lanes_decode_kernel(const LanesDecArg
   if (lane == 0) st[2 * kLanes] = pos;
 }
 
+struct LanesSegList { int P; const int32_t* n; };   // clc_rans_lanes_segments with the lengths in device memory
+
+template <class Segs>
 struct LanesEncArgs {
   const int32_t* symbols;
   const int32_t* indexes; long ld;
@@ -128,10 +135,11 @@ struct LanesEncArgs {
   const int32_t* regions;   // [B][W][2]: first word, capacity
   int32_t* result;          // [B][W][2]: first word, count — or (code < 0, 0)
   int W;
-  clc_rans_lanes_segments segs;
+  Segs segs;   // .P lengths .n[p]; a negative length counts as 0
 };
 
-__global__ __launch_bounds__(64) void rans_lanes_encode_kernel(const LanesEncArgs a) {
+template <class Segs>
+__global__ __launch_bounds__(64) void rans_lanes_encode_kernel(const LanesEncArgs<Segs> a) {
   const int lane = threadIdx.x;
   const int wid = blockIdx.x;   // (b, w)
   const int b = wid / a.W, w = wid - b * a.W;
@@ -148,10 +156,10 @@ __global__ __launch_bounds__(64) void rans_lanes_encode_kernel(const LanesEncArg
   uint64_t x = kL;
   bool zero_freq = false;
   long at = 0;
-  for (int p = 0; p < a.segs.P; ++p) at += a.segs.n[p];
+  for (int p = 0; p < a.segs.P; ++p) at += a.segs.n[p] > 0 ? a.segs.n[p] : 0;
 #pragma unroll 1
   for (int p = a.segs.P - 1; p >= 0; --p) {
-    const int n = a.segs.n[p];
+    const int n = a.segs.n[p] > 0 ? a.segs.n[p] : 0;
     at -= n;
     const int chunks = (n + kLanes - 1) / kLanes;
     if (chunks <= w) continue;
@@ -222,6 +230,10 @@ __global__ __launch_bounds__(64) void rans_lanes_encode_kernel(const LanesEncArg
 // rans_lanes_decode_kernel with the row index formed here (quantize_build_indexes_kernel's, entropy.hip) and the symbol leaving as
 // y_hat = (float)symbol + mu.  The coder's part is that kernel's, statement for statement: it is repeated, not shared, so that the
 // kernel of the table-coded stream keeps its code.
+//
+// WHERE a (row, channel) lands is the template's parameter.  LanesDenseRows: at r * ldh + c, the slice models' map.  LanesPixelList: the
+// rows of an image are the pixels of a step of the context model's schedule, row p of image b lands at pixel pix[p] = (h, w) of the
+// NHWC latent, ((b H + h) W + w) ldh + c (ar_commit_kernel's expression), and a pair outside the map is decoded and not written.
 constexpr float kScaleBound = 0.11f;
 constexpr int kMaxScales = 256;
 
@@ -238,7 +250,24 @@ struct LanesGaussArgs {
   int32_t* symbols; long ld_sym;   // symbols may be null
 };
 
-__global__ __launch_bounds__(64) void rans_lanes_decode_gauss_kernel(const LanesGaussArgs a) {
+struct LanesDenseRows {
+  static constexpr bool kEveryRow = true;   // every row has a place
+  __device__ __forceinline__ long at(int, long r, int, int c, long ldh) const { return r * ldh + c; }
+};
+
+struct LanesPixelList {
+  static constexpr bool kEveryRow = false;
+  const int32_t* pix;   // [P][2]: (h, w) of the image's row p
+  int H, W;
+  __device__ __forceinline__ long at(int b, long, int p, int c, long ldh) const {   // -1: outside the map
+    const int h = pix[2 * p], w = pix[2 * p + 1];
+    if (h < 0 || h >= H || w < 0 || w >= W) return -1;
+    return (((long)b * H + h) * W + w) * ldh + c;
+  }
+};
+
+template <class Landing>
+__global__ __launch_bounds__(64) void rans_lanes_decode_gauss_kernel(const LanesGaussArgs a, const Landing place) {
   __shared__ float tb[kMaxScales];
   const int lane = threadIdx.x;
   const int ns1 = a.n_scales - 1;
@@ -326,7 +355,7 @@ __global__ __launch_bounds__(64) void rans_lanes_decode_gauss_kernel(const Lanes
       size_next = clamp_int(a.t.cdf_sizes[ci_next], 2, a.t.cdf_stride);
       off_next = a.t.offsets[ci_next];
       mu_next = a.mu[r * a.ldmu + c];
-      at_next = r * a.ldh + c;
+      at_next = place.at(b, r, row.p, c, a.ldh);
     }
     advance(row);
   };
@@ -386,7 +415,7 @@ __global__ __launch_bounds__(64) void rans_lanes_decode_gauss_kernel(const Lanes
     }
     if (active) {
       const int32_t sym = (int32_t)(value + (uint32_t)off);
-      a.y_hat[at] = (float)sym + m_;
+      if (Landing::kEveryRow || at >= 0) a.y_hat[at] = (float)sym + m_;
       if (a.symbols) a.symbols[(long)b * a.ld_sym + j] = sym;
     }
   }
@@ -482,11 +511,11 @@ extern "C" int clc_rans_lanes_encode(const int32_t* symbols, const int32_t* inde
   CLC_CHECK(total < (1l << 27), "clc_rans_lanes_encode: %ld symbols per image; a region's 128 + 10 n words must stay below 2^31", total);
   CLC_CHECK(ld >= total, "clc_rans_lanes_encode: ld < the segments' total (%ld < %ld)", ld, total);
   CLC_CHECK((long)B * W < (1l << 24), "clc_rans_lanes_encode: B * W must be below 2^24");
-  LanesEncArgs a = {};
+  LanesEncArgs<clc_rans_lanes_segments> a = {};
   a.symbols = symbols; a.indexes = indexes; a.ld = ld;
   a.t = {cdfs, cdf_stride, n_rows, cdf_sizes, offsets};
   a.out = out; a.regions = regions; a.result = result; a.W = W; a.segs = segs;
-  hipLaunchKernelGGL(rans_lanes_encode_kernel, dim3(B * W), dim3(kLanes), 0, ST, a);
+  hipLaunchKernelGGL(rans_lanes_encode_kernel<clc_rans_lanes_segments>, dim3(B * W), dim3(kLanes), 0, ST, a);
   CLC_LAUNCH_CHECK();
   return 0;
 }
@@ -513,7 +542,61 @@ extern "C" int clc_rans_lanes_decode_gauss(const float* scale, long ldsc, const 
   a.t = {cdfs, cdf_stride, n_rows, cdf_sizes, offsets};
   a.words = words; a.spans = spans; a.state = reinterpret_cast<uint32_t*>(state);
   a.y_hat = y_hat; a.ldh = ldh; a.symbols = symbols; a.ld_sym = ld_sym;
-  hipLaunchKernelGGL(rans_lanes_decode_gauss_kernel, dim3(B * W), dim3(kLanes), 0, ST, a);
+  const LanesDenseRows place = {};
+  hipLaunchKernelGGL(rans_lanes_decode_gauss_kernel<LanesDenseRows>, dim3(B * W), dim3(kLanes), 0, ST, a, place);
+  CLC_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int clc_ar_lanes_decode(const float* gp, long ldg, int M, const int32_t* pix, int P, int B, int H, int W_map, const float* scale_table,
+                                   int n_scales, const int32_t* cdfs, int cdf_stride, int n_rows, const int32_t* cdf_sizes, const int32_t* offsets,
+                                   const uint32_t* words, const int32_t* spans, clc_rans_lanes_state* state, int W, float* y_hat, long ldh,
+                                   int32_t* symbols, long ld_sym, clc_stream_t stream) {
+  CLC_CHECK(gp && scale_table && words && spans && state && y_hat, "clc_ar_lanes_decode: null pointer");
+  CLC_CHECK(cdfs && cdf_sizes && offsets, "clc_ar_lanes_decode: null table pointer");
+  CLC_CHECK(cdf_stride >= 2 && n_rows >= 1, "clc_ar_lanes_decode: the table needs cdf_stride >= 2 and n_rows >= 1 (got %d, %d)", cdf_stride, n_rows);
+  CLC_CHECK(n_scales > 1 && n_scales <= kMaxScales, "clc_ar_lanes_decode: n_scales must be between 2 and %d (got %d)", kMaxScales, n_scales);
+  CLC_CHECK(W >= 1 && W <= CLC_RANS_LANES_MAX_W, "clc_ar_lanes_decode: W must be between 1 and %d waves (got %d)", CLC_RANS_LANES_MAX_W, W);
+  CLC_CHECK(P >= 0 && B > 0 && H > 0 && W_map > 0 && M > 0, "clc_ar_lanes_decode: P must not be negative and B, H, W and M must be positive (got %d, %d, %d, %d, %d)",
+            P, B, H, W_map, M);
+  CLC_CHECK((long)P * M < (1l << 30), "clc_ar_lanes_decode: n = P * M must be below 2^30 symbols per image (got %ld)", (long)P * M);
+  CLC_CHECK(P == 0 || pix, "clc_ar_lanes_decode: null pixel list");
+  CLC_CHECK(ldg >= 2l * M, "clc_ar_lanes_decode: ldg < 2 M (scales first, means second)");
+  CLC_CHECK(ldh >= M, "clc_ar_lanes_decode: ldh < M");
+  CLC_CHECK((long)B * H * W_map < (1l << 31), "clc_ar_lanes_decode: B * H * W must be below 2^31");
+  const int n = P * M;
+  CLC_CHECK(!symbols || ld_sym >= n, "clc_ar_lanes_decode: ld_sym < n");
+  CLC_CHECK((long)B * W < (1l << 24), "clc_ar_lanes_decode: B * W must be below 2^24");
+  if (n == 0) return 0;   // an empty step contributes nothing
+  LanesGaussArgs a = {};
+  a.scale = gp; a.ldsc = ldg; a.mu = gp + M; a.ldmu = ldg; a.C = M; a.n = n; a.W = W;
+  a.table = scale_table; a.n_scales = n_scales;
+  a.t = {cdfs, cdf_stride, n_rows, cdf_sizes, offsets};
+  a.words = words; a.spans = spans; a.state = reinterpret_cast<uint32_t*>(state);
+  a.y_hat = y_hat; a.ldh = ldh; a.symbols = symbols; a.ld_sym = ld_sym;
+  const LanesPixelList place = {pix, H, W_map};
+  hipLaunchKernelGGL(rans_lanes_decode_gauss_kernel<LanesPixelList>, dim3(B * W), dim3(kLanes), 0, ST, a, place);
+  CLC_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int clc_rans_lanes_encode_list(const int32_t* symbols, const int32_t* indexes, long ld, int B, const int32_t* seg_len, int P, int W,
+                                          const int32_t* cdfs, int cdf_stride, int n_rows, const int32_t* cdf_sizes, const int32_t* offsets,
+                                          uint32_t* out, const int32_t* regions, int32_t* result, clc_stream_t stream) {
+  CLC_CHECK(symbols && indexes && out && regions && result, "clc_rans_lanes_encode_list: null pointer");
+  CLC_CHECK(cdfs && cdf_sizes && offsets, "clc_rans_lanes_encode_list: null table pointer");
+  CLC_CHECK(cdf_stride >= 2 && n_rows >= 1, "clc_rans_lanes_encode_list: the table needs cdf_stride >= 2 and n_rows >= 1 (got %d, %d)", cdf_stride, n_rows);
+  CLC_CHECK(W >= 1 && W <= CLC_RANS_LANES_MAX_W, "clc_rans_lanes_encode_list: W must be between 1 and %d waves (got %d)", CLC_RANS_LANES_MAX_W, W);
+  CLC_CHECK(B > 0, "clc_rans_lanes_encode_list: B must be positive (got %d)", B);
+  CLC_CHECK(P >= 0, "clc_rans_lanes_encode_list: P must not be negative (got %d)", P);
+  CLC_CHECK(P == 0 || seg_len, "clc_rans_lanes_encode_list: null segment list");
+  CLC_CHECK(ld >= 0 && ld < (1l << 27), "clc_rans_lanes_encode_list: ld must be between 0 and 2^27 - 1 (got %ld); a region's 128 + 10 n words must stay below 2^31", ld);
+  CLC_CHECK((long)B * W < (1l << 24), "clc_rans_lanes_encode_list: B * W must be below 2^24");
+  LanesEncArgs<LanesSegList> a = {};
+  a.symbols = symbols; a.indexes = indexes; a.ld = ld;
+  a.t = {cdfs, cdf_stride, n_rows, cdf_sizes, offsets};
+  a.out = out; a.regions = regions; a.result = result; a.W = W; a.segs = {P, seg_len};
+  hipLaunchKernelGGL(rans_lanes_encode_kernel<LanesSegList>, dim3(B * W), dim3(kLanes), 0, ST, a);
   CLC_LAUNCH_CHECK();
   return 0;
 }

@@ -293,6 +293,8 @@ SIGNATURES = {
     "clc_rans_lanes_encode": (_i, [fp, fp, _l, _i, LanesSegments, _i, fp, _i, _i, fp, fp, fp, fp, fp, fp]),
     "clc_rans_lanes_decode_gauss": (_i, [fp, _l, fp, _l, _i, _i, _i, fp, _i, fp, _i, _i, fp, fp, fp, fp, fp, _i, fp, _l, fp, _l, fp]),
     "clc_rans_lanes_pack": (_i, [fp, _l, fp, _i, _i, fp, _l, fp, fp]),
+    "clc_ar_lanes_decode": (_i, [fp, _l, _i, fp, _i, _i, _i, _i, fp, _i, fp, _i, _i, fp, fp, fp, fp, fp, _i, fp, _l, fp, _l, fp]),
+    "clc_rans_lanes_encode_list": (_i, [fp, fp, _l, _i, fp, _i, _i, fp, _i, _i, fp, fp, fp, fp, fp, fp]),
 }
 
 

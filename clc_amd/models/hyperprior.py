@@ -10,7 +10,12 @@ models are checked against a plain-torch restatement of the same definitions (te
 They train through plain autograd and code through the model methods; TrainEngine, graphed_training, CodecEngine and ReferenceBank
 do not take them.  The host side of the context-model coders — the start of a decoder's pass loop, the symbols of a host-decoded step,
 the result item — is coding.py's; ``mbt2018`` and ``mbt2018-checkerboard`` each state their schedule once (_ar_passes, _ckbd_passes) and
-share one encoder loop and one decoder loop over it (_encode_passes, _decode_passes).
+share one encoder loop and one decoder loop over it (_encode_passes, _decode_passes / _decode_from).
+
+THE LANES STREAM (``compress(x, lanes=W)`` / ``decompress(..., lanes=W)``; DESIGN 27, include/clc_hip.h, clc_amd/ans.py) is opt-in and
+shared by both models: the y string becomes the CLN1 container cut by the model's dependent steps — mbt2018's wavefront steps
+(ar_lanes_order), the checkerboard's two passes (_ckbd_order) — and _decode_lanes decodes it on the device, per step the chain and ONE
+clc_ar_lanes_decode, with no download and no synchronize.  With lanes=None nothing of it runs.
 """
 from __future__ import annotations
 
@@ -23,7 +28,8 @@ from ..entropy_models import EntropyBottleneck, GaussianConditional
 from ..layers import GDN, CheckerboardMaskedConv2d, Conv2d, MaskedConv2d, conv, deconv
 from ..ops import ACT_LRELU, ACT_NONE, ACT_RELU, CL
 from .clc import CompressionModel, _resize_registered_buffers, get_scale_table
-from .coding import CodeInputs, HostSymbols, coded_item, decoder_start, linear_filters, open_decoders
+from .coding import (CodeInputs, HostSymbols, coded_item, decoder_start, lanes_check, lanes_count, lanes_parse, lanes_strings, linear_filters,
+                     open_decoders, refuse_lanes_strings, upload_streams)
 
 
 class ScaleHyperprior(CompressionModel):
@@ -190,6 +196,13 @@ def ar_schedule(H, W, order="wavefront"):
     return steps
 
 
+def ar_lanes_order(H, W):
+    """THE PIXEL ORDER of mbt2018's lanes stream, as raster positions h * W + w -> int64 [H * W]: the non-empty steps of
+    ar_schedule(H, W, "wavefront") in ascending t, inside a step its pixels in list order (ascending h).  The stream's segments are
+    those steps (JointAutoregressiveHierarchicalPriors._lanes_segments); channels are inner."""
+    return np.array([h * int(W) + w for step in ar_schedule(H, W, "wavefront") for h, w in step], dtype=np.int64)
+
+
 def ckbd_lists(H, W, dev):
     """(number of anchors, number of non-anchors, the uploaded pixel list: anchors first)"""
     anchors, others = ckbd_pixels(H, W)
@@ -319,9 +332,14 @@ class JointAutoregressiveHierarchicalPriors(CodeInputs, MeanScaleHyperprior):
         image on a decoder opened once, one symbol upload.  most: the pixels of the schedule's largest step."""
         params, y_hat = decoder_start(params, len(y_strings), self.M)
         B, M, H, W = y_hat.shape
-        gc = self.gaussian_conditional
-        table = gc.scale_table
-        src = HostSymbols([d.decode_stream for d in open_decoders(y_strings)], gc.host_tables(), B * most * M, y_hat.device)
+        src = HostSymbols([d.decode_stream for d in open_decoders(y_strings)], self.gaussian_conditional.host_tables(), B * most * M, y_hat.device)
+        return self._decode_from(src, params, y_hat, passes, *schedule)
+
+    def _decode_from(self, src, params, y_hat, passes, *schedule):
+        """The decoder's loop over a source of symbols with a hop per step (coding.HostSymbols over one-stream or lanes decoders;
+        coding.DeviceLanesSymbols fits too): per step the chain, ar_finish_decode, the source's step and ar_commit -> y_hat."""
+        B, M, H, W = y_hat.shape
+        table = self.gaussian_conditional.scale_table
         cut = None
         for cnt, px, gp in passes(params, y_hat, *schedule):
             if cnt != cut:   # the views are cut when the step's size changes: once for mbt2018's pixel per step, whatever the latent
@@ -335,18 +353,101 @@ class JointAutoregressiveHierarchicalPriors(CodeInputs, MeanScaleHyperprior):
         """The autoregressive pass of compress: _encode_passes over the steps of ``order``"""
         return self._encode_passes("mbt2018", y, params, self._ar_passes, order)
 
+    # ---- the lanes stream: its order and segments (one owner each per model), the encoder's tail, the decoder's loop ----
+    _lanes_order = staticmethod(ar_lanes_order)
+    _lanes_encoder = staticmethod(ops.rans_lanes_encode_list)   # a wavefront has more segments than clc_rans_lanes_encode takes by value
+
+    def _lanes_segments(self, H, W):
+        """the lanes stream's segments: the non-empty wavefront steps in ar_lanes_order, n = pixels of the step x M"""
+        return [len(s) * self.M for s in ar_schedule(H, W, "wavefront") if s]
+
+    def _lanes_passes(self, params, y_hat):
+        """the schedule the lanes stream is cut by: the decoder runs the wavefront too"""
+        return self._ar_passes(params, y_hat, "wavefront")
+
+    @staticmethod
+    def _lanes_most(H, W):
+        """the pixels of the largest step"""
+        return max(len(s) for s in ar_schedule(H, W, "wavefront"))
+
+    def _lanes_encode_device(self, sym, idx, segments, W):
+        """int32 [B, T] device symbols / indexes in stream order -> per image its lanes string: one launch of the model's lanes encoder
+        and one clc_rans_lanes_pack for the batch, then two device -> host copies (the header, the packed words)."""
+        gc = self.gaussian_conditional
+        B = sym.shape[0]
+        out, _, result = self._lanes_encoder(sym, idx, segments, W, (gc._quantized_cdf, gc._cdf_length, gc._offset))
+        packed, header = ops.rans_lanes_pack(out, result)
+        head = header.cpu().numpy()
+        words = packed[:int(head[B * W])].cpu().numpy() if (head[:B * W] >= 0).all() else np.zeros(0, np.int32)
+        return lanes_strings(head, words, B, W)   # (raises by name on a negative code)
+
+    def _lanes_y_strings(self, sym, idx, H, W, Wn):
+        """_encode_passes' raster [B, H*W, M] buffers -> the lanes strings: gathered into stream order on the device by one index tensor"""
+        order = torch.from_numpy(self._lanes_order(H, W)).to(sym.device)
+        flat = lambda t: t.index_select(1, order).reshape(t.shape[0], -1)
+        return self._lanes_encode_device(flat(sym), flat(idx), self._lanes_segments(H, W), Wn)
+
     @torch.no_grad()
-    def compress(self, x, order="wavefront"):
+    def _decode_lanes(self, subs, params, device_coder=True):
+        """The decoder over lanes streams (subs[b][w]: bytes), for both models -> (y_hat, state).
+        device_coder: one pinned upload of every wave stream's states, spans and words, then per step of _lanes_passes the chain and ONE
+        clc_ar_lanes_decode — stream-ordered launches only, no download, no synchronize, no per-image loop; state is the device's
+        int32 [B, W, 130] (64 x (x low, x high), pos, pad) as the last step left it.
+        Host coder: _decode_from with one ans.LanesDecoder per image, a hop per step; state is the list of decoders."""
+        params, y_hat = decoder_start(params, len(subs), self.M)
+        B, M, H, W = y_hat.shape
+        gc = self.gaussian_conditional
+        if not device_coder:
+            decoders = [ans.LanesDecoder(img) for img in subs]
+            src = HostSymbols([d.decode for d in decoders], gc.host_tables(), B * self._lanes_most(H, W) * M, y_hat.device, state=decoders)
+            return self._decode_from(src, params, y_hat, self._lanes_passes), decoders
+        tables, table = (gc._quantized_cdf, gc._cdf_length, gc._offset), gc.scale_table
+        state, spans, words = upload_streams(subs, 2 * ans.LANES, y_hat.device)   # a wave stream starts with its 64 lane states
+        for _, px, gp in self._lanes_passes(params, y_hat):
+            ops.ar_lanes_decode(gp, M, px, B, H, W, table, tables, words, spans, state, y_hat)
+        return y_hat, state
+
+    @torch.no_grad()
+    def _decompress_lanes(self, strings, shape, Wn, device_coder, check):
+        subs = lanes_parse(strings[0], Wn)   # the headers, before any device work
+        if len(subs) != len(strings[1]):
+            raise ValueError(f"decompress: {len(subs)} y streams for {len(strings[1])} z streams")
+        z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
+        y_hat, state = self._decode_lanes(subs, self._hyper_synthesis(z_hat), device_coder)
+        x_hat = self._synthesis(y_hat).clamp_(0, 1)
+        if check:
+            lanes_check(state, subs)
+        return {"x_hat": x_hat}
+
+    @torch.no_grad()
+    def compress(self, x, order="wavefront", lanes=None):
+        """order: the encoder's schedule of computation only; the bytes do not depend on it.  lanes=None: CompressAI's raster stream.
+        lanes=W: THE LANES STREAM (clc_amd/ans.py: lanes_pack; include/clc_hip.h), W wave streams of 64 rANS lanes per image cut by
+        wavefront steps, encoded on the device, and "lanes": W in the result; pass the same W to decompress."""
+        Wn = lanes_count(lanes, f"{type(self).__name__}.compress")
         y, params, z_strings, z_size = self._code_inputs(x)
-        cdf, ln, off = self.gaussian_conditional.host_tables()
         sym, idx, _ = self._ar_encode(y, params, order)
+        if Wn is not None:   # the buffers stay on the device
+            return coded_item(self._lanes_y_strings(sym, idx, y.shape[2], y.shape[3], Wn), z_strings, z_size, lanes=Wn)
+        cdf, ln, off = self.gaussian_conditional.host_tables()
         both = torch.stack((sym, idx)).cpu().numpy()   # the one device -> host copy: [2, B, H*W, M], raster pixels, channels inner
         y_strings = [ans.encode(both[0, i].reshape(-1), both[1, i].reshape(-1), cdf, ln, off) for i in range(both.shape[1])]
         return coded_item(y_strings, z_strings, z_size)
 
     @torch.no_grad()
-    def decompress(self, strings, shape):
+    def decompress(self, strings, shape, lanes=None, device_coder=True, check=True):
+        """lanes=None: the one-stream format, one hop per raster pixel.  lanes=W: the lanes stream of compress(x, lanes=W); its headers
+        are parsed on the host before any device work.  device_coder=True decodes it on the device, W + 3 (H - 1) wavefront steps of
+        the chain and one clc_ar_lanes_decode each: no device -> host copy and no synchronize between the upload of the streams and the
+        finished y_hat; check=True adds ONE download of the final coder states, after the synthesis transform has been launched, and
+        raises ValueError naming the image and the wave streams that did not end where a whole stream ends (a check against streams
+        out of step or cut short, not a checksum).  device_coder=False runs the same format on the host coder (ans.LanesDecoder), a
+        hop per step: the oracle and the fallback."""
+        Wn = lanes_count(lanes, f"{type(self).__name__}.decompress")
         assert isinstance(strings, (list, tuple)) and len(strings) == 2
+        if Wn is not None:
+            return self._decompress_lanes(strings, shape, Wn, device_coder, check)
+        refuse_lanes_strings(strings[0])
         z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
         y_hat = self._decode_passes(strings[0], self._hyper_synthesis(z_hat), 1, self._ar_passes, "raster")
         return {"x_hat": self._synthesis(y_hat).clamp_(0, 1)}
@@ -423,11 +524,35 @@ class JointCheckerboardHierarchicalPriors(JointAutoregressiveHierarchicalPriors)
         anchors, others = ckbd_pixels(H, W)
         return np.array([h * W + w for h, w in anchors + others], dtype=np.int64)
 
+    # ---- the lanes stream: two segments in _ckbd_order, today's symbol order; the tail and the decoder's loop are inherited ----
+    _lanes_encoder = staticmethod(ops.rans_lanes_encode)
+
+    @staticmethod
+    def _lanes_order(H, W):
+        return JointCheckerboardHierarchicalPriors._ckbd_order(H, W)
+
+    def _lanes_segments(self, H, W):
+        """the lanes stream's segments: the anchors, then the non-anchors, n = pixels of the pass x M"""
+        anchors, others = ckbd_pixels(H, W)
+        return [len(anchors) * self.M, len(others) * self.M]
+
+    def _lanes_passes(self, params, y_hat):
+        return self._ckbd_passes(params, y_hat)
+
+    @staticmethod
+    def _lanes_most(H, W):
+        return (H * W + 1) // 2
+
     @torch.no_grad()
-    def compress(self, x):
+    def compress(self, x, lanes=None):
+        """lanes=None: the one-stream format.  lanes=W: the lanes stream, the same symbols cut into the two passes as segments and encoded
+        on the device; "lanes": W in the result; pass the same W to decompress."""
+        Wn = lanes_count(lanes, f"{type(self).__name__}.compress")
         y, params, z_strings, z_size = self._code_inputs(x)
-        cdf, ln, off = self.gaussian_conditional.host_tables()
         sym, idx, _ = self._ckbd_encode(y, params)
+        if Wn is not None:   # the buffers stay on the device
+            return coded_item(self._lanes_y_strings(sym, idx, y.shape[2], y.shape[3], Wn), z_strings, z_size, lanes=Wn)
+        cdf, ln, off = self.gaussian_conditional.host_tables()
         both = torch.stack((sym, idx)).cpu().numpy()   # the one device -> host copy: [2, B, H*W, M], raster pixels, channels inner
         order = self._ckbd_order(y.shape[2], y.shape[3])
         y_strings = [ans.encode(np.ascontiguousarray(both[0, i][order]).reshape(-1), np.ascontiguousarray(both[1, i][order]).reshape(-1), cdf, ln, off)
@@ -439,8 +564,14 @@ class JointCheckerboardHierarchicalPriors(JointAutoregressiveHierarchicalPriors)
         return self._decode_passes(y_strings, params, (params.shape[2] * params.shape[3] + 1) // 2, self._ckbd_passes)
 
     @torch.no_grad()
-    def decompress(self, strings, shape):
+    def decompress(self, strings, shape, lanes=None, device_coder=True, check=True):
+        """lanes, device_coder, check: as for mbt2018 (JointAutoregressiveHierarchicalPriors.decompress); the device decoder takes the
+        two passes with one clc_ar_lanes_decode each."""
+        Wn = lanes_count(lanes, f"{type(self).__name__}.decompress")
         assert isinstance(strings, (list, tuple)) and len(strings) == 2
+        if Wn is not None:
+            return self._decompress_lanes(strings, shape, Wn, device_coder, check)
+        refuse_lanes_strings(strings[0])
         z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
         y_hat = self._ckbd_decode(strings[0], self._hyper_synthesis(z_hat))
         return {"x_hat": self._synthesis(y_hat).clamp_(0, 1)}

@@ -3053,6 +3053,47 @@ def rans_lanes_regions(segments, W, B):
     return np.stack((firsts, np.tile(caps, B)), axis=1).reshape(B, W, 2).astype(np.int32)
 
 
+def _lanes_encode_args(who, symbols, indexes, segments, W, tables, out, regions, regions_dev, most):
+    """The arguments rans_lanes_encode and rans_lanes_encode_list share, checked -> (B, T, W, segments, table pointers, out, regions,
+    the device's regions, result).  most: the largest number of segments the entry takes (None: any)."""
+    import numpy as np
+
+    W = _lanes_w(W, who)
+    for t, what in ((symbols, "symbols"), (indexes, "indexes")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 2:
+            raise ValueError(f"{who}: {what} must be a contiguous int32 [B, T] device tensor")
+    if symbols.shape != indexes.shape or symbols.shape[0] < 1:
+        raise ValueError(f"{who}: symbols and indexes must have one shape [B >= 1, T] (got {tuple(symbols.shape)}, {tuple(indexes.shape)})")
+    B, T = int(symbols.shape[0]), int(symbols.shape[1])
+    segments = [int(n) for n in segments]
+    if (most is not None and len(segments) > most) or any(n < 0 for n in segments) or sum(segments) > T:
+        count = "segments" if most is None else f"at most {most} segments"
+        raise ValueError(f"{who}: {count} of non-negative length adding up to at most T = {T} (got {segments})")
+    if regions is None:
+        regions = rans_lanes_regions(segments, W, B)
+    regions = np.ascontiguousarray(np.asarray(regions, dtype=np.int32))
+    if regions.shape != (B, W, 2):
+        raise ValueError(f"{who}: regions must be int32 [B, W, 2] = {(B, W, 2)} (got {regions.shape})")
+    if out is None:
+        out = torch.empty((int((regions[..., 0].astype(np.int64) + regions[..., 1]).max()),), device=symbols.device, dtype=torch.int32)
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or not out.is_cuda or not out.is_contiguous() or out.dim() != 1:
+        raise ValueError(f"{who}: out must be a contiguous int32 [m] device tensor")
+    ends = regions[..., 0].astype(np.int64) + regions[..., 1]
+    if (regions < 0).any() or int(ends.max()) > out.numel():
+        raise ValueError(f"{who}: every region must lie inside out ({out.numel()} words; the regions reach word {int(ends.max())}, "
+                         f"their smallest entry is {int(regions.min())})")
+    ptrs = _lanes_tables(tables, who)
+    if regions_dev is None:
+        reg_dev = torch.from_numpy(regions).to(symbols.device)
+    else:
+        reg_dev = regions_dev
+        if (not isinstance(reg_dev, torch.Tensor) or reg_dev.dtype != torch.int32 or not reg_dev.is_cuda or not reg_dev.is_contiguous()
+                or tuple(reg_dev.shape) != (B, W, 2)):
+            raise ValueError(f"{who}: regions_dev must be a contiguous int32 [B, W, 2] = {(B, W, 2)} device tensor")
+    result = torch.empty((B, W, 2), device=symbols.device, dtype=torch.int32)
+    return B, T, W, segments, ptrs, out, regions, reg_dev, result
+
+
 def rans_lanes_encode(symbols, indexes, segments, W, tables, out=None, regions=None, regions_dev=None):
     """clc_rans_lanes_encode: a whole batch's lanes streams in one launch.  symbols / indexes: contiguous int32 device tensors [B, T] in
     stream order; segments: the P <= 32 segment lengths (host ints, sum <= T); tables as for rans_lanes_decode_step.  out: int32 [m] device
@@ -3061,47 +3102,27 @@ def rans_lanes_encode(symbols, indexes, segments, W, tables, out=None, regions=N
     spares the upload — a captured graph passes one.
     -> (out, regions, result): result int32 [B, W, 2] on the device, (first word, word count) of each wave stream or
     (RANS_LANES_ZERO_FREQ / RANS_LANES_OVERFLOW, 0)."""
-    import numpy as np
-
-    W = _lanes_w(W, "rans_lanes_encode")
-    for t, what in ((symbols, "symbols"), (indexes, "indexes")):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 2:
-            raise ValueError(f"rans_lanes_encode: {what} must be a contiguous int32 [B, T] device tensor")
-    if symbols.shape != indexes.shape or symbols.shape[0] < 1:
-        raise ValueError(f"rans_lanes_encode: symbols and indexes must have one shape [B >= 1, T] (got {tuple(symbols.shape)}, {tuple(indexes.shape)})")
-    B, T = int(symbols.shape[0]), int(symbols.shape[1])
-    segments = [int(n) for n in segments]
-    if len(segments) > _lib.RANS_LANES_MAX_SEGMENTS or any(n < 0 for n in segments) or sum(segments) > T:
-        raise ValueError(f"rans_lanes_encode: at most {_lib.RANS_LANES_MAX_SEGMENTS} segments of non-negative length adding up to at most T = {T} "
-                         f"(got {segments})")
-    if regions is None:
-        regions = rans_lanes_regions(segments, W, B)
-    regions = np.ascontiguousarray(np.asarray(regions, dtype=np.int32))
-    if regions.shape != (B, W, 2):
-        raise ValueError(f"rans_lanes_encode: regions must be int32 [B, W, 2] = {(B, W, 2)} (got {regions.shape})")
-    if out is None:
-        out = torch.empty((int((regions[..., 0].astype(np.int64) + regions[..., 1]).max()),), device=symbols.device, dtype=torch.int32)
-    if not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or not out.is_cuda or not out.is_contiguous() or out.dim() != 1:
-        raise ValueError("rans_lanes_encode: out must be a contiguous int32 [m] device tensor")
-    ends = regions[..., 0].astype(np.int64) + regions[..., 1]
-    if (regions < 0).any() or int(ends.max()) > out.numel():
-        raise ValueError(f"rans_lanes_encode: every region must lie inside out ({out.numel()} words; the regions reach word {int(ends.max())}, "
-                         f"their smallest entry is {int(regions.min())})")
-    cp, stride, rows, lp, op = _lanes_tables(tables, "rans_lanes_encode")
+    B, T, W, segments, (cp, stride, rows, lp, op), out, regions, reg_dev, result = _lanes_encode_args(
+        "rans_lanes_encode", symbols, indexes, segments, W, tables, out, regions, regions_dev, _lib.RANS_LANES_MAX_SEGMENTS)
     segs = _lib.LanesSegments()
     segs.P = len(segments)
     for i, n in enumerate(segments):
         segs.n[i] = n
-    if regions_dev is None:
-        reg_dev = torch.from_numpy(regions).to(symbols.device)
-    else:
-        reg_dev = regions_dev
-        if (not isinstance(reg_dev, torch.Tensor) or reg_dev.dtype != torch.int32 or not reg_dev.is_cuda or not reg_dev.is_contiguous()
-                or tuple(reg_dev.shape) != (B, W, 2)):
-            raise ValueError(f"rans_lanes_encode: regions_dev must be a contiguous int32 [B, W, 2] = {(B, W, 2)} device tensor")
-    result = torch.empty((B, W, 2), device=symbols.device, dtype=torch.int32)
     _lib.check(_L().clc_rans_lanes_encode(symbols.data_ptr(), indexes.data_ptr(), T, B, segs, W, cp, stride, rows, lp, op, out.data_ptr(),
                                           reg_dev.data_ptr(), result.data_ptr(), _stream()), "clc_rans_lanes_encode")
+    return out, regions, result
+
+
+def rans_lanes_encode_list(symbols, indexes, segments, W, tables, out=None, regions=None):
+    """clc_rans_lanes_encode_list: rans_lanes_encode for ANY number of segments (mbt2018's wavefront steps: 61 at a 16 x 16 latent, 141
+    at 32 x 48).  The lengths are checked here, on the host (non-negative, sum <= T < 2^27), and uploaded once; the kernel reads them
+    from device memory.  Everything else, the return value included, is rans_lanes_encode's."""
+    B, T, W, segments, (cp, stride, rows, lp, op), out, regions, reg_dev, result = _lanes_encode_args(
+        "rans_lanes_encode_list", symbols, indexes, segments, W, tables, out, regions, None, None)
+    seg_dev = torch.tensor(segments, dtype=torch.int32).to(symbols.device) if segments else None
+    _lib.check(_L().clc_rans_lanes_encode_list(symbols.data_ptr(), indexes.data_ptr(), T, B, seg_dev.data_ptr() if segments else None,
+                                               len(segments), W, cp, stride, rows, lp, op, out.data_ptr(), reg_dev.data_ptr(),
+                                               result.data_ptr(), _stream()), "clc_rans_lanes_encode_list")
     return out, regions, result
 
 
@@ -3180,3 +3201,40 @@ def rans_lanes_pack(out, result, capacity=None, packed=None, header=None):
     _lib.check(_L().clc_rans_lanes_pack(out.data_ptr(), out.numel(), result.data_ptr(), B, W, packed.data_ptr(), capacity, header.data_ptr(),
                                         _stream()), "clc_rans_lanes_pack")
     return packed, header
+
+
+def ar_lanes_decode(gp, M, pix, B, H, W, scale_table, tables, words, spans, state, y_hat, symbols=None):
+    """clc_ar_lanes_decode: one step of a context model's schedule decoded from the lanes stream for the whole batch — what
+    ar_finish_decode, rans_lanes_decode_step and ar_commit do, in one launch.  gp: ar_linear's dense [>= B P, >= 2 M] rows (scales |
+    means) of the step; pix: its pixel list; scale_table, tables, words, spans, state as for rans_lanes_decode_gauss; y_hat: the
+    [B, M, H, W] pixel-major latent, written at the listed pixels (a pair outside the map is decoded and not written); symbols: an
+    optional contiguous int32 device tensor of B equal blocks of at least P M elements that receives the decoded symbols.  No copy
+    to the host, no sync."""
+    who = "ar_lanes_decode"
+    pp, P = _ar_pix(pix)
+    gpp, ldg = _ar_dense(gp, B * P, f"{who} gp")
+    hp, Bh, Hh, Wh, Ch, ldh = _ar_map(y_hat, who)
+    if gp.shape[1] < 2 * M or (Bh, Hh, Wh, Ch) != (B, H, W, M):
+        raise ValueError(f"{who}: gp needs 2 M = {2 * M} columns and y_hat must be a [B, M, H, W] = {(B, M, H, W)} map "
+                         f"(got {tuple(gp.shape)}, {tuple(y_hat.shape)})")
+    if (not isinstance(scale_table, torch.Tensor) or scale_table.dtype != torch.float32 or not scale_table.is_cuda
+            or not scale_table.is_contiguous() or not 2 <= scale_table.numel() <= 256):
+        raise ValueError(f"{who}: scale_table must be a contiguous float32 device tensor of 2 .. 256 entries")
+    Bs, Wn = _coder_streams(words, spans, state, who, "W", RANS_LANES_STATE_WORDS)
+    _lanes_w(Wn, who)
+    if Bs != B:
+        raise ValueError(f"{who}: spans must be int32 [B = {B}, W, 2] (got {tuple(spans.shape)})")
+    cp, stride, rows, lp, op = _lanes_tables(tables, who)
+    n = P * M
+    if n >= 1 << 30:
+        raise ValueError(f"{who}: {n} symbols per image in one step; n must be below 2^30")
+    symp, lds = None, 0
+    if symbols is not None:
+        if (not isinstance(symbols, torch.Tensor) or symbols.dtype != torch.int32 or not symbols.is_cuda or not symbols.is_contiguous()
+                or symbols.numel() % B or symbols.numel() // B < n):
+            raise ValueError(f"{who}: symbols must be a contiguous int32 device tensor of B = {B} equal image blocks of at least n = {n} elements")
+        symp, lds = symbols.data_ptr(), symbols.numel() // B
+    _lib.check(_L().clc_ar_lanes_decode(gpp, ldg, M, pp, P, B, H, W, scale_table.data_ptr(), scale_table.numel(), cp, stride, rows, lp, op,
+                                        words.data_ptr(), spans.data_ptr(), state.data_ptr(), Wn, hp, ldh, symp, lds, _stream()),
+               "clc_ar_lanes_decode")
+    return y_hat

@@ -938,8 +938,28 @@ int clc_gmm_decode_step(const float* gp, int ldg, int N, int K, const int32_t* p
  *                    count, or its negative code as it is (a code copies nothing and counts as 0), header[B W] = the total.  Each wave
  *                    forms its own prefix over the counts, so no wave depends on another's output.  No word is stored at or past
  *                    `capacity` and none is read at or past n_words: a total beyond the capacity is reported and the copy stops there.
+ *
+ * THE LANES STREAM OF mbt2018 AND mbt2018-checkerboard (model.compress(..., lanes=W); clc_amd/models/hyperprior.py): the same container,
+ * cut by the DEPENDENT STEPS of the context model instead of by raster pixels.  mbt2018: the segments are the non-empty steps of the
+ * wavefront schedule in ascending t = w + 3 h (W + 3 (H - 1) steps at most, against H W raster pixels); inside a segment the step's
+ * pixels in ascending h, channels inner, n = pixels of the step x M.  mbt2018-checkerboard: two segments, the anchors ((h + w) odd) and
+ * then the non-anchors, each in raster order with channels inner: the symbol order of its default stream.  z stays the default stream.
+ * clc_ar_lanes_decode  ONE step of such a schedule for the whole batch, what clc_ar_finish(CLC_AR_DECODE), clc_rans_lanes_decode_step
+ *                    and clc_ar_commit do in three launches: clc_rans_lanes_decode_gauss with scale = gp, mu = gp + M, C = M, and a
+ *                    scatter through the step's pixel list in place of the dense row.  gp: dense [B P][ldg], ldg >= 2 M, scales in
+ *                    [0, M) and means in [M, 2 M) (clc_ar_linear's output); pix: the step's P (h, w) pairs, device memory.  Symbol
+ *                    j < n = P M of image b is row b P + j / M, channel j % M; its index is clc_quantize_build_indexes's, bit for bit;
+ *                    it writes y_hat[((b H + h) W + w) ldh + c] = (float)symbol + mean with (h, w) = pix[j / M] (clc_ar_commit's
+ *                    expression; y_hat NHWC, ldh >= M) and, when symbols is not null, symbols[b ld_sym + j].  A pair outside the map
+ *                    is decoded — it occupies its place in the stream — and not written.  Scale table, words, spans, state, the
+ *                    clamps, the bounds of every loop and what is never read are clc_rans_lanes_decode_gauss's.  n < 2^30; n == 0
+ *                    launches nothing.  A wave with no round in the step (w >= ceil(n / 64)) leaves its state as it was.
+ * clc_rans_lanes_encode_list  clc_rans_lanes_encode with the P segment lengths read from DEVICE memory, seg_len[P], any P >= 0 (a 16 x 16
+ *                    latent of mbt2018 has 61 segments, a 32 x 48 one 141).  Regions, result codes and words are clc_rans_lanes_encode's.
+ *                    The lengths cannot be checked before the launch: a negative one counts as 0, and THE CALLER keeps their sum
+ *                    within ld (no symbol at or past ld may be named); ld < 2^27.
  * All kernels: stream-ordered, graph-capturable, allocation- and sync-free; no atomics, no wave waits on another; no LDS and no barrier
- * but for the scale table of clc_rans_lanes_decode_gauss.  Bad arguments are refused by name before any launch. */
+ * but for the scale table of clc_rans_lanes_decode_gauss / clc_ar_lanes_decode.  Bad arguments are refused by name before any launch. */
 #define CLC_RANS_LANES_MAX_W 16
 #define CLC_RANS_LANES_MAX_SEGMENTS 32
 #define CLC_RANS_LANES_ZERO_FREQ (-1)
@@ -969,6 +989,14 @@ int clc_rans_lanes_decode_gauss(const float* scale, long ldsc, const float* mu, 
                                 long ld_sym, clc_stream_t stream);
 int clc_rans_lanes_pack(const uint32_t* words, long n_words, const int32_t* result /* [B][W][2] */, int B, int W, uint32_t* packed,
                         long capacity, int32_t* header /* [B W + 1] */, clc_stream_t stream);
+int clc_ar_lanes_decode(const float* gp, long ldg, int M, const int32_t* pix /* [P][2] */, int P, int B, int H, int W_map,
+                        const float* scale_table, int n_scales, const int32_t* cdfs, int cdf_stride, int n_rows, const int32_t* cdf_sizes,
+                        const int32_t* offsets, const uint32_t* words, const int32_t* spans /* [B][W][2] */,
+                        clc_rans_lanes_state* state /* [B][W] */, int W, float* y_hat, long ldh, int32_t* symbols /* or NULL */,
+                        long ld_sym, clc_stream_t stream);
+int clc_rans_lanes_encode_list(const int32_t* symbols, const int32_t* indexes, long ld, int B, const int32_t* seg_len /* [P], DEVICE */, int P,
+                               int W, const int32_t* cdfs, int cdf_stride, int n_rows, const int32_t* cdf_sizes, const int32_t* offsets,
+                               uint32_t* out, const int32_t* regions /* [B][W][2] */, int32_t* result /* [B][W][2] */, clc_stream_t stream);
 
 #ifdef __cplusplus
 }
