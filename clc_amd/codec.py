@@ -18,6 +18,10 @@ file.  Same bitstreams, re-staged for the MI355X:
               device->host copies, the header with the z symbols and the packed words); decompress is ONE pinned upload and ONE
               replay of ONE graph with the coder inside every slice step (clc_rans_lanes_decode_gauss): no copy back, no
               synchronize; check=True adds one download of the coder's end states after the replay is issued.
+  context     ContextCodecEngine: the same service for mbt2018 and mbt2018-checkerboard (models/hyperprior.py) on the lanes stream — ONE
+  models      graph per compress (transforms, the encoder's whole schedule, the lanes encoder and pack) and ONE per decompress (h_s,
+              every step's chain and clc_ar_lanes_decode, g_s); DESIGN 28.  The plan tables, their LRU, the capture and the lanes
+              stream's host halves are _Engine's, shared by both engines.
   container   `pack` / `unpack` / `write_file` / `read_file`: a self-describing byte layout around {"strings", "shape"}
               (the reference only counts len(strings[k][0]), eval_CLC.py:337).
 
@@ -181,8 +185,24 @@ class _Plan:
     pass
 
 
-class CodecEngine:
-    """engine = CodecEngine(model); outs = engine.compress(x[B], refs); xs = engine.decompress(outs, refs)."""
+def check_items(items, lanes):
+    """What decompress refuses about its items before any device work: a "lanes" entry other than the call's, and another kernel state's
+    container header (`meta`, from unpack_item) or `kernel_config` entry (from compress)."""
+    for k, it in enumerate(items):
+        if it.get("lanes") is not None and it["lanes"] != lanes:
+            raise ValueError(f"decompress: item {k} was coded with lanes = {it['lanes']}, the call says lanes = {lanes}")
+    if lanes is None:
+        coding.refuse_lanes_strings([it["strings"][0][0] for it in items])
+    for k, it in enumerate(items):      # items that came out of a container carry its header: refuse another kernel generation's
+        if it.get("meta") is not None:
+            check_kernel_config(it["meta"], f"item {k}")
+        elif it.get("kernel_config") is not None and tuple(it["kernel_config"]) != kernel_config():
+            raise KernelConfigMismatch(f"item {k} was encoded under kernel state {tuple(it['kernel_config'])}, this process now decodes under {kernel_config()}")
+
+
+class _Engine:
+    """What CodecEngine and ContextCodecEngine share: the coder threads, the plan tables and their LRU, the capture of a plan's function,
+    the life cycle, and the two host halves of the lanes stream (the encoder's downloads, the decoder's upload and replay)."""
 
     def __init__(self, model, threads: int = 8, use_graph: bool = True, max_plans: int = 0):
         """max_plans > 0: keep at most that many captured signatures per direction (least recently used out first) — a data set of many
@@ -194,6 +214,7 @@ class CodecEngine:
         self._enc = {}
         self._dec = {}
         self.max_plans = int(max_plans)
+        self._built_ms = 0.0   # building time of the plans the current call made (_plan)
         self.last = {}   # wall-clock split of the last compress() / decompress() call (ms): device segments incl. the hops' copies and waits | host rANS
         self.zc = int(model.entropy_bottleneck.channels)   # hyper-latent channels (192 in the reference configuration)
         model.update()   # CDF tables (no-op when present)
@@ -225,14 +246,11 @@ class CodecEngine:
         if pl is None:
             while self.max_plans > 0 and len(table) >= self.max_plans:
                 table.pop(next(iter(table)))   # least recently used: its graphs, pool and pinned buffers go with it (outside any capture)
+            t0 = time.perf_counter()
             pl = build()
+            self._built_ms += (time.perf_counter() - t0) * 1e3   # (warm-up passes and captures of the plans a call built)
         table[sig] = pl
         return pl
-
-    def _sig(self, x, refs):
-        # (the kernel state is part of the signature: a captured graph keeps the kernels it was captured with, so a changed tuning /
-        #  precision state must not replay the old plan — and the result's `kernel_config` must be the one that encoded)
-        return (tuple(x.shape), None if refs is None else tuple(tuple(r.shape) for r in refs), kernel_config())
 
     def _capture(self, fn):
         """run fn() twice eagerly on a side stream (allocator / lazy kernel attributes), then capture it; -> (graph, outputs)."""
@@ -250,6 +268,116 @@ class CodecEngine:
             out = fn()
         g.replay()   # capture does not execute: leave valid values behind for the next segment's warm-up passes
         return g, out
+
+    def _last_extras(self, last, pl):
+        """what an engine adds to `last` about the plan a call ran"""
+        return last
+
+    # ---------------------------------------------------------------- the lanes stream's host halves
+    def _lanes_encoder_host(self, pl):
+        """a lanes encoder plan's host side: the pinned header twin and the z indexes (pl.packed = (small, packed words), pl.zshape)"""
+        pl.small_host = torch.empty(pl.packed[0].shape, dtype=torch.int32).pin_memory()
+        pl.words_host = None   # pinned, grown to the largest total seen
+        C = self.zc
+        pl.zidx = np.ascontiguousarray(np.broadcast_to(np.arange(C, dtype=np.int32).reshape(C, 1, 1), (C,) + pl.zshape)).reshape(-1)
+        return pl
+
+    def _finish_lanes_encoder(self, pl, t0):
+        """the host half of compress(lanes=W): the header copy (counts, total, z symbols), the copy of `total` words, the containers"""
+        small, packed = pl.packed
+        B, W = pl.x.shape[0], pl.lanes
+        stream = torch.cuda.current_stream()
+        pl.small_host.copy_(small, non_blocking=True)
+        stream.synchronize()
+        head = pl.small_host.numpy()
+        total = int(head[B * W])
+        if total > packed.numel():
+            raise ValueError(f"compress: the wave streams hold {total} words, the packed buffer {packed.numel()}")
+        if pl.words_host is None or pl.words_host.numel() < total:
+            pl.words_host = torch.empty((max(total, 1) * 5 // 4 + 1024,), dtype=torch.int32).pin_memory()
+        if (head[:B * W] >= 0).all():
+            pl.words_host[:total].copy_(packed[:total], non_blocking=True)
+            stream.synchronize()
+        t1 = time.perf_counter()
+        ys = coding.lanes_strings(head, pl.words_host.numpy()[:total], B, W)   # (raises by name on a negative code)
+        ecdf, eln, eoff = self.model.entropy_bottleneck.host_tables()
+        zsym = head[B * W + 1:].reshape(B, -1)
+        enc_z = lambda b: ans.encode(zsym[b], pl.zidx, ecdf, eln, eoff)
+        zs = list(self.pool.map(enc_z, range(B))) if B > 1 else [enc_z(0)]
+        self.last = self._last_extras({"op": "compress", "device_ms": (t1 - t0) * 1e3, "rans_ms": (time.perf_counter() - t1) * 1e3, "hops": 2,
+                                       "lanes": W}, pl)
+        return [{"strings": [[y], [z]], "shape": torch.Size(pl.zshape), "kernel_config": pl.kernel_config, "lanes": W} for y, z in zip(ys, zs)]
+
+    def _lanes_decoder_buffers(self, pl, B, zshape, dev, W, cap_words):
+        """a lanes decoder plan's inputs at fixed device addresses, with their pinned twins: the z symbols and the upload image
+        [states | spans | cap_words words] (coding.stream_image), whose views the plan's graph reads"""
+        pl.lanes, pl.cap_words = W, int(cap_words)
+        pl.z_in = torch.zeros((B, self.zc) + tuple(zshape), dtype=torch.int32, device=dev)
+        pl.z_host = torch.empty(pl.z_in.shape, dtype=torch.int32).pin_memory()
+        n_state = 2 * ans.LANES
+        size = (n_state + 4) * B * W + pl.cap_words
+        pl.image = torch.zeros((size,), dtype=torch.int32, device=dev)   # (all zero: empty spans, which read nothing)
+        pl.image_host = torch.zeros((size,), dtype=torch.int32).pin_memory()
+        pl.state, pl.spans, pl.words = coding.stream_views(pl.image, B, W, n_state)
+
+    lanes_words_slack = 1.5   # a lanes decoder plan's words buffer holds this multiple of what the batch that built it needed
+
+    def _decompress_lanes(self, items, pl_for, W, check):
+        """decompress(lanes=W) behind the argument checks; pl_for(cap_words, rebuild) -> the plan"""
+        m = self.model
+        B = len(items)
+        tm = time.perf_counter()
+        subs = coding.lanes_parse([it["strings"][0][0] for it in items], W)   # the headers, before any device work
+        image = coding.stream_image(subs, 2 * ans.LANES)
+        head = (2 * ans.LANES + 4) * B * W
+        need = image.size - head
+        pl = pl_for(max(need, int(need * self.lanes_words_slack)), False)
+        rebuilt = False
+        if getattr(pl, "uploaded", None) is not None:
+            pl.uploaded.synchronize()   # the previous call's uploads (not its graph) may still be reading the pinned pages written below
+        if need > pl.cap_words:   # never truncated: a larger buffer, a new graph
+            pl = pl_for(max(need, int(need * self.lanes_words_slack)), True)
+            rebuilt = True
+        ecdf, eln, eoff = m.entropy_bottleneck.host_tables()
+        C = self.zc
+        zshape = tuple(pl.z_in.shape[2:])
+        zidx = np.ascontiguousarray(np.broadcast_to(np.arange(C, dtype=np.int32).reshape(C, 1, 1), (C,) + zshape)).reshape(-1)
+        zh = pl.z_host.numpy()
+
+        def dec_z(b):
+            zh[b] = ans.decode(items[b]["strings"][1][0], zidx, ecdf, eln, eoff).reshape(zh.shape[1:])
+
+        if B > 1:
+            list(self.pool.map(dec_z, range(B)))
+        else:
+            dec_z(0)
+        t_rans = time.perf_counter() - tm
+        tm = time.perf_counter()
+        pl.image_host.numpy()[:image.size] = image
+        pl.z_in.copy_(pl.z_host, non_blocking=True)
+        pl.image[:image.size].copy_(pl.image_host[:image.size], non_blocking=True)   # THE upload: states, spans, words
+        if getattr(pl, "uploaded", None) is None:
+            pl.uploaded = torch.cuda.Event()
+        pl.uploaded.record()
+        if pl.graph is not None:
+            pl.graph.replay()
+            res = pl.out.clone()
+        else:
+            res = pl.run()
+        self.last = self._last_extras({"op": "decompress", "device_ms": 0.0, "rans_ms": t_rans * 1e3, "hops": 1 if check else 0, "lanes": W,
+                                       "tail_issue_ms": (time.perf_counter() - tm) * 1e3, "plan_rebuilt": rebuilt}, pl)
+        if check:   # ONE download, after everything has been issued
+            coding.lanes_check(pl.state, subs)
+        return res
+
+
+class CodecEngine(_Engine):
+    """engine = CodecEngine(model); outs = engine.compress(x[B], refs); xs = engine.decompress(outs, refs)."""
+
+    def _sig(self, x, refs):
+        # (the kernel state is part of the signature: a captured graph keeps the kernels it was captured with, so a changed tuning /
+        #  precision state must not replay the old plan — and the result's `kernel_config` must be the one that encoded)
+        return (tuple(x.shape), None if refs is None else tuple(tuple(r.shape) for r in refs), kernel_config())
 
     # ---------------------------------------------------------------- encoder
     def _bank_slots(self, pl, arena, slots):
@@ -314,12 +442,8 @@ class CodecEngine:
         pl.graph, (pl.packed, pl.zshape) = self._capture(run)
         pl.run = run
         if lanes is not None:
-            pl.small_host = torch.empty(pl.packed[0].shape, dtype=torch.int32).pin_memory()
-            pl.words_host = None   # pinned, grown to the largest total seen
-            C = self.zc
-            pl.zidx = np.ascontiguousarray(np.broadcast_to(np.arange(C, dtype=np.int32).reshape(C, 1, 1), (C,) + pl.zshape)).reshape(-1)
-            return pl
-        pl.host = torch.empty(pl.packed.shape, dtype=torch.int32).pin_memory()
+            return self._lanes_encoder_host(pl)
+        pl.host =torch.empty(pl.packed.shape, dtype=torch.int32).pin_memory()
         pl.ny = (pl.packed.shape[1] - self.zc * pl.zshape[0] * pl.zshape[1]) // 2
         C = self.zc
         pl.zidx = np.ascontiguousarray(np.broadcast_to(np.arange(C, dtype=np.int32).reshape(C, 1, 1), (C,) + pl.zshape)).reshape(-1)
@@ -418,31 +542,6 @@ class CodecEngine:
         # (a replayed graph holds the kernels of the state it was CAPTURED under: plans are keyed by it, see _sig)
         return [{"strings": [[ys], [zs]], "shape": torch.Size(pl.zshape), "kernel_config": pl.kernel_config} for ys, zs in streams]
 
-    def _finish_lanes_encoder(self, pl, t0):
-        """the host half of compress(lanes=W): the header copy (counts, total, z symbols), the copy of `total` words, the containers"""
-        small, packed = pl.packed
-        B, W = pl.x.shape[0], pl.lanes
-        stream = torch.cuda.current_stream()
-        pl.small_host.copy_(small, non_blocking=True)
-        stream.synchronize()
-        head = pl.small_host.numpy()
-        total = int(head[B * W])
-        if total > packed.numel():
-            raise ValueError(f"compress: the wave streams hold {total} words, the packed buffer {packed.numel()}")
-        if pl.words_host is None or pl.words_host.numel() < total:
-            pl.words_host = torch.empty((max(total, 1) * 5 // 4 + 1024,), dtype=torch.int32).pin_memory()
-        if (head[:B * W] >= 0).all():
-            pl.words_host[:total].copy_(packed[:total], non_blocking=True)
-            stream.synchronize()
-        t1 = time.perf_counter()
-        ys = coding.lanes_strings(head, pl.words_host.numpy()[:total], B, W)   # (raises by name on a negative code)
-        ecdf, eln, eoff = self.model.entropy_bottleneck.host_tables()
-        zsym = head[B * W + 1:].reshape(B, -1)
-        enc_z = lambda b: ans.encode(zsym[b], pl.zidx, ecdf, eln, eoff)
-        zs = list(self.pool.map(enc_z, range(B))) if B > 1 else [enc_z(0)]
-        self.last = {"op": "compress", "device_ms": (t1 - t0) * 1e3, "rans_ms": (time.perf_counter() - t1) * 1e3, "hops": 2, "lanes": W}
-        return [{"strings": [[y], [z]], "shape": torch.Size(pl.zshape), "kernel_config": pl.kernel_config, "lanes": W} for y, z in zip(ys, zs)]
-
     # ---------------------------------------------------------------- decoder
     def _build_decoder_lanes(self, B, zshape, refs, dev, W, cap_words, bank=None):
         """The lanes decoder: ONE graph — hyper-synthesis, per slice the parameter nets, clc_rans_lanes_decode_gauss and the refinement,
@@ -450,17 +549,10 @@ class CodecEngine:
         m = self.model
         S = m.num_slices
         pl = _Plan()
-        pl.lanes, pl.cap_words = W, int(cap_words)
         pl.refs = [r.clone() for r in refs] if refs is not None else None
         if bank is not None:
             self._bank_slots(pl, *bank)
-        pl.z_in = torch.zeros((B, self.zc) + tuple(zshape), dtype=torch.int32, device=dev)
-        pl.z_host = torch.empty(pl.z_in.shape, dtype=torch.int32).pin_memory()
-        n_state = 2 * ans.LANES
-        size = (n_state + 4) * B * W + pl.cap_words
-        pl.image = torch.zeros((size,), dtype=torch.int32, device=dev)   # (all zero: empty spans, which read nothing)
-        pl.image_host = torch.zeros((size,), dtype=torch.int32).pin_memory()
-        pl.state, pl.spans, pl.words = coding.stream_views(pl.image, B, W, n_state)
+        self._lanes_decoder_buffers(pl, B, zshape, dev, W, cap_words)
         y_shape = [zshape[0] * 4, zshape[1] * 4]
         gc = m.gaussian_conditional
         tables = (gc._quantized_cdf, gc._cdf_length, gc._offset)
@@ -482,56 +574,6 @@ class CodecEngine:
         pl.graph, pl.out = self._capture(run)
         pl.run = run
         return pl
-
-    lanes_words_slack = 1.5   # a lanes decoder plan's words buffer holds this multiple of what the batch that built it needed
-
-    def _decompress_lanes(self, items, pl_for, W, check):
-        """decompress(lanes=W) behind the argument checks; pl_for(cap_words, rebuild) -> the plan"""
-        m = self.model
-        B = len(items)
-        tm = time.perf_counter()
-        subs = coding.lanes_parse([it["strings"][0][0] for it in items], W)   # the headers, before any device work
-        image = coding.stream_image(subs, 2 * ans.LANES)
-        head = (2 * ans.LANES + 4) * B * W
-        need = image.size - head
-        pl = pl_for(max(need, int(need * self.lanes_words_slack)), False)
-        rebuilt = False
-        if getattr(pl, "uploaded", None) is not None:
-            pl.uploaded.synchronize()   # the previous call's uploads (not its graph) may still be reading the pinned pages written below
-        if need > pl.cap_words:   # never truncated: a larger buffer, a new graph
-            pl = pl_for(max(need, int(need * self.lanes_words_slack)), True)
-            rebuilt = True
-        ecdf, eln, eoff = m.entropy_bottleneck.host_tables()
-        C = self.zc
-        zshape = tuple(pl.z_in.shape[2:])
-        zidx = np.ascontiguousarray(np.broadcast_to(np.arange(C, dtype=np.int32).reshape(C, 1, 1), (C,) + zshape)).reshape(-1)
-        zh = pl.z_host.numpy()
-
-        def dec_z(b):
-            zh[b] = ans.decode(items[b]["strings"][1][0], zidx, ecdf, eln, eoff).reshape(zh.shape[1:])
-
-        if B > 1:
-            list(self.pool.map(dec_z, range(B)))
-        else:
-            dec_z(0)
-        t_rans = time.perf_counter() - tm
-        tm = time.perf_counter()
-        pl.image_host.numpy()[:image.size] = image
-        pl.z_in.copy_(pl.z_host, non_blocking=True)
-        pl.image[:image.size].copy_(pl.image_host[:image.size], non_blocking=True)   # THE upload: states, spans, words
-        if getattr(pl, "uploaded", None) is None:
-            pl.uploaded = torch.cuda.Event()
-        pl.uploaded.record()
-        if pl.graph is not None:
-            pl.graph.replay()
-            res = pl.out.clone()
-        else:
-            res = pl.run()
-        self.last = {"op": "decompress", "device_ms": 0.0, "rans_ms": t_rans * 1e3, "hops": 1 if check else 0, "lanes": W,
-                     "tail_issue_ms": (time.perf_counter() - tm) * 1e3, "plan_rebuilt": rebuilt}
-        if check:   # ONE download, after everything has been issued
-            coding.lanes_check(pl.state, subs)
-        return res
 
     def _build_decoder(self, B, zshape, refs, dev, bank=None):
         m = self.model
@@ -628,16 +670,7 @@ class CodecEngine:
         string without lanes=, a default string with it."""
         m = self.model
         Wn = coding.lanes_count(lanes, "CodecEngine.decompress")
-        for k, it in enumerate(items):
-            if it.get("lanes") is not None and it["lanes"] != Wn:
-                raise ValueError(f"decompress: item {k} was coded with lanes = {it['lanes']}, the call says lanes = {Wn}")
-        if Wn is None:
-            coding.refuse_lanes_strings([it["strings"][0][0] for it in items])
-        for k, it in enumerate(items):      # items that came out of a container carry its header: refuse another kernel generation's
-            if it.get("meta") is not None:
-                check_kernel_config(it["meta"], f"item {k}")
-            elif it.get("kernel_config") is not None and tuple(it["kernel_config"]) != kernel_config():
-                raise KernelConfigMismatch(f"item {k} was encoded under kernel state {tuple(it['kernel_config'])}, this process now decodes under {kernel_config()}")
+        check_items(items, Wn)
         B = len(items)
         zshape = tuple(int(v) for v in items[0]["shape"])
         dev = next(m.parameters()).device
@@ -725,3 +758,160 @@ class CodecEngine:
         finally:
             for d in decoders:
                 d.close()
+
+
+class ContextCodecEngine(_Engine):
+    """CodecEngine's service for the two context models of models/hyperprior.py on THE LANES STREAM:
+
+        eng = ContextCodecEngine(model, lanes=4); items = eng.compress(x[B]); x_hat = eng.decompress(items, check=True)
+
+    model: a JointAutoregressiveHierarchicalPriors (``mbt2018``) or a JointCheckerboardHierarchicalPriors; every other class is refused by
+    name.  An item is CodecEngine.compress(lanes=W)'s, its strings byte for byte model.compress(x, lanes=W)'s, and decompress returns
+    model.decompress(strings, shape, lanes=W)["x_hat"] bit for bit: the plans run the model's own pass code (_lanes_encode,
+    _lanes_pack_scheduled, _lanes_decode_pass) on a models.hyperprior.PassSchedule they keep.
+
+      compress    ONE graph per (x.shape, W, kernel state): g_a, h_a, z_hat = round(z - median) + median on the device (identical to
+                  decoding the z stream that the host writes afterwards, so nothing waits for the host coder), h_s, the encoder's whole
+                  schedule, the gather into stream order, the lanes encoder and clc_rans_lanes_pack.  Then two device->host copies
+                  (header with the z symbols; the packed words, cut to the header's total) and z on the host threads.
+      decompress  headers parsed and z decoded on the host; ONE pinned upload (z symbols; states | spans | words) into plan-owned buffers
+                  and ONE replay of ONE graph: z_hat, h_s, per step of the schedule the chain and one clc_ar_lanes_decode, g_s, clamp.
+                  No copy back; check=True adds the one download of the coder's end states after the replay is issued.
+
+    MODEL STATE.  A graph holds the addresses of the parameters and entropy-model buffers it was captured over.  Every call compares the
+    model's CURRENT tensors — object, data_ptr() and _version of each parameter and buffer, read from the modules anew — with those of
+    the previous call and drops every plan when one differs (an in-place change, update(force=True), load_state_dict, .to()): the next
+    call rebuilds.  The previous call's tensor objects are held until then, so an identity can never be that of a freed tensor's
+    successor, and a dropped plan's graph is never replayed.
+    `last`: op, graphs (replays of the call: 1, or 0 without use_graph), hops, rans_ms, device_ms, plan_rebuilt, capture_ms (building
+    time of the plans this call made, 0.0 when it made none)."""
+
+    def __init__(self, model, lanes=4, threads: int = 8, use_graph: bool = True, max_plans: int = 0):
+        from .models.hyperprior import JointAutoregressiveHierarchicalPriors, JointCheckerboardHierarchicalPriors
+
+        served = (JointAutoregressiveHierarchicalPriors, JointCheckerboardHierarchicalPriors)
+        if type(model) not in served:
+            name = type(model).__name__
+            why = ""
+            if name.startswith("Cheng2020"):
+                why = ": its compress takes no lanes="
+            elif name == "Elic2022":
+                why = ": its lanes encoder downloads inside the pass"
+            elif hasattr(model, "gaussian_conditional") and not hasattr(model, "context_prediction"):
+                why = ": it has no context model to schedule"
+            raise ValueError(f"ContextCodecEngine: {name} is not served{why} (it takes {served[0].__name__} and {served[1].__name__})")
+        if lanes is None:
+            raise ValueError("ContextCodecEngine: lanes=None (the one-stream format) is not served; pass lanes = 1 .. 16")
+        self.lanes = coding.lanes_count(lanes, "ContextCodecEngine")
+        super().__init__(model, threads, use_graph, max_plans)
+        self._state = None
+
+    # ---------------------------------------------------------------- model state
+    def _model_state(self):
+        return [(t, t.data_ptr(), t._version) for mod in self.model.modules() for held in (mod._parameters, mod._buffers)
+                for t in held.values() if t is not None]
+
+    def _begin(self):
+        """the start of a public call: plans captured over another model state go"""
+        self._built_ms = 0.0
+        now, was = self._model_state(), self._state
+        self._dropped = False
+        if was is None or len(was) != len(now) or any(a[0] is not b[0] or a[1:] != b[1:] for a, b in zip(was, now)):
+            self._dropped = bool(self._enc or self._dec)
+            if self._dropped:
+                torch.cuda.synchronize()   # (a replay of the last call may still run: its graph, pool and buffers go below)
+            self._enc.clear()
+            self._dec.clear()
+        self._state = now
+
+    def _last_extras(self, last, pl):
+        """graphs, capture_ms; plan_rebuilt: a plan was replaced — its words buffer was too small, or the model's state had moved"""
+        last.update(graphs=0 if pl.graph is None else 1, capture_ms=self._built_ms, plan_rebuilt=last.get("plan_rebuilt", False) or self._dropped)
+        return last
+
+    # ---------------------------------------------------------------- encoder
+    def _build_encoder(self, x):
+        m, W = self.model, self.lanes
+        pl = _Plan()
+        pl.lanes, pl.kernel_config = W, kernel_config()
+        pl.x = x.clone()
+        B, dev = x.shape[0], x.device
+        pl.sched = m._lanes_schedule(B, x.shape[2] // 16, x.shape[3] // 16, dev)
+        pl.regions = ops.rans_lanes_regions(pl.sched.segments, W, B)
+        pl.regions_dev = torch.from_numpy(pl.regions).to(dev)
+
+        @torch.no_grad()
+        def run():
+            y = m._analysis(m._prep(pl.x))
+            z = m._hyper_analysis(y)
+            med = m.entropy_bottleneck._get_medians().reshape(1, -1, 1, 1)
+            z_sym = torch.round(z - med).to(torch.int32)                    # == EntropyBottleneck.compress's symbols
+            z_hat = (z_sym.float() + med).contiguous(memory_format=CL)      # == decompress(compress(z)), as _code_inputs takes it
+            sym, idx, _ = m._lanes_encode(y, m._hyper_synthesis(z_hat), pl.sched)
+            zs = z_sym.contiguous().reshape(-1)
+            small = torch.empty((B * W + 1 + zs.numel(),), device=dev, dtype=torch.int32)
+            packed, _ = m._lanes_pack_scheduled(sym, idx, pl.sched, W, pl.regions, pl.regions_dev, small[:B * W + 1])
+            small[B * W + 1:].copy_(zs)
+            return (small, packed), tuple(z.shape[-2:])
+
+        pl.graph, (pl.packed, pl.zshape) = self._capture(run)
+        pl.run = run
+        return self._lanes_encoder_host(pl)
+
+    @torch.no_grad()
+    def compress(self, x) -> List[dict]:
+        """x [B, 3, H, W], H and W multiples of 64 -> one {"strings": [[y], [z]], "shape", "kernel_config", "lanes": W} per image"""
+        x = self.model._prep(x)
+        self._begin()
+        pl = self._plan(self._enc, (tuple(x.shape), self.lanes, kernel_config()), lambda: self._build_encoder(x))
+        t0 = time.perf_counter()
+        pl.x.copy_(x, non_blocking=True)
+        if pl.graph is not None:
+            pl.graph.replay()
+        else:
+            pl.packed, _ = pl.run()
+        return self._finish_lanes_encoder(pl, t0)
+
+    # ---------------------------------------------------------------- decoder
+    def _build_decoder(self, B, zshape, dev, cap_words):
+        m = self.model
+        pl = _Plan()
+        self._lanes_decoder_buffers(pl, B, zshape, dev, self.lanes, cap_words)
+        pl.sched = m._lanes_schedule(B, zshape[0] * 4, zshape[1] * 4, dev)
+
+        @torch.no_grad()
+        def run():
+            med = m.entropy_bottleneck._get_medians().reshape(1, -1, 1, 1)
+            z_hat = (pl.z_in.float() + med).contiguous(memory_format=CL)
+            params, y_hat = coding.decoder_start(m._hyper_synthesis(z_hat), B, m.M)
+            return m._synthesis(m._lanes_decode_pass(params, y_hat, (pl.state, pl.spans, pl.words), pl.sched)).clamp_(0, 1)
+
+        pl.graph, pl.out = self._capture(run)
+        pl.run = run
+        return pl
+
+    @torch.no_grad()
+    def decompress(self, items: Sequence[dict], check=True) -> torch.Tensor:
+        """items: compress()'s (or unpack_item()ed containers, whose kernel-config tag is checked here) of B images of one shape -> x_hat
+        [B, 3, H, W] clamped to [0, 1].  check=True downloads the coder's end states once, after the replay is issued, and raises
+        ValueError naming the image and the wave streams that did not end where a whole stream ends.  Refused by name: an empty list,
+        an item whose "lanes" is not the engine's, items of more than one shape, a header of another stream count, a one-stream string."""
+        items = list(items)
+        if not items:
+            raise ValueError("ContextCodecEngine.decompress: no items")
+        W = self.lanes
+        check_items(items, W)
+        shapes = sorted({tuple(int(v) for v in it["shape"]) for it in items})
+        if len(shapes) != 1:
+            raise ValueError(f"ContextCodecEngine.decompress: the items of one call share one shape, got {shapes}")
+        B, zshape = len(items), shapes[0]
+        self._begin()
+        dev = next(self.model.parameters()).device
+        sig = (B, zshape, W, kernel_config())
+
+        def pl_for(cap, rebuild):
+            if rebuild:
+                self._dec.pop(sig, None)
+            return self._plan(self._dec, sig, lambda: self._build_decoder(B, zshape, dev, cap))
+
+        return self._decompress_lanes(items, pl_for, W, check)

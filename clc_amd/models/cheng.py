@@ -31,7 +31,7 @@ host coder.  8 + 12 S bytes more per image (200 at S = 16).  Its decoder runs on
 (clc_gmm_decode_step): the whole wavefront pass is stream-ordered launches with no host hop.  The default stays the one-stream format,
 byte for byte.
 
-TrainEngine, graphed_training, CodecEngine and ReferenceBank do not take these models.  The walk over the wavefront's steps is
+TrainEngine, graphed_training, CodecEngine, ContextCodecEngine and ReferenceBank do not take these models.  The walk over the wavefront's steps is
 ``mbt2018``'s (_ar_walk), for both decoders.  The host side of the coder — the start of a decoder's loop, the hop of a host-decoded step,
 the upload image of the device-decoded split stream, its parser and its end-state check — is coding.py's.
 """

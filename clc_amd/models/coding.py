@@ -7,7 +7,8 @@ owner here:
   decoders) and ``DeviceLanesSymbols`` (the device's lanes decoder, no hop), one interface: ``views``, ``decode``, ``state``.
 * THE START of a decoder's pass loop: ``decoder_start`` (parameters channels-last, the batch refusal, the zeroed y_hat).
 * THE UPLOAD IMAGE of a device-decoded batch, ``[states | spans | words]`` in one pinned int32 buffer: ``stream_image`` (numpy),
-  ``stream_views``, ``upload_streams``; and the end-state rule of a whole stream, ``check_stream_ends`` / ``device_ends``.
+  ``stream_views``, ``upload_streams`` (a buffer per call; an engine plan keeps its own image at a fixed address and hands its
+  ``stream_views`` to the model's pass, codec._Engine._lanes_decoder_buffers); and the end-state rule of a whole stream, ``check_stream_ends`` / ``device_ends``.
 * THE MULTI-STREAM STRINGS of a batch, for either container of ans.py: ``stream_parse`` and ``stream_check``; for the lanes stream
   (elic2022, CLC, TCM; model and CodecEngine) also ``lanes_count``, ``lanes_parse``, ``refuse_lanes_strings``, ``lanes_strings``,
   ``lanes_check``.

@@ -19,7 +19,7 @@ batch-invariant routes ``mbt2018-mean`` codes with: a stream written at batch 8 
 STREAM ORDER: one rANS stream per image for y — for k ascending, group k's anchors in raster order, then its non-anchors in raster
 order, channels inner; z as in the other hyperprior models.
 
-TrainEngine, graphed_training, CodecEngine and ReferenceBank do not take this model.  Owners: the schedule of the 2 K passes is
+TrainEngine, graphed_training, CodecEngine, ContextCodecEngine and ReferenceBank do not take this model.  Owners: the schedule of the 2 K passes is
 _scctx_passes, for encoder and decoder; the decoder's loop is _scctx_decode_from, over a source of symbols.  The host side of the
 coder is coding.py's: the start of the decoder's loop, the sources (a hop to the host's one-stream or lanes decoder,
 the device's lanes decoder on one upload image), and the lanes strings — count, parser, refusal, assembly, end-state check.

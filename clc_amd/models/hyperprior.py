@@ -8,8 +8,11 @@ so CompressAI checkpoints load.  CompressAI itself is not a dependency and nothi
 models are checked against a plain-torch restatement of the same definitions (tests/hyperprior_ref.py).
 
 They train through plain autograd and code through the model methods; TrainEngine, graphed_training, CodecEngine and ReferenceBank
-do not take them.  The host side of the context-model coders — the start of a decoder's pass loop, the symbols of a host-decoded step,
-the result item — is coding.py's; ``mbt2018`` and ``mbt2018-checkerboard`` each state their schedule once (_ar_passes, _ckbd_passes) and
+do not take them.  ``mbt2018`` and ``mbt2018-checkerboard`` on the lanes stream have a batched service of their own,
+clc_amd.codec.ContextCodecEngine (one captured graph per compress / decompress): its plans run the pass code below on a
+PassSchedule they keep — the pixel list, the chain's workspace, the stream's gather index and segment list, everything a pass would
+otherwise upload or allocate per call.  The plain hyperpriors have no such service.  The host side of the context-model coders —
+the start of a decoder's pass loop, the symbols of a host-decoded step, the result item — is coding.py's; ``mbt2018`` and ``mbt2018-checkerboard`` each state their schedule once (_ar_passes, _ckbd_passes) and
 share one encoder loop and one decoder loop over it (_encode_passes, _decode_passes / _decode_from).
 
 THE LANES STREAM (``compress(x, lanes=W)`` / ``decompress(..., lanes=W)``; DESIGN 27, include/clc_hip.h, clc_amd/ans.py) is opt-in and
@@ -221,6 +224,27 @@ def ckbd_pixels(H, W):
     return anchors, others
 
 
+class PassSchedule:
+    """What the passes of a context model over a [B, M, H, W] latent need besides the latent and the weights, made ONCE and outside any
+    graph capture (every entry is an upload or an allocation): ``steps``, the non-empty steps in order, each a list of (h, w);
+    ``pix``, their pixels back to back as the device's int32 [P, 2]; ``ws``, the chain's workspace for the largest step; ``ctx0``, the
+    checkerboard's zero context map (read only; None for mbt2018).  A model's own call makes one per call (_pass_schedule), a
+    ContextCodecEngine plan keeps one for its graph's lifetime.
+    ``_lanes_schedule`` adds what the lanes stream is cut by: ``segments`` (_lanes_segments), ``order`` (_lanes_order as the device's
+    int64 gather index) and ``seg_dev`` (the segments as the device's int32 list, for clc_rans_lanes_encode_list)."""
+
+    segments = order = seg_dev = ctx0 = None
+
+    def __init__(self, shape, steps, pix, ws):
+        self.shape, self.steps, self.pix, self.ws = shape, steps, pix, ws   # shape: (B, H, W, device)
+
+    def check(self, y_hat):
+        B, _, H, W = y_hat.shape
+        if self.shape != (B, H, W, y_hat.device):
+            raise ValueError(f"the schedule was made for (B, H, W, device) = {self.shape}, the latent is {(B, H, W, y_hat.device)}")
+        return self
+
+
 class JointAutoregressiveHierarchicalPriors(CodeInputs, MeanScaleHyperprior):
     """Minnen et al. 2018 with the context model (``mbt2018``): the mean-scale hyperprior plus a masked 5x5 convolution over the coded
     latent and a three-layer 1x1 ``entropy_parameters`` net on cat((hyper parameters, context)).
@@ -301,13 +325,18 @@ class JointAutoregressiveHierarchicalPriors(CodeInputs, MeanScaleHyperprior):
             self._ar_chain(px, B, H, W, y_hat, params, ws, filt)
             yield cnt, px, gp
 
-    def _ar_passes(self, params, y_hat, order):
+    def _pass_schedule(self, B, H, W, dev, order="wavefront"):
+        """the PassSchedule of ar_schedule(H, W, order): the pixel list's upload and the workspace's allocation, in one place"""
+        steps, pix = self._ar_pixels(ar_schedule(H, W, order), dev)
+        return PassSchedule((B, H, W, dev), steps, pix, self._ar_workspace(B * max(len(s) for s in steps), dev))
+
+    def _ar_passes(self, params, y_hat, order, sched=None):
         """THE SCHEDULE of mbt2018: the non-empty steps of ar_schedule(H, W, order).  The encoder takes whole wavefront steps, the
-        decoder must follow the stream: one raster pixel per step."""
+        decoder must follow the stream: one raster pixel per step.  sched: the caller's PassSchedule of that order (default: made
+        here, for this call); with one, the walk uploads and allocates nothing."""
         B, _, H, W = y_hat.shape
-        steps, pix = self._ar_pixels(ar_schedule(H, W, order), y_hat.device)
-        ws = self._ar_workspace(B * max(len(s) for s in steps), y_hat.device)
-        return self._ar_walk(steps, pix, y_hat, params, ws, self._ar_filters())
+        sched = self._pass_schedule(B, H, W, y_hat.device, order) if sched is None else sched.check(y_hat)
+        return self._ar_walk(sched.steps, sched.pix, y_hat, params, sched.ws, self._ar_filters())
 
     @torch.no_grad()
     def _encode_passes(self, who, y, params, passes, *schedule):
@@ -361,31 +390,64 @@ class JointAutoregressiveHierarchicalPriors(CodeInputs, MeanScaleHyperprior):
         """the lanes stream's segments: the non-empty wavefront steps in ar_lanes_order, n = pixels of the step x M"""
         return [len(s) * self.M for s in ar_schedule(H, W, "wavefront") if s]
 
-    def _lanes_passes(self, params, y_hat):
+    def _lanes_passes(self, params, y_hat, sched=None):
         """the schedule the lanes stream is cut by: the decoder runs the wavefront too"""
-        return self._ar_passes(params, y_hat, "wavefront")
+        return self._ar_passes(params, y_hat, "wavefront", sched)
+
+    def _lanes_schedule(self, B, H, W, dev):
+        """the PassSchedule of _lanes_passes with the stream's cut: segments, the gather index of _lanes_order and the segments' device
+        list, each uploaded here"""
+        sched = self._pass_schedule(B, H, W, dev)
+        sched.segments = self._lanes_segments(H, W)
+        sched.order = torch.from_numpy(self._lanes_order(H, W)).to(dev)
+        sched.seg_dev = torch.tensor(sched.segments, dtype=torch.int32).to(dev)
+        return sched
+
+    def _lanes_encoder_keywords(self, sched):
+        """what the model's lanes encoder takes from a schedule: clc_rans_lanes_encode_list reads its lengths from device memory"""
+        return {"segments_dev": sched.seg_dev}
+
+    def _lanes_encode(self, y, params, sched):
+        """_encode_passes over _lanes_passes on the caller's schedule: the encoder as a captured graph runs it"""
+        return self._encode_passes(type(self).__name__, y, params, self._lanes_passes, sched)
 
     @staticmethod
     def _lanes_most(H, W):
         """the pixels of the largest step"""
         return max(len(s) for s in ar_schedule(H, W, "wavefront"))
 
-    def _lanes_encode_device(self, sym, idx, segments, W):
-        """int32 [B, T] device symbols / indexes in stream order -> per image its lanes string: one launch of the model's lanes encoder
-        and one clc_rans_lanes_pack for the batch, then two device -> host copies (the header, the packed words)."""
+    def _lanes_launch(self, sym, idx, segments, W, header=None, **keywords):
+        """int32 [B, T] device symbols / indexes in stream order -> (packed words, header [B W + 1]) on the device: one launch of the
+        model's lanes encoder and one clc_rans_lanes_pack for the batch.  keywords: the encoder's regions / regions_dev /
+        segments_dev; without them it derives and uploads them, which a capture cannot."""
         gc = self.gaussian_conditional
+        out, _, result = self._lanes_encoder(sym, idx, segments, W, (gc._quantized_cdf, gc._cdf_length, gc._offset), **keywords)
+        return ops.rans_lanes_pack(out, result, header=header)
+
+    def _lanes_encode_device(self, sym, idx, segments, W):
+        """int32 [B, T] device symbols / indexes in stream order -> per image its lanes string: _lanes_launch, then two device -> host
+        copies (the header, the packed words)."""
         B = sym.shape[0]
-        out, _, result = self._lanes_encoder(sym, idx, segments, W, (gc._quantized_cdf, gc._cdf_length, gc._offset))
-        packed, header = ops.rans_lanes_pack(out, result)
+        packed, header = self._lanes_launch(sym, idx, segments, W)
         head = header.cpu().numpy()
         words = packed[:int(head[B * W])].cpu().numpy() if (head[:B * W] >= 0).all() else np.zeros(0, np.int32)
         return lanes_strings(head, words, B, W)   # (raises by name on a negative code)
 
+    @staticmethod
+    def _lanes_gather(t, order):
+        """_encode_passes' raster [B, H*W, M] buffer -> [B, T] in stream order, by the device's index tensor"""
+        return t.index_select(1, order).reshape(t.shape[0], -1)
+
     def _lanes_y_strings(self, sym, idx, H, W, Wn):
         """_encode_passes' raster [B, H*W, M] buffers -> the lanes strings: gathered into stream order on the device by one index tensor"""
         order = torch.from_numpy(self._lanes_order(H, W)).to(sym.device)
-        flat = lambda t: t.index_select(1, order).reshape(t.shape[0], -1)
-        return self._lanes_encode_device(flat(sym), flat(idx), self._lanes_segments(H, W), Wn)
+        return self._lanes_encode_device(self._lanes_gather(sym, order), self._lanes_gather(idx, order), self._lanes_segments(H, W), Wn)
+
+    def _lanes_pack_scheduled(self, sym, idx, sched, W, regions, regions_dev, header):
+        """_lanes_y_strings' device half on a caller's schedule and regions (ops.rans_lanes_regions and their device copy): the gather,
+        the encoder and the pack with nothing uploaded, allocated on the host or read back -> (packed words, header)"""
+        return self._lanes_launch(self._lanes_gather(sym, sched.order), self._lanes_gather(idx, sched.order), sched.segments, W, header=header,
+                                  regions=regions, regions_dev=regions_dev, **self._lanes_encoder_keywords(sched))
 
     @torch.no_grad()
     def _decode_lanes(self, subs, params, device_coder=True):
@@ -401,11 +463,20 @@ class JointAutoregressiveHierarchicalPriors(CodeInputs, MeanScaleHyperprior):
             decoders = [ans.LanesDecoder(img) for img in subs]
             src = HostSymbols([d.decode for d in decoders], gc.host_tables(), B * self._lanes_most(H, W) * M, y_hat.device, state=decoders)
             return self._decode_from(src, params, y_hat, self._lanes_passes), decoders
-        tables, table = (gc._quantized_cdf, gc._cdf_length, gc._offset), gc.scale_table
         state, spans, words = upload_streams(subs, 2 * ans.LANES, y_hat.device)   # a wave stream starts with its 64 lane states
-        for _, px, gp in self._lanes_passes(params, y_hat):
+        return self._lanes_decode_pass(params, y_hat, (state, spans, words)), state
+
+    def _lanes_decode_pass(self, params, y_hat, streams, sched=None):
+        """The device decoder's pass over the caller's (state, spans, words) views of an uploaded coding.stream_image -> y_hat: per step
+        of _lanes_passes the chain and ONE clc_ar_lanes_decode; state is advanced in place.  params, y_hat: decoder_start's.  With a
+        schedule the pass is launches only — what a graph captures."""
+        B, M, H, W = y_hat.shape
+        gc = self.gaussian_conditional
+        tables, table = (gc._quantized_cdf, gc._cdf_length, gc._offset), gc.scale_table
+        state, spans, words = streams
+        for _, px, gp in self._lanes_passes(params, y_hat, sched):
             ops.ar_lanes_decode(gp, M, px, B, H, W, table, tables, words, spans, state, y_hat)
-        return y_hat, state
+        return y_hat
 
     @torch.no_grad()
     def _decompress_lanes(self, strings, shape, Wn, device_coder, check):
@@ -496,21 +567,27 @@ class JointCheckerboardHierarchicalPriors(JointAutoregressiveHierarchicalPriors)
     def _ckbd_filters(self):
         return linear_filters(self.entropy_parameters)
 
-    def _ckbd_passes(self, params, y_hat):
+    def _pass_schedule(self, B, H, W, dev):
+        """the PassSchedule of the two passes: the pixel list's upload, the workspace and the zero context map, in one place"""
+        anchors, others = ckbd_pixels(H, W)
+        na, nn_, pix = self._ckbd_lists(H, W, dev)
+        sched = PassSchedule((B, H, W, dev), [s for s in (anchors, others) if s], pix, self._ckbd_workspace(B * max(na, nn_), dev))
+        sched.ctx0 = torch.zeros((B, 2 * self.M, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
+        return sched
+
+    def _ckbd_passes(self, params, y_hat, sched=None):
         """THE SCHEDULE of the checkerboard model, for encoder and decoder alike: the anchors, then the non-anchors; an empty pass is
         skipped.  Pass 1 reads a zero context map, pass 2 the context layer over the anchors that pass 1 committed.  Per pass the
-        chain, then (pixels of the pass, its pixel list, its (scales | means) rows) to the caller's body."""
+        chain, then (pixels of the pass, its pixel list, its (scales | means) rows) to the caller's body.  sched: the caller's
+        PassSchedule (default: made here, for this call); with one, the passes upload and allocate nothing but the context map."""
         B, M, H, W = y_hat.shape
-        na, nn_, pix = self._ckbd_lists(H, W, y_hat.device)
-        ws, filt = self._ckbd_workspace(B * max(na, nn_), y_hat.device), self._ckbd_filters()
-        for lo, cnt in ((0, na), (na, nn_)):
-            if not cnt:
-                continue
-            if lo:
-                ctx_map = self.context_prediction(y_hat)
-            else:
-                ctx_map = torch.zeros((B, 2 * M, H, W), device=y_hat.device, dtype=torch.float32).contiguous(memory_format=CL)
+        sched = self._pass_schedule(B, H, W, y_hat.device) if sched is None else sched.check(y_hat)
+        pix, ws, filt = sched.pix, sched.ws, self._ckbd_filters()
+        lo = 0
+        for cnt in (len(s) for s in sched.steps):
+            ctx_map = self.context_prediction(y_hat) if lo else sched.ctx0   # (ctx0 is never written)
             px = pix[lo:lo + cnt]
+            lo += cnt
             self._ckbd_chain(px, B, H, W, params, ctx_map, ws, filt)
             yield cnt, px, ws["gp"]
 
@@ -536,8 +613,11 @@ class JointCheckerboardHierarchicalPriors(JointAutoregressiveHierarchicalPriors)
         anchors, others = ckbd_pixels(H, W)
         return [len(anchors) * self.M, len(others) * self.M]
 
-    def _lanes_passes(self, params, y_hat):
-        return self._ckbd_passes(params, y_hat)
+    def _lanes_passes(self, params, y_hat, sched=None):
+        return self._ckbd_passes(params, y_hat, sched)
+
+    def _lanes_encoder_keywords(self, sched):
+        return {}   # clc_rans_lanes_encode takes its two segments by value
 
     @staticmethod
     def _lanes_most(H, W):

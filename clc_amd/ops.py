@@ -3113,13 +3113,25 @@ def rans_lanes_encode(symbols, indexes, segments, W, tables, out=None, regions=N
     return out, regions, result
 
 
-def rans_lanes_encode_list(symbols, indexes, segments, W, tables, out=None, regions=None):
+def rans_lanes_encode_list(symbols, indexes, segments, W, tables, out=None, regions=None, regions_dev=None, segments_dev=None):
     """clc_rans_lanes_encode_list: rans_lanes_encode for ANY number of segments (mbt2018's wavefront steps: 61 at a 16 x 16 latent, 141
     at 32 x 48).  The lengths are checked here, on the host (non-negative, sum <= T < 2^27), and uploaded once; the kernel reads them
-    from device memory.  Everything else, the return value included, is rans_lanes_encode's."""
+    from device memory.  regions_dev: as for rans_lanes_encode; segments_dev: the caller's device copy of `segments` (contiguous int32
+    [len(segments)], holding exactly those lengths: the host list is what is checked), which spares the upload — a captured graph
+    passes both.  Everything else, the return value included, is rans_lanes_encode's."""
+    who = "rans_lanes_encode_list"
+    for t, what, dim in ((regions_dev, "regions_dev", 3), (segments_dev, "segments_dev", 1)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.dim() != dim):
+            shape = "[B, W, 2]" if dim == 3 else "[len(segments)]"
+            raise ValueError(f"{who}: {what} must be a contiguous int32 {shape} device tensor")
+    if segments_dev is not None and segments_dev.numel() != len(segments):
+        raise ValueError(f"{who}: segments_dev holds {segments_dev.numel()} lengths, segments {len(segments)}")
     B, T, W, segments, (cp, stride, rows, lp, op), out, regions, reg_dev, result = _lanes_encode_args(
-        "rans_lanes_encode_list", symbols, indexes, segments, W, tables, out, regions, None, None)
-    seg_dev = torch.tensor(segments, dtype=torch.int32).to(symbols.device) if segments else None
+        who, symbols, indexes, segments, W, tables, out, regions, regions_dev, None)
+    if segments_dev is not None:
+        seg_dev = segments_dev
+    else:
+        seg_dev = torch.tensor(segments, dtype=torch.int32).to(symbols.device) if segments else None
     _lib.check(_L().clc_rans_lanes_encode_list(symbols.data_ptr(), indexes.data_ptr(), T, B, seg_dev.data_ptr() if segments else None,
                                                len(segments), W, cp, stride, rows, lp, op, out.data_ptr(), reg_dev.data_ptr(),
                                                result.data_ptr(), _stream()), "clc_rans_lanes_encode_list")
