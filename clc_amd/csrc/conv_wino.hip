@@ -43,7 +43,7 @@ struct WinoParams {
 };
 
 #ifndef WINO_AB
-#define WINO_AB 0   // timing builds of conv_wino_kernel (results WRONG for 1..8): 1 no MFMAs, 2 one output round of two, 4 no filter loads, 8 no transform-ahead, 32 phase time stamps
+#define WINO_AB 0   // timing builds of conv_wino_kernel (results WRONG for 1..8): 1 no MFMAs, 2 one output round of two, 4 no filter loads, 8 no transform-ahead, 32 phase time stamps (both kernels)
 #endif
 #if WINO_AB & 32   // phase time stamps of workgroup 0 / wave 0's second item (tools/bench_wino.py prints them through clc_wino_debug)
 __device__ unsigned long long wino_dbg[32];
@@ -309,22 +309,40 @@ __global__ __launch_bounds__(512, 1) void conv_wino_kernel(const WinoParams wp) 
   }
 }
 
-// ---- the 64-wide instantiation: 64 input channels resident (45 KB halo), 64 output channels per item, 16-channel chunks (V: 32 KB) — 78 KB of LDS and
-// <= 256 VGPRs, so TWO workgroups of 4 waves share a CU and one's transforms / output rounds run under the other's MFMAs.  Wave w owns row w of
-// the 4 x 4 transformed positions (xi = 4 w .. 4 w + 3): 4 x (32 tiles x 64 out) accumulators, 64 MFMAs per chunk.  Takes the 64 -> 64 layers of
-// the transforms' first / last stages (128 x 128 maps at 256 x 256 input), which the 128-wide kernel cannot.
+// ---- the 64-wide instantiation: 64 input channels resident (45 KB halo), 64 output channels per item — 64 KB of LDS (the output round's image, over
+// the halo) and <= 256 VGPRs, so TWO workgroups of 4 waves share a CU and one's halo wait / output round runs under the other's MFMAs.  Wave w owns
+// row w of the 4 x 4 transformed positions (xi = 4 w .. 4 w + 3) for all 64 output channels: 4 x (32 tiles x 64 out) accumulators.  Nobody else
+// reads that row, and the MFMA A operand of lane (li, h) is ONE tile (li) and ONE 16-byte channel group, so there is no V buffer here: every lane
+// builds its own operand from the halo — per step (16-channel chunk kc, quarter pair t8) 8 ds_read_b128 of rows ra, rb of its tile's 4 x 4 patch
+// (16-B chunk 4 kc + 2 t8 + h), T = d[ra] +- d[rb] (row w of B^T d), then T0 - T2, T1 + T2, T2 - T1, T1 - T3 (times B): the A operands of
+// xi = 4 w .. 4 w + 3, 32 MFMAs.  Software-pipelined: the reads and adds of step + 1 sit between the four 8-MFMA groups of the step, the filter
+// fragments of (step + 1, s) are requested behind group s of the step (three groups ahead), the order pinned by sched_barrier.  Barriers only
+// around the halo deposit and the output round.  Takes the 64 -> 64 layers of the transforms' first / last stages (128 x 128 maps at 256 x 256
+// input), which the 128-wide kernel cannot.
+// Measured (tools/bench_wino.py with a -DWINO_AB=32 build, 64 -> 64 @ 8 x 128^2: s_memtime stamps of one item, two workgroups per CU): ~50 k cycles
+// per item against 16.4 k of MFMA issue per wave — 8 k for the halo (behind the previous item's store acknowledgements), 5.2-7.9 k per chunk with
+// both workgroups in their K loops (4.9 k with the other one in its memory phases), 5 k staging S, 6.6 k for the epilogue.
 constexpr int HALO2_FLOATS = HPIX * 64;   // 46 080 B
-constexpr int V2_FLOATS = 16 * 32 * 16;   // 32 768 B
+constexpr int S2_FLOATS = 16 * 32 * 32;   // 65 536 B: the output round's image
 constexpr int PIECES2 = HPIX / 4;         // 1-KB LDS-DMA pieces (four pixels each)
+static_assert(HALO2_FLOATS <= S2_FLOATS, "the halo lies inside the output round's image");
+// Slot of 16-B chunk c of halo pixel (hy, hx): c ^ wino64_swz(hy, hx).  A ds_read_b128 is served in lane groups {0-3, 12-15, 20-27} and {4-11, 16-19,
+// 28-31} (+ 32); its lanes li = 8 ty + tx read ONE chunk at pixels (2 ty + r, 2 tx + c).  Each group holds every tx & 3 once per ty and every ty
+// once, so (tx + (c >> 1)) & 3 in the low and (ty + (r >> 1)) & 3 in the high bits give its 16 lanes the 16 distinct slots: 256 B per cycle.
+__device__ __forceinline__ int wino64_swz(int hy, int hx) { return ((hx >> 1) & 3) | (((hy >> 1) & 3) << 2); }
+// The input transform's f32 operations as single instructions: plain -O3 packs neighbouring adds into v_pk_*_f32, which cost the MFMAs they are
+// issued between more than the two scalar ones.  (fma1: s b + a with s = +-1 in an SGPR — exactly a +- b.)
+__device__ __forceinline__ float add1(float a, float b) { float r; asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ float sub1(float a, float b) { float r; asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ float fma1(float s, float b, float a) { float r; asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "s"(s), "v"(b), "v"(a)); return r; }
 
 template <bool SHUF>
 __global__ __launch_bounds__(256, 2) void conv_wino64_kernel(const WinoParams wp) {
   const ConvParams& p = wp.c;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* halo = smem;                  // [HPIX][64], 16-B chunk c of halo pixel (hy, hx) in slot c ^ (((hx >> 1) & 3) << 2)
-  float* V = smem + HALO2_FLOATS;      // [16][32][16]: chunk q of row t in slot q ^ ((t >> 2) & 3)
-  float* S = smem;                     // output rounds: [16][32][32] over the halo and the head of V (both free by then)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float* halo = smem;                  // [HPIX][64], 16-B chunk c of halo pixel (hy, hx) in slot c ^ wino64_swz(hy, hx)
+  float* S = smem;                     // output round: [16][32][32] over the halo (free by then)
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 31, h = lane >> 5;
   const int tiles_w = p.W / TW, tiles_h = p.H / TH;
   const int KCT = wp.ncg * 2;          // 32-channel chunks of the packed filter (wp.ncg: groups of 64 input channels)
@@ -332,17 +350,31 @@ __global__ __launch_bounds__(256, 2) void conv_wino64_kernel(const WinoParams wp
   const int i0 = (int)((long)wp.items * blockIdx.x / gridDim.x), i1 = (int)((long)wp.items * (blockIdx.x + 1) / gridDim.x);
   const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t ur = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wp.u), 0, wp.u_bytes, 0x00020000);
-  // input-transform role: (tile t, 16-B chunk q of the 16-channel chunk, half); output-transform role: (tile to, 16-B chunk qo of a 32-channel block)
-  const int q = tid & 3, t = (tid >> 2) & 31, half = tid >> 7;
-  const int ty = t >> 3, tx = t & 7;
+  // operand role = MFMA role: lane (li, h) of wave w holds tile li (ty, tx), row w of B^T d B, channels 4 (2 t8 + h) .. + 3 of the chunk;
+  // output-transform role: (tile to, 16-B chunk qo of a 32-channel block)
+  const int ty = li >> 3, tx = li & 7;
   const int qo = tid & 15;             // (output role: chunk qo of the 64 channels, tiles (tid >> 4) and + 16)
   const bool lean = epilogue_is_lean(p);
-  int afo[2];
+  // B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]: row w = d[ra] + sg d[rb] (wave-uniform; fma(+-1, b, a) is a +- b exactly)
+  const int ra = wave == 0 ? 0 : (wave == 2 ? 2 : 1), rb = wave == 0 ? 2 : (wave == 1 ? 2 : (wave == 2 ? 1 : 3));
+  const float sg = wave == 1 ? 1.f : -1.f;
+  // LDS byte address of chunk h of the patch's pixel (row ra | rb, column 0): columns c = 2 ch, 2 ch + 1 share a swizzle; column c lies at + 256 c and the
+  // step's chunk 4 kc + 2 t8 + h at ^ ((4 kc + 2 t8) << 4) (h: bit 0 of the chunk index; the slot bits 4..7 of the address lie below the pixel's)
+  int pa[2][2];
 #pragma unroll
-  for (int t8 = 0; t8 < 2; ++t8) afo[t8] = li * 16 + (((2 * t8 + h) ^ ((li >> 2) & 3)) << 2);
+  for (int rr = 0; rr < 2; ++rr)
+#pragma unroll
+    for (int ch = 0; ch < 2; ++ch) {
+      const int hy = 2 * ty + (rr ? rb : ra);
+      pa[rr][ch] = (hy * HW + 2 * tx) * 256 + ((h ^ wino64_swz(hy, 2 * tx + 2 * ch)) << 4);
+    }
+  const char* hb = reinterpret_cast<const char*>(halo);
+  auto read_row = [&](f32x4 (&d)[4], int rr, int kx) {      // the four pixels of patch row ra (rr = 0) / rb (1), chunk kx >> 4 (+ h)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) d[c] = *reinterpret_cast<const f32x4*>(hb + ((pa[rr][c >> 1] ^ kx) + c * 256));
+  };
   const unsigned b_lane = (unsigned)lane * 16u;
 
-  int cur_pt = -1, cur_cg = -1;
   for (int it = i0; it < i1; ++it) {
     const int pt = it / wp.ntn, nt = it - pt * wp.ntn;      // nt: n-tile of 64 output channels = blocks 2 (nt & 1), +1 of 128-row tile nt >> 1
     const int txx = pt % tiles_w, t2 = pt / tiles_w, tyy = t2 % tiles_h, n = t2 / tiles_h;
@@ -354,96 +386,91 @@ __global__ __launch_bounds__(256, 2) void conv_wino64_kernel(const WinoParams wp
       for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[s][nb][r] = 0.f;
-    f32x4 bq[2][2][2];
-    auto load_b = [&](int slot, int s, int c16) {     // xi = 4 wave + s, 16-channel chunk c16 (global): both 32-row blocks
-      const int kcg = c16 >> 1, t8g = 2 * (c16 & 1);
+    f32x4 bq[4][2];          // a ring over s: slot s holds the fragments of (step, xi = 4 wave + s), refilled for the next step behind the step's group s
+    auto load_b = [&](int s, int c16, int t8) {       // xi = 4 wave + s, 16-channel chunk c16 (global), quarter pair t8: both 32-row blocks
+      const int kcg = c16 >> 1, t8g = 2 * (c16 & 1) + t8;
 #pragma unroll
-      for (int nb = 0; nb < 2; ++nb) {
-        const unsigned base = (unsigned)((((((nt >> 1) * 16 + 4 * wave + s) * KCT + kcg) * 4 + 2 * (nt & 1) + nb) * 4 + t8g)) * 1024u;
-#pragma unroll
-        for (int t8 = 0; t8 < 2; ++t8) bq[slot][nb][t8] = buf_load4(ur, b_lane + base + (unsigned)(t8 * 1024));
-      }
+      for (int nb = 0; nb < 2; ++nb)
+        bq[s][nb] = buf_load4(ur, b_lane + (unsigned)((((((nt >> 1) * 16 + 4 * wave + s) * KCT + kcg) * 4 + 2 * (nt & 1) + nb) * 4 + t8g)) * 1024u);
     };
-    load_b(0, 0, 0);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) load_b(s, 0, 0);
+    WINO_STAMP(0);
 
     for (int cg = 0; cg < wp.ncg; ++cg) {
-      if (pt != cur_pt || cg != cur_cg) {   // block-uniform.  (Every wave is past the last read of the old halo / the output rounds: barriers below.)
-        cur_pt = pt; cur_cg = cg;
+      if (cg) __syncthreads();              // every wave has read the previous group's halo.  (cg = 0: the barrier behind the previous item's output round.)
+      {
         const int org = ((n * p.H + oy0 - 1) * p.W + ox0 - 1) * p.ldx + cg * 64;
         int hy = 0, hx = 4 * wave + (lane >> 4);    // (the halo pixel advances by 16 per step, HW = 18: no division in the loop)
 #pragma unroll 1
         for (int pc = wave; pc < PIECES2; pc += 4) {
           const int iy = oy0 - 1 + hy, ix = ox0 - 1 + hx;
           const bool ok = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
-          const int c = (lane & 15) ^ (((hx >> 1) & 3) << 2);
+          const int c = (lane & 15) ^ wino64_swz(hy, hx);
           dma16(xr, halo + pc * 256, ok ? (unsigned)(org + (hy * p.W + hx) * p.ldx + c * 4) * 4u : kOOB);
           hx += 16;
           if (hx >= HW) { hx -= HW; ++hy; }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
+      __syncthreads();       // the halo has landed (everyone's pieces)
+      WINO_STAMP(1);
+      f32x4 aq[2][4];        // [step parity][s]: the A operands of xi = 4 wave + s, this step's and the next one's
+      f32x4 da[4], db[4];
+      auto rows_T = [&]() {                 // row w of B^T d, into da
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) da[c][e] = fma1(sg, db[c][e], da[c][e]);
+      };
+      auto cols_B = [&](f32x4 (&v)[4]) {    // ... times B
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          v[0][e] = sub1(da[0][e], da[2][e]);
+          v[1][e] = add1(da[1][e], da[2][e]);
+          v[2][e] = sub1(da[2][e], da[1][e]);
+          v[3][e] = sub1(da[1][e], da[3][e]);
+        }
+      };
+      read_row(da, 0, 0);    // step (chunk 0, t8 0) of this group, not overlapped
+      read_row(db, 1, 0);
+      rows_T();
+      cols_B(aq[0]);
+      WINO_STAMP(2);
 #pragma unroll 1
       for (int kc = 0; kc < 4; ++kc) {
-        __syncthreads();     // the halo has landed; every wave is done reading V
-        {
-          const int cidx = kc * 4 + q;
-          f32x4 d[3][4];
-#pragma unroll
-          for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              const int hy = 2 * ty + r + half, hx = 2 * tx + c;
-              d[r][c] = *reinterpret_cast<const f32x4*>(halo + (hy * HW + hx) * 64 + ((cidx ^ (((hx >> 1) & 3) << 2)) << 2));
-            }
-          f32x4 T[2][4];
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            if (half == 0) { T[0][c] = d[0][c] - d[2][c]; T[1][c] = d[1][c] + d[2][c]; }
-            else           { T[0][c] = d[1][c] - d[0][c]; T[1][c] = d[0][c] - d[2][c]; }
-          }
-#pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            const f32x4 v0 = T[i][0] - T[i][2], v1 = T[i][1] + T[i][2], v2 = T[i][2] - T[i][1], v3 = T[i][1] - T[i][3];
-            float* dst = V + (((2 * half + i) * 4) * 32 + t) * 16 + ((q ^ ((t >> 2) & 3)) << 2);
-            *reinterpret_cast<f32x4*>(dst) = v0;
-            *reinterpret_cast<f32x4*>(dst + 1 * 32 * 16) = v1;
-            *reinterpret_cast<f32x4*>(dst + 2 * 32 * 16) = v2;
-            *reinterpret_cast<f32x4*>(dst + 3 * 32 * 16) = v3;
-          }
-        }
-        __syncthreads();
+        if (cg == 0) WINO_STAMP(3 + kc);
         const int c16 = cg * 4 + kc;
-        f32x4 aq[2][2];   // (one xi ahead, like the filter fragments: all four at once would not fit beside the accumulators)
 #pragma unroll
-        for (int t8 = 0; t8 < 2; ++t8) aq[0][t8] = *reinterpret_cast<const f32x4*>(V + (4 * wave) * 512 + afo[t8]);
+        for (int t8 = 0; t8 < 2; ++t8) {    // step (kc, t8): 4 groups of 8 MFMAs; between them the operands of the next step.  (The last step of
+          // the group runs a throw-away pass over chunk 0 — the next group's / item's first step starts over — instead of a branch around each part.)
+          const int kxn = t8 == 0 ? (4 * kc + 2) << 4 : (4 * ((kc + 1) & 3)) << 4;
+          const int c16n = t8 == 0 ? c16 : (c16 + 1 < NC16 ? c16 + 1 : 0);
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const int cur = s & 1;
-          if (s < 3) {
-            load_b(cur ^ 1, s + 1, c16);
-#pragma unroll
-            for (int t8 = 0; t8 < 2; ++t8) aq[cur ^ 1][t8] = *reinterpret_cast<const f32x4*>(V + (4 * wave + s + 1) * 512 + afo[t8]);
-          } else {
-            load_b(cur ^ 1, 0, c16 + 1 < NC16 ? c16 + 1 : 0);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int t8 = 0; t8 < 2; ++t8)
+          for (int s = 0; s < 4; ++s) {
+            if (s == 0) read_row(da, 0, kxn);
+            else if (s == 1) read_row(db, 1, kxn);
+            else if (s == 2) rows_T();
+            else cols_B(aq[t8 ^ 1]);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int ss = 0; ss < 4; ++ss)
 #pragma unroll
-              for (int nb = 0; nb < 2; ++nb) acc[s][nb] = MFMA(aq[cur][t8][ss], bq[cur][nb][t8][ss], acc[s][nb]);
-          __builtin_amdgcn_sched_barrier(0);
+              for (int nb = 0; nb < 2; ++nb) acc[s][nb] = MFMA(aq[t8][s][ss], bq[s][nb][ss], acc[s][nb]);
+            load_b(s, c16n, t8 ^ 1);
+            __builtin_amdgcn_sched_barrier(0);
+          }
         }
       }
     }
+    WINO_STAMP(11);
     // ---- output transform Y = A^T M A, A^T = [1 1 1 0; 0 1 -1 -1].  Columns first, in registers (wave w holds row w of M): c_b = (M A)[w][b]; then the
-    // rows meet through LDS in ONE round — [w][b][tile][64 channels] = 64 KB over the halo and V (the next item re-deposits the halo)
-    cur_pt = -1;
+    // rows meet through LDS in ONE round — [w][b][tile][64 channels] = 64 KB over the halo (the next item re-deposits it)
     {
       const int co = nt * 64 + (qo >> 3) * 32 + (qo & 7) * 4;
       const f32x4 bv = epilogue_bias4(p.bias, co);
-      __syncthreads();       // the last chunk's MFMAs have read V, its transform the halo
+      __syncthreads();       // every wave has read the halo for its last step
+      WINO_STAMP(13);
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
         float* dst = S + ((wave * 2 + b) * 32) * 64;
@@ -457,11 +484,9 @@ __global__ __launch_bounds__(256, 2) void conv_wino64_kernel(const WinoParams wp
           }
       }
       __syncthreads();
-#pragma unroll 1
-      for (int tt = 0; tt < 2; ++tt) {     // this thread's two tiles
-        const int to = (tid >> 4) + 16 * tt, tyo = to >> 3, txo = to & 7;
+      WINO_STAMP(14);
+      auto read_y = [&](int to, f32x4 (&y)[2][2]) {     // [output row a][output column b] of tile `to`, this thread's four channels
         const int col = (qo << 2) ^ (((to >> 2) & 1) << 5);
-        f32x4 y[2][2];       // [output row a][output column b]
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
           f32x4 c[4];
@@ -470,35 +495,64 @@ __global__ __launch_bounds__(256, 2) void conv_wino64_kernel(const WinoParams wp
           y[0][b] = (c[0] + c[1]) + c[2];
           y[1][b] = (c[1] - c[2]) - c[3];
         }
-        const int mrow0 = (n * p.OH + oy0 + 2 * tyo) * p.OW + ox0 + 2 * txo;
+      };
+      if (lean && !SHUF) {
+        // What the step's layers take.  The accumulators are dead, so all eight pixels of this thread's two tiles fit in registers: every epilogue
+        // input is requested before the first store.  (A pixel pair at a time, each pair's loads wait behind the pair before's stores — vmcnt
+        // counts both — i.e. for their write acknowledgements: four such waits were 20 k of an item's 49 k cycles.)
+        f32x4 y[2][2][2];
+        Lean4In in[2][2][2];
+        size_t px[2][2];
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+          const int to = (tid >> 4) + 16 * tt, tyo = to >> 3, txo = to & 7;
+          read_y(to, y[tt]);
+#pragma unroll
+          for (int a = 0; a < 2; ++a) px[tt][a] = (size_t)((n * p.OH + oy0 + 2 * tyo + a) * p.OW + ox0 + 2 * txo);
+        }
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+          for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) in[tt][a][b] = lean_load4(p, px[tt][a] + b, co);
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+          for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) lean_finish4(p, bv, y[tt][a][b], in[tt][a][b], px[tt][a] + b, co);
+      } else {
 #pragma unroll 1
-        for (int a = 0; a < 2; ++a) {
-          const size_t pix = (size_t)(mrow0 + a * p.OW);
-          const f32x4 ya = a ? y[1][0] : y[0][0], yb = a ? y[1][1] : y[0][1];
-          if (lean) {
-            if (!SHUF) {
-              const Lean4In ia = lean_load4(p, pix, co), ib = lean_load4(p, pix + 1, co);
-              lean_finish4(p, bv, ya, ia, pix, co);
-              lean_finish4(p, bv, yb, ib, pix + 1, co);
-            } else {
+        for (int tt = 0; tt < 2; ++tt) {     // this thread's two tiles
+          const int to = (tid >> 4) + 16 * tt, tyo = to >> 3, txo = to & 7;
+          f32x4 y[2][2];
+          read_y(to, y);
+          const int mrow0 = (n * p.OH + oy0 + 2 * tyo) * p.OW + ox0 + 2 * txo;
+#pragma unroll 1
+          for (int a = 0; a < 2; ++a) {
+            const size_t pix = (size_t)(mrow0 + a * p.OW);
+            const f32x4 ya = a ? y[1][0] : y[0][0], yb = a ? y[1][1] : y[0][1];
+            if (lean) {              // (with SHUF)
               lean_store_shuffle4(p, bv, ya, n, oy0 + 2 * tyo + a, ox0 + 2 * txo, co);
               lean_store_shuffle4(p, bv, yb, n, oy0 + 2 * tyo + a, ox0 + 2 * txo + 1, co);
-            }
-          } else if (!SHUF) {
-            const Epi4In ia = epilogue_load4(p, pix, co), ib = epilogue_load4(p, pix + 1, co);
-            epilogue_finish4(p, bv, ya, ia, pix, co);
-            epilogue_finish4(p, bv, yb, ib, pix + 1, co);
-          } else {
+            } else if (!SHUF) {
+              const Epi4In ia = epilogue_load4(p, pix, co), ib = epilogue_load4(p, pix + 1, co);
+              epilogue_finish4(p, bv, ya, ia, pix, co);
+              epilogue_finish4(p, bv, yb, ib, pix + 1, co);
+            } else {
 #pragma unroll 1
-            for (int e = 0; e < 4; ++e) {
-              epilogue_store(p, ya[e], bv[e], (int)pix, co + e, p.OH, p.OW, 0, 0);
-              epilogue_store(p, yb[e], bv[e], (int)pix + 1, co + e, p.OH, p.OW, 0, 0);
+              for (int e = 0; e < 4; ++e) {
+                epilogue_store(p, ya[e], bv[e], (int)pix, co + e, p.OH, p.OW, 0, 0);
+                epilogue_store(p, yb[e], bv[e], (int)pix + 1, co + e, p.OH, p.OW, 0, 0);
+              }
             }
           }
         }
       }
     }
-    __syncthreads();         // the next item's halo deposit / transforms write over S
+    WINO_STAMP(15);
+    __syncthreads();         // the next item's halo deposit writes over S
   }
 }
 
@@ -615,7 +669,7 @@ int clc_conv_wino_launch(const void* conv_params, const float* u, hipStream_t st
     }
   } else {
     const int grid = wp.items < 512 ? wp.items : 512;
-    const int lds = (HALO2_FLOATS + V2_FLOATS) * 4;
+    const int lds = S2_FLOATS * 4;
     if (shuf) {
       if (once[k].first()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino64_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
       hipLaunchKernelGGL(conv_wino64_kernel<true>, dim3(grid), dim3(256), lds, st, wp);

@@ -1,5 +1,6 @@
 """Winograd F(2x2, 3x3) kernel (csrc/conv_wino.hip) against the halo / tiled kernels on the layers it takes: accuracy against an fp64 convolution
-and time, one process, hipGraph-replayed (median of `reps` replays of 10 back-to-back launches on rotating operands).  python tools/bench_wino.py [reps]"""
+and time, one process, hipGraph-replayed (median of `reps` replays of 10 back-to-back launches on rotating operands).  python tools/bench_wino.py [reps]
+WINO_SHAPES=n: the first n shapes; WINO_ONLY=text: the shapes whose name contains it (with a -DWINO_AB=32 build: the stamps of that kernel alone)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -32,6 +33,7 @@ SHAPES_ALL = [  # name, N, H, W, Cin, Cout, shuffle, transposed
     ("64->64 @8x32^2 fwd", 8, 32, 32, 64, 64, False, False),
 ]
 SHAPES = SHAPES_ALL[:int(os.environ.get('WINO_SHAPES', len(SHAPES_ALL)))]
+SHAPES = [s for s in SHAPES if os.environ.get("WINO_ONLY", "") in s[0]]   # (WINO_ONLY="64->64 @8x128^2 fwd": the stamps of that launch alone)
 g = torch.Generator().manual_seed(0)
 NB = 4
 for name, N, H, W, Cin, Cout, shuf, tr in SHAPES:
@@ -91,8 +93,12 @@ if hasattr(L, "clc_wino_debug") or os.environ.get("CLC_LIB_PATH"):   # a -DWINO_
         t = list(buf)
         names = {0: "item start", 1: "halo landed + barrier", 2: "first transform", 11: "after last chunk", 12: "DMA wait", 13: "round 0 barrier", 14: "round 0 staged",
                  15: "round 0 stored", 16: "round 1 barrier", 17: "round 1 staged", 18: "round 1 stored"}
+        prev = 0
         for k in range(1, 19):
-            print(f"  stamp {k:2d} {names.get(k, 'chunk %d barrier' % (k - 3)):24s} +{t[k] - t[k - 1]:7d} ticks  (total {t[k] - t[0]})")
+            if not t[k]:      # a stamp the kernel that ran does not take (the 64-wide one: four chunks, no DMA wait, one output round)
+                continue
+            print(f"  stamp {k:2d} {names.get(k, 'chunk %d barrier' % (k - 3)):24s} +{t[k] - t[prev]:7d} ticks  (total {t[k] - t[0]})")
+            prev = k
         if t[19] and t[20]:
             print(f"  round 0: staged -> y in registers {t[19] - t[14]} ticks, -> first pixel pair stored {t[20] - t[19]}, -> second {t[15] - t[20]}")
     except AttributeError:
