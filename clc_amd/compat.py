@@ -66,6 +66,7 @@ def install(force: bool = False):
 
     from . import ans, entropy_models, layers, models, ssim, train
     from .models import clc as _clc
+    from .models import video as _video
 
     done = []
 
@@ -87,13 +88,17 @@ def install(force: bool = False):
                 MeanScaleHyperprior=models.MeanScaleHyperprior,
                 JointAutoregressiveHierarchicalPriors=models.JointAutoregressiveHierarchicalPriors,
                 JointCheckerboardHierarchicalPriors=models.JointCheckerboardHierarchicalPriors, Elic2022=models.Elic2022,
-                Cheng2020Anchor=models.Cheng2020Anchor, Cheng2020Attention=models.Cheng2020Attention)
+                Cheng2020Anchor=models.Cheng2020Anchor, Cheng2020Attention=models.Cheng2020Attention,
+                ScaleSpaceFlow=models.ScaleSpaceFlow)
+        sys.modules["compressai.models.video"] = _video
+        sys.modules["compressai.models"].video = _video
         _module("compressai.datasets", ImageFolder=ImageFolder)
         _module("compressai.zoo", models={"clc": models.CLC, "tcm": models.TCM, "bmshj2018-hyperprior": models.ScaleHyperprior,
                                          "mbt2018-mean": models.MeanScaleHyperprior, "mbt2018": models.JointAutoregressiveHierarchicalPriors,
                                          "mbt2018-checkerboard": models.JointCheckerboardHierarchicalPriors, "elic2022": models.Elic2022,
-                                         "cheng2020-anchor": models.Cheng2020Anchor, "cheng2020-attn": models.Cheng2020Attention})
-        done += ["compressai.models", "compressai.datasets", "compressai.zoo"]
+                                         "cheng2020-anchor": models.Cheng2020Anchor, "cheng2020-attn": models.Cheng2020Attention},
+                video_models={"ssf2020": models.ScaleSpaceFlow})
+        done += ["compressai.models", "compressai.models.video", "compressai.datasets", "compressai.zoo"]
         c = sys.modules["compressai"]
         for sub in ("entropy_models", "ans", "layers", "models", "datasets", "zoo"):
             setattr(c, sub, sys.modules["compressai." + sub])

@@ -102,6 +102,13 @@ class SsimDesc(C.Structure):
                 ("dx", fp), ("lddx", C.c_int), ("dy", fp), ("lddy", C.c_int), ("dnext_x", fp), ("dnext_y", fp)]
 
 
+SS_MAX_TAPS = 33   # CLC_SS_MAX_TAPS
+
+
+class SsDesc(C.Structure):
+    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("levels", C.c_int), ("ntaps", C.c_int), ("taps", C.c_float * SS_MAX_TAPS)]
+
+
 class RefSrc(C.Structure):
     _fields_ = [("src", fp), ("h", C.c_int), ("w", C.c_int)]
 
@@ -295,6 +302,12 @@ SIGNATURES = {
     "clc_rans_lanes_pack": (_i, [fp, _l, fp, _i, _i, fp, _l, fp, fp]),
     "clc_ar_lanes_decode": (_i, [fp, _l, _i, fp, _i, _i, _i, _i, fp, _i, fp, _i, _i, fp, fp, fp, fp, fp, _i, fp, _l, fp, _l, fp]),
     "clc_rans_lanes_encode_list": (_i, [fp, fp, _l, _i, fp, _i, _i, fp, _i, _i, fp, fp, fp, fp, fp, fp]),
+    "clc_ss_volume_workspace_bytes": (_sz, [C.POINTER(SsDesc)]),
+    "clc_ss_volume_fwd": (_i, [C.POINTER(SsDesc), fp, _i, fp, fp, _sz, fp]),
+    "clc_ss_volume_bwd": (_i, [C.POINTER(SsDesc), fp, fp, _i, fp, _sz, fp]),
+    "clc_ss_warp_fwd": (_i, [fp, _i, _i, _i, _i, fp, _i, fp, _i, fp, _i, fp]),
+    "clc_ss_warp_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "clc_ss_warp_bwd": (_i, [fp, _i, _i, _i, _i, fp, _i, fp, _i, fp, _i, fp, _i, fp, _i, fp, fp, _sz, fp]),
 }
 
 

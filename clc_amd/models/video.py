@@ -1,0 +1,292 @@
+"""``ssf2020`` — the scale-space-flow video model of Agustsson et al. (CVPR 2020) as CompressAI publishes it — on the engine's own
+kernels: its nine sub-networks are ``conv(k=5, s=2)`` / ``deconv(k=5, s=2)`` stacks with ReLU (csrc/conv5.hip, the ReLU in the producing
+layer's epilogue), its three hyperpriors use the entropy models and the host rANS coder of the plain hyperprior baselines, and the two
+operators that make it a video model — the scale-space volume of the reference frame and the trilinear warp through it — run on
+csrc/scale_space.hip (clc_amd/scale_space.py).
+
+Written from CompressAI's published definition (module order and names, hence the ``state_dict`` keys; QReLU on the scale decoder;
+``quantize_ste(y - means) + means``; the keyframe's reconstruction detached, later ones not), so CompressAI checkpoints load.
+CompressAI is not a dependency: the model is checked against a plain-torch restatement (tests/ssf_ref.py).  CompressAI builds the three
+hyperpriors with its defaults (192, 192); here they are ``Hyperprior(planes, planes)``, the same at the default width, and
+``mid_planes`` sizes the six encoders / decoders only.
+
+A frame is coded against the previous RECONSTRUCTION: keyframe -> y, z; every later frame -> motion (y, z) and residual (y, z).
+``forward`` returns unclamped reconstructions, ``decompress`` too (callers clamp); both sides of the codec run the same unclamped
+chain, so ``decompress(compress(frames))`` equals the eval-mode forward bit for bit.
+
+The 3-channel residual head and the 6-channel motion head need an input gradient, which the few-channel patch-row path of
+layers.Conv2d does not give: their inputs are zero-padded to 4 / 8 channels and the filter likewise inside the forward (the
+Parameter keeps CompressAI's shape; autograd slices its gradient), so they run on the aligned 5x5 kernel.  The keyframe head keeps the
+patch rows (the image takes no gradient).
+
+Plain autograd and the model's own compress / decompress only: TrainEngine, graphed_training, CodecEngine and the lanes streams do
+not take this model.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .. import ans, ops
+from ..entropy_models import EntropyBottleneck, GaussianConditional
+from ..layers import conv, deconv
+from ..ops import ACT_NONE, ACT_RELU, CL
+from ..scale_space import gaussian_taps, scale_space_volume, scale_space_warp
+from .clc import CompressionModel, _resize_registered_buffers
+
+__all__ = ["ScaleSpaceFlow"]
+
+
+class _QReLUFn(torch.autograd.Function):
+    """CompressAI's QReLU: clamp(0, 2^bit_depth - 1) forward; backward passes the gradient inside the range and multiplies it by
+    exp(-alpha^beta |2 x / max - 1|^beta) outside (plain torch: three small maps per hyperprior)."""
+
+    @staticmethod
+    def forward(ctx, x, bit_depth, beta):
+        ctx.alpha, ctx.beta, ctx.max_value = 0.9943258522851727, beta, 2 ** bit_depth - 1
+        ctx.save_for_backward(x)
+        return x.clamp(min=0, max=ctx.max_value)
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        sub = torch.exp(-ctx.alpha ** ctx.beta * torch.abs(2.0 * x / ctx.max_value - 1) ** ctx.beta) * g
+        return torch.where((x < 0) | (x > ctx.max_value), sub, g), None, None
+
+
+class QReLU(nn.Module):
+    def __init__(self, bit_depth=8, beta=100):
+        super().__init__()
+        self.bit_depth, self.beta = int(bit_depth), beta
+
+    def forward(self, x):
+        return _QReLUFn.apply(x, self.bit_depth, self.beta)
+
+
+def _head(layer, x, act):
+    """a 5x5 / stride-2 layer whose input has Cin % 4 != 0 AND takes a gradient: input and filter zero-padded to the next multiple of 4"""
+    pad = -layer.in_channels % 4
+    if pad == 0:
+        return layer(x, act=act)
+    xp = F.pad(x, (0, 0, 0, 0, 0, pad)).contiguous(memory_format=CL)
+    wp = F.pad(layer.weight, (0, 0, 0, 0, 0, pad))
+    return ops.conv2d(xp, wp, layer.bias, stride=layer.stride[0], act=act)
+
+
+class _Stack(nn.Sequential):
+    """conv / deconv layers with ReLU placeholders between them (CompressAI's Sequential indexes); the ReLUs run in the epilogues"""
+
+    input_grad = False   # True: the first layer's input takes a gradient (see _head)
+
+    def forward(self, x):
+        layers = [m for m in self if not isinstance(m, nn.ReLU)]
+        for i, m in enumerate(layers):
+            act = ACT_RELU if i + 1 < len(layers) else ACT_NONE
+            x = _head(m, x, act) if (i == 0 and self.input_grad) else m(x, act=act)
+        return x
+
+
+class Encoder(_Stack):
+    def __init__(self, in_planes, mid_planes=128, out_planes=192, input_grad=False):
+        super().__init__(conv(in_planes, mid_planes), nn.ReLU(inplace=True), conv(mid_planes, mid_planes), nn.ReLU(inplace=True),
+                         conv(mid_planes, mid_planes), nn.ReLU(inplace=True), conv(mid_planes, out_planes))
+        self.input_grad = bool(input_grad)
+
+
+class Decoder(_Stack):
+    def __init__(self, out_planes, in_planes=192, mid_planes=128):
+        super().__init__(deconv(in_planes, mid_planes), nn.ReLU(inplace=True), deconv(mid_planes, mid_planes), nn.ReLU(inplace=True),
+                         deconv(mid_planes, mid_planes), nn.ReLU(inplace=True), deconv(mid_planes, out_planes))
+
+
+class HyperEncoder(_Stack):
+    def __init__(self, in_planes=192, mid_planes=192, out_planes=192):
+        super().__init__(conv(in_planes, mid_planes), nn.ReLU(inplace=True), conv(mid_planes, mid_planes), nn.ReLU(inplace=True),
+                         conv(mid_planes, out_planes))
+
+
+class HyperDecoder(_Stack):
+    def __init__(self, in_planes=192, mid_planes=192, out_planes=192):
+        super().__init__(deconv(in_planes, mid_planes), nn.ReLU(inplace=True), deconv(mid_planes, mid_planes), nn.ReLU(inplace=True),
+                         deconv(mid_planes, out_planes))
+
+
+class HyperDecoderWithQReLU(nn.Module):
+    def __init__(self, in_planes=192, mid_planes=192, out_planes=192):
+        super().__init__()
+        self.deconv1 = deconv(in_planes, mid_planes)
+        self.qrelu1 = QReLU(8, 100)
+        self.deconv2 = deconv(mid_planes, mid_planes)
+        self.qrelu2 = QReLU(8, 100)
+        self.deconv3 = deconv(mid_planes, out_planes)
+        self.qrelu3 = QReLU(8, 100)
+
+    def forward(self, x):
+        return self.qrelu3(self.deconv3(self.qrelu2(self.deconv2(self.qrelu1(self.deconv1(x))))))
+
+
+class Hyperprior(CompressionModel):
+    """mean-scale hyperprior of one latent: y -> (y_hat, {"y", "z"} likelihoods); compress / decompress on the host rANS coder"""
+
+    def __init__(self, planes=192, mid_planes=192):
+        super().__init__(entropy_bottleneck_channels=mid_planes)
+        self.hyper_encoder = HyperEncoder(planes, mid_planes, planes)
+        self.hyper_decoder_mean = HyperDecoder(planes, mid_planes, planes)
+        self.hyper_decoder_scale = HyperDecoderWithQReLU(planes, mid_planes, planes)
+        self.gaussian_conditional = GaussianConditional(None)
+
+    def forward(self, y):
+        z = self.hyper_encoder(y)
+        z_hat, z_likelihoods = self.entropy_bottleneck(z)
+        scales = self.hyper_decoder_scale(z_hat)
+        means = self.hyper_decoder_mean(z_hat)
+        # (likelihood of the noisy / dequantised y, ste_round(y - means) + means) in one kernel
+        y_likelihoods, y_hat = self.gaussian_conditional.likelihood_and_ste(y, scales, means)
+        return y_hat, {"y": y_likelihoods, "z": z_likelihoods}
+
+    @torch.no_grad()
+    def compress(self, y):
+        z = self.hyper_encoder(y)
+        z_strings = self.entropy_bottleneck.compress(z)
+        z_hat = self.entropy_bottleneck.decompress(z_strings, z.size()[-2:])
+        scales = self.hyper_decoder_scale(z_hat)
+        means = self.hyper_decoder_mean(z_hat)
+        gc = self.gaussian_conditional
+        cdf, ln, off = gc.host_tables()
+        sym, idx, _ = gc.quantize_and_index(y, means, scales)
+        y_hat = sym.to(torch.float32) + means   # formed as decompress forms it: the two sides run one chain
+        sym = sym.contiguous().cpu().numpy()   # [N, C, H, W]: the element order of CompressAI's symbols[i].reshape(-1)
+        idx = idx.contiguous().cpu().numpy()
+        y_strings = [ans.encode(sym[i].reshape(-1), idx[i].reshape(-1), cdf, ln, off) for i in range(sym.shape[0])]
+        return y_hat, {"strings": [y_strings, z_strings], "shape": z.size()[-2:]}
+
+    @torch.no_grad()
+    def decompress(self, strings, shape):
+        assert isinstance(strings, (list, tuple)) and len(strings) == 2
+        z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
+        scales = self.hyper_decoder_scale(z_hat)
+        means = self.hyper_decoder_mean(z_hat)
+        gc = self.gaussian_conditional
+        cdf, ln, off = gc.host_tables()
+        idx = gc.build_indexes(scales).contiguous().cpu().numpy()
+        out = np.empty(idx.shape, dtype=np.float32)
+        for i, s in enumerate(strings[0]):
+            out[i] = ans.decode(s, idx[i].reshape(-1), cdf, ln, off).reshape(idx.shape[1:])
+        return torch.from_numpy(out).to(z_hat.device).contiguous(memory_format=CL) + means
+
+
+class ScaleSpaceFlow(CompressionModel):
+    """ScaleSpaceFlow(num_levels=5, sigma0=1.5, scale_field_shift=1.0): ``scale_field_shift`` is stored and unused, as in CompressAI.
+    mid_planes / planes (multiples of 4; 128 / 192 in the published model) size the sub-networks."""
+
+    def __init__(self, num_levels=5, sigma0=1.5, scale_field_shift=1.0, mid_planes=128, planes=192):
+        super().__init__()
+        if int(num_levels) != num_levels or num_levels < 1:
+            raise ValueError(f"ScaleSpaceFlow: num_levels must be an integer >= 1 (got num_levels={num_levels})")
+        if num_levels > 8:
+            raise ValueError(f"ScaleSpaceFlow: num_levels must be at most 8, since frames are multiples of 128 (got num_levels={num_levels})")
+        gaussian_taps(sigma0)   # (refuses sigma0 <= 0, and a sigma0 whose window the kernels do not take, by name)
+        if mid_planes % 4 or planes % 4 or mid_planes < 4 or planes < 4:
+            raise ValueError(f"ScaleSpaceFlow: mid_planes and planes must be positive multiples of 4 (the kernels' aligned path); got "
+                             f"mid_planes={mid_planes}, planes={planes}")
+        self.img_encoder = Encoder(3, mid_planes, planes)
+        self.img_decoder = Decoder(3, planes, mid_planes)
+        self.img_hyperprior = Hyperprior(planes, planes)
+        self.res_encoder = Encoder(3, mid_planes, planes, input_grad=True)
+        self.res_decoder = Decoder(3, 2 * planes, mid_planes)
+        self.res_hyperprior = Hyperprior(planes, planes)
+        self.motion_encoder = Encoder(2 * 3, mid_planes, planes, input_grad=True)
+        self.motion_decoder = Decoder(2 + 1, planes, mid_planes)
+        self.motion_hyperprior = Hyperprior(planes, planes)
+        self.sigma0 = float(sigma0)
+        self.num_levels = int(num_levels)
+        self.scale_field_shift = scale_field_shift
+
+    # ---- argument checks ----
+    @staticmethod
+    def _prep(frames):
+        if not isinstance(frames, (list, tuple)):
+            raise ValueError(f"ScaleSpaceFlow: frames must be a list of [N, 3, H, W] tensors (got {type(frames).__name__})")
+        if len(frames) < 1:
+            raise ValueError("ScaleSpaceFlow: fewer than one frame (frames is empty)")
+        shape = tuple(frames[0].shape)
+        for i, f in enumerate(frames):
+            if tuple(f.shape) != shape:
+                raise ValueError(f"ScaleSpaceFlow: frames of differing shapes (frame 0 is {shape}, frame {i} is {tuple(f.shape)})")
+        if len(shape) != 4 or shape[1] != 3 or shape[2] % 128 or shape[3] % 128 or shape[2] < 128 or shape[3] < 128:
+            raise ValueError(f"ScaleSpaceFlow: frames must be [N, 3, H, W] with H and W multiples of 128 (got {shape})")
+        for f in frames:
+            ops._require_gpu(f, "ScaleSpaceFlow")
+        return [f.detach().contiguous(memory_format=CL) for f in frames]   # (the frames take no gradient)
+
+    def _predict(self, x_ref, y_m_hat):
+        """the motion-compensated prediction of a frame from the reference reconstruction and the decoded motion latent"""
+        info = self.motion_decoder(y_m_hat)   # channels 0-1: the flow, channel 2: the scale field
+        volume = scale_space_volume(x_ref, self.sigma0, self.num_levels)
+        return scale_space_warp(volume, info[:, :2], info[:, 2:3])
+
+    # ---- training / evaluation forward ----
+    def forward(self, frames):
+        frames = self._prep(frames)
+        x_hat, lik = self.forward_keyframe(frames[0])
+        recs, liks = [x_hat], [lik]
+        x_ref = x_hat.detach()
+        for x in frames[1:]:
+            x_ref, lik = self.forward_inter(x, x_ref)
+            recs.append(x_ref)
+            liks.append(lik)
+        return {"x_hat": recs, "likelihoods": liks}
+
+    def forward_keyframe(self, x):
+        y_hat, lik = self.img_hyperprior(self.img_encoder(x))
+        return self.img_decoder(y_hat), {"keyframe": lik}
+
+    def forward_inter(self, x_cur, x_ref):
+        y_m_hat, m_lik = self.motion_hyperprior(self.motion_encoder(torch.cat((x_cur, x_ref), dim=1)))
+        x_pred = self._predict(x_ref, y_m_hat)
+        y_r_hat, r_lik = self.res_hyperprior(self.res_encoder(x_cur - x_pred))
+        x_rec = x_pred + self.res_decoder(torch.cat((y_r_hat, y_m_hat), dim=1))
+        return x_rec, {"motion": m_lik, "residual": r_lik}
+
+    # ---- codec ----
+    @torch.no_grad()
+    def compress(self, frames):
+        """-> (frame_strings, shape_infos): the keyframe's [y_strings, z_strings] and z size, then per frame
+        {"motion": [y, z], "residual": [y, z]} and {"motion": z size, "residual": z size}"""
+        frames = self._prep(frames)
+        y_hat, item = self.img_hyperprior.compress(self.img_encoder(frames[0]))
+        x_ref = self.img_decoder(y_hat)
+        frame_strings, shape_infos = [item["strings"]], [item["shape"]]
+        for x in frames[1:]:
+            y_m_hat, m = self.motion_hyperprior.compress(self.motion_encoder(torch.cat((x, x_ref), dim=1)))
+            x_pred = self._predict(x_ref, y_m_hat)
+            y_r_hat, r = self.res_hyperprior.compress(self.res_encoder(x - x_pred))
+            x_ref = x_pred + self.res_decoder(torch.cat((y_r_hat, y_m_hat), dim=1))
+            frame_strings.append({"motion": m["strings"], "residual": r["strings"]})
+            shape_infos.append({"motion": m["shape"], "residual": r["shape"]})
+        return frame_strings, shape_infos
+
+    @torch.no_grad()
+    def decompress(self, frame_strings, shape_infos):
+        """-> the list of reconstructions, unclamped as forward returns them"""
+        if len(frame_strings) < 1 or len(frame_strings) != len(shape_infos):
+            raise ValueError(f"ScaleSpaceFlow.decompress: {len(frame_strings)} frame strings for {len(shape_infos)} shape infos (at least one of each)")
+        x_ref = self.img_decoder(self.img_hyperprior.decompress(frame_strings[0], shape_infos[0]))
+        recs = [x_ref]
+        for strings, shapes in zip(frame_strings[1:], shape_infos[1:]):
+            y_m_hat = self.motion_hyperprior.decompress(strings["motion"], shapes["motion"])
+            x_pred = self._predict(x_ref, y_m_hat)
+            y_r_hat = self.res_hyperprior.decompress(strings["residual"], shapes["residual"])
+            x_ref = x_pred + self.res_decoder(torch.cat((y_r_hat, y_m_hat), dim=1))
+            recs.append(x_ref)
+        return recs
+
+    def load_state_dict(self, state_dict, strict=True):
+        for name, m in self.named_modules():
+            if isinstance(m, EntropyBottleneck):
+                _resize_registered_buffers(m, name, ["_quantized_cdf", "_offset", "_cdf_length"], state_dict)
+            if isinstance(m, GaussianConditional):
+                _resize_registered_buffers(m, name, ["_quantized_cdf", "_offset", "_cdf_length", "scale_table"], state_dict)
+        return nn.Module.load_state_dict(self, state_dict, strict=strict)

@@ -998,6 +998,37 @@ int clc_rans_lanes_encode_list(const int32_t* symbols, const int32_t* indexes, l
                                int W, const int32_t* cdfs, int cdf_stride, int n_rows, const int32_t* cdf_sizes, const int32_t* offsets,
                                uint32_t* out, const int32_t* regions /* [B][W][2] */, int32_t* result /* [B][W][2] */, clc_stream_t stream);
 
+/* ---- scale-space flow (ssf2020): the scale-space volume of a frame and the trilinear warp through it (csrc/scale_space.hip) ---- *
+ * Frames x / dx / y / dy are pixel-major [N, H, W] with 3 channels at a leading dimension (>= 3); flow [N, H, W] x 2 (channel 0
+ * along the width, 1 along the height, normalised coordinates) and scale [N, H, W] x 1 (the normalised depth coordinate) likewise,
+ * so both may be channel slices of one 3-channel map.  THE VOLUME is [N][H][W][D][4] f32, D = levels + 1: depth and channel
+ * innermost, three channels padded to a 16-byte voxel (lane 3 is written 0); 16-byte aligned.
+ * Volume: V0 = x; V1 = blur(x); per further level a 2x2 average pool, a blur, and i bilinear x2 upsamplings (align_corners=False)
+ * back to H x W.  blur = the separable filter `taps` with replicate padding.  H and W must be divisible by 2^(levels - 1).
+ * clc_ss_volume_bwd is the adjoint, dvol -> dx, in gather form (one owner per element, fixed order).
+ * Warp: F.grid_sample(volume, identity grid + flow | scale, padding_mode="border", align_corners=False) and its three gradients;
+ * a NULL gradient output is not computed.  dvol is a deterministic scatter (no float atomics; bit-identical run to run and for an
+ * image alone or in a batch): one stable radix sort of (lower-corner voxel, pixel id) pairs, then one gathering thread per voxel;
+ * total work O(N H W), longest serial chain 8 x the largest bucket.  ws (256-byte aligned) is needed only when dvol is wanted.
+ * Stream-ordered launches and one hipMemsetAsync; nothing is allocated. */
+#define CLC_SS_MAX_TAPS 33
+#define CLC_SS_MAX_LEVELS 12
+typedef struct {
+  int N, H, W;
+  int levels;                    /* L >= 1; D = L + 1 */
+  int ntaps;                     /* odd, 1 .. CLC_SS_MAX_TAPS */
+  float taps[CLC_SS_MAX_TAPS];   /* taps [0, ntaps), applied along both axes */
+} clc_ss_desc;
+size_t clc_ss_volume_workspace_bytes(const clc_ss_desc* d);   /* 0 and clc_last_error on a refused descriptor */
+int clc_ss_volume_fwd(const clc_ss_desc* d, const float* x, int ldx, float* vol, void* ws, size_t ws_bytes, clc_stream_t stream);
+int clc_ss_volume_bwd(const clc_ss_desc* d, const float* dvol, float* dx, int lddx, void* ws, size_t ws_bytes, clc_stream_t stream);
+int clc_ss_warp_fwd(const float* vol, int N, int H, int W, int D, const float* flow, int ldf, const float* scale, int lds, float* y, int ldy,
+                    clc_stream_t stream);
+size_t clc_ss_warp_bwd_workspace_bytes(int N, int H, int W, int D);
+int clc_ss_warp_bwd(const float* vol, int N, int H, int W, int D, const float* flow, int ldf, const float* scale, int lds, const float* dy, int lddy,
+                    float* dflow /* or NULL */, int lddf, float* dscale /* or NULL */, int ldds, float* dvol /* or NULL */, void* ws, size_t ws_bytes,
+                    clc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
