@@ -16,12 +16,12 @@
 //
 // Work per step is tiny (M = 192: 7.5 MB of filters, a few hundred rows at most): launch- and latency-bound, so plain f32 VALU FMAs,
 // no LDS, no barrier, nothing that waits on another workgroup.  Stream-ordered, allocation-free, graph-capturable.
-#include "common.h"
+#include "coder_device.h"
 
 namespace {
+using namespace coder;
 
 constexpr int kRows = 8;   // rows that share one wave's filter registers
-constexpr float kScaleBound = 0.11f;
 constexpr long kMaxRowBlocksY = 32;   // grid.y: beyond 256 rows a workgroup walks several row blocks
 
 struct ArLinArgs {
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(256) void ar_linear_kernel(const ArLinArgs a) {
 }
 
 // mode 0 (encode): symbols / indexes at the pixel's raster place of [B][H*W][M], y_hat into the map; mode 1 (decode): indexes to the
-// dense [rows][M] buffer.  The expressions are those of quantize_build_indexes_kernel (entropy.hip), operation for operation.
+// dense [rows][M] buffer.  The index is quantize_build_indexes_kernel's (entropy.hip): coder::scale_index_linear.
 // y and y_hat may be the same map (each element is read and then written by one thread).
 __global__ __launch_bounds__(256) void ar_finish_kernel(const float* __restrict__ gp, int ldg, int M, const int32_t* __restrict__ pix, int P, int H, int W,
                                                       const float* __restrict__ table, int n_scales, const float* y, int ldy, float* y_hat, int ldh,
@@ -135,17 +135,14 @@ __global__ __launch_bounds__(256) void ar_finish_kernel(const float* __restrict_
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const long r = i / M;
     const int c = (int)(i - r * M);
-    const float sg = fmaxf(gp[r * ldg + c], kScaleBound);
-    int idx = n_scales - 1;
-    for (int k = 0; k < n_scales - 1; ++k) idx -= (sg <= tb[k]) ? 1 : 0;
+    const int idx = scale_index_linear(fmaxf(gp[r * ldg + c], kScaleBound), tb, n_scales);
     if (mode == 1) {
       indexes[i] = idx;
       continue;
     }
     const int b = (int)(r / P), p = (int)(r - (long)b * P);
-    const int h = pix[2 * p], w = pix[2 * p + 1];
-    if (h < 0 || h >= H || w < 0 || w >= W) continue;
-    const long px = ((long)b * H + h) * W + w;
+    const long px = pixel_of(pix, p, b, H, W);
+    if (px < 0) continue;
     const float m = gp[r * ldg + M + c];
     const float q = rintf(y[px * ldy + c] - m);
     symbols[px * M + c] = (int32_t)q;
@@ -161,10 +158,10 @@ __global__ __launch_bounds__(256) void ar_commit_kernel(const int32_t* __restric
     const long r = i / M;
     const int c = (int)(i - r * M);
     const int b = (int)(r / P), p = (int)(r - (long)b * P);
-    const int h = pix[2 * p], w = pix[2 * p + 1];
-    if (h < 0 || h >= H || w < 0 || w >= W) continue;
+    const long px = pixel_of(pix, p, b, H, W);
+    if (px < 0) continue;
     const float q = (float)symbols[i];   // the encoder's rintf(y - m): an integer-valued float either way
-    y_hat[(((long)b * H + h) * W + w) * ldh + c] = q + gp[r * ldg + M + c];
+    y_hat[px * ldh + c] = q + gp[r * ldg + M + c];
   }
 }
 

@@ -9,16 +9,12 @@
 // Algorithmic bytes per latent element (forward): read y, mu, scale (+noise) = 12-16 B,
 // write lik, y_hat = 8 B.  The rate sum is a wave shuffle reduction -> one partial per
 // workgroup -> fixed-order final sum (no float atomics).
-#include "common.h"
+#include "coder_device.h"
 
 namespace {
+using namespace coder;
 
-constexpr float kScaleBound = 0.11f;
 constexpr float kLikBound = 1e-9f;
-constexpr float kInvSqrt2 = 0.70710678118654752440f;
-constexpr float kInvSqrt2Pi = 0.39894228040143267794f;
-
-__device__ __forceinline__ float std_cum(float x) { return 0.5f * erfcf(-kInvSqrt2 * x); }
 
 __global__ __launch_bounds__(256) void gauss_lik_fwd_kernel(const float* __restrict__ y, int ldy, const float* __restrict__ mu, int ldmu,
                                                           const float* __restrict__ scale, int ldsc, const float* __restrict__ noise, int ldn,
@@ -97,9 +93,7 @@ __global__ __launch_bounds__(256) void quantize_build_indexes_kernel(const float
     const int c = (int)(i - r * C);
     const float m = mu[r * ldmu + c];
     const float q = rintf(y[r * ldy + c] - m);
-    const float sg = fmaxf(scale[r * ldsc + c], kScaleBound);
-    int idx = n_scales - 1;
-    for (int k = 0; k < n_scales - 1; ++k) idx -= (sg <= tb[k]) ? 1 : 0;
+    const int idx = scale_index_linear(fmaxf(scale[r * ldsc + c], kScaleBound), tb, n_scales);
     // symbols/indexes are emitted in the coder's order: element (row r, channel c) of an NHWC slice
     // belongs at NCHW position handled by the caller's (rows,C) -> stream permutation
     symbols[i] = (int32_t)q;

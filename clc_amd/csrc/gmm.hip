@@ -15,20 +15,16 @@
 // pixel (16-byte loads and stores) when C % 4 == 0 and everything is aligned, else one channel.  The coder kernels own one element per
 // thread and scan its row with scalars, storing as they go: no per-thread array indexed at run time, no scratch.  All stream-ordered,
 // allocation- and sync-free, graph-capturable; no LDS, no barrier, nothing waits on another workgroup.
-#include "common.h"
+#include "coder_device.h"
 
 namespace {
+using namespace coder;
 
-constexpr float kScaleBound = 0.11f;
 constexpr float kLikBound = 1e-9f;
-constexpr float kInvSqrt2 = 0.70710678118654752440f;
-constexpr float kInvSqrt2Pi = 0.39894228040143267794f;
 constexpr int kR = CLC_GMM_R, kL = 2 * CLC_GMM_R + 1, kStride = CLC_GMM_ROW_STRIDE;
 constexpr float kS = (float)(65535 - kL);
 constexpr float kCtrBound = 1048576.f;    // 2^20: centre - R + j - 1/2 stays exact in f32, and every int32 expression stays far from overflow
 constexpr float kSymBound = 16777216.f;   // 2^24: the escape payload 2 |sym - offset| stays below 2^27 (8 nibbles carry 32 bits)
-
-__device__ __forceinline__ float std_cum(float x) { return 0.5f * erfcf(-kInvSqrt2 * x); }
 
 template <int V>
 __device__ __forceinline__ void ldv(const float* p, float (&o)[V]) {
@@ -210,9 +206,8 @@ __global__ __launch_bounds__(256) void gmm_finish_kernel(const GmmFinArgs a) {
     int value = 0;   // encode: the symbol's place in the row; < 0 or >= kL: escaped
     if (a.mode == CLC_AR_ENCODE) {
       const int b = (int)(r / a.P), p = (int)(r - (long)b * a.P);
-      const int h = a.pix[2 * p], w = a.pix[2 * p + 1];
-      if (h < 0 || h >= a.H || w < 0 || w >= a.W) continue;   // a pixel outside the map is neither read nor written
-      const long px = ((long)b * a.H + h) * a.W + w;
+      const long px = pixel_of(a.pix, p, b, a.H, a.W);
+      if (px < 0) continue;   // a pixel outside the map is neither read nor written
       const int sym = (int)clamp_fixed(rintf(a.y[px * a.ldy + c]), kSymBound);
       a.y_hat[px * a.ldh + c] = (float)sym;
       value = sym - offset;
@@ -261,9 +256,9 @@ __global__ __launch_bounds__(256) void gmm_commit_kernel(const int32_t* __restri
     const long r = i / N;
     const int c = (int)(i - r * N);
     const int b = (int)(r / P), p = (int)(r - (long)b * P);
-    const int h = pix[2 * p], w = pix[2 * p + 1];
-    if (h < 0 || h >= H || w < 0 || w >= W) continue;
-    y_hat[(((long)b * H + h) * W + w) * ldh + c] = (float)symbols[i];
+    const long px = pixel_of(pix, p, b, H, W);
+    if (px < 0) continue;
+    y_hat[px * ldh + c] = (float)symbols[i];
   }
 }
 
@@ -283,12 +278,12 @@ struct GmmDecArgs {
 };
 
 struct SubStream {
-  const uint32_t* w;   // the sub-stream's first word
-  uint32_t count, pos;
+  WordSpan span;   // the sub-stream's words
+  uint32_t pos;
   uint64_t x;
   __device__ __forceinline__ void renorm() {   // rans_host.cpp: one word when x < 2^31, zeros at or past the end
     if (x < (1ull << 31)) {
-      const uint32_t v = pos < count ? w[pos] : 0u;
+      const uint32_t v = span.word(pos);
       ++pos;
       x = (x << 32) | v;
     }
@@ -307,19 +302,17 @@ __global__ __launch_bounds__(256) void gmm_decode_kernel(const GmmDecArgs a) {
   const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);   // (b, s); the last workgroup's spare waves leave
   if (wid >= a.B * a.S) return;
   const int b = wid / a.S, s = wid - b * a.S;
-  const int first = a.spans[2 * wid], count = a.spans[2 * wid + 1];
   uint32_t* st = a.state + 4 * (long)wid;
   SubStream d;
-  d.w = a.words + (first > 0 ? first : 0);
-  d.count = (first >= 0 && count > 0) ? (uint32_t)count : 0u;
+  d.span.open(a.words, a.spans, wid);
   d.x = (uint64_t)st[0] | ((uint64_t)st[1] << 32);
   d.pos = st[2];
 #pragma unroll 1
   for (int p = 0; p < a.P; ++p) {
-    const int h = a.pix[2 * p], w = a.pix[2 * p + 1];
-    if (h < 0 || h >= a.H || w < 0 || w >= a.W) continue;   // neither read nor written, consumes nothing
+    const long px = pixel_of(a.pix, p, b, a.H, a.W);
+    if (px < 0) continue;   // neither read nor written, consumes nothing
     const float* grow = a.gp + ((long)b * a.P + p) * a.ldg;
-    float* out = a.y_hat + (((long)b * a.H + h) * a.W + w) * a.ldh;
+    float* out = a.y_hat + px * a.ldh;
 #pragma unroll 1
     for (int c = s; c < a.N; c += a.S) {
       float pi[K], mu[K], sg[K];

@@ -10,14 +10,20 @@
 // No atomics, no wave waits on another; every loop is bounded by a constant or by the symbol count.  The two kernels of the table-coded
 // stream use no LDS and no barrier; rans_lanes_decode_gauss_kernel keeps the scale table in LDS (one barrier before its first round).
 //
+// The decoder has one owner, coder::LaneCoder (coder_device.h): the open and write-back of span and state, the ballot-and-popcount renorm,
+// a round's symbol search and state update, the escape.  Both decode kernels run their rounds through it and own what surrounds a round:
+// which row it decodes from (fetched one round ahead of the state; read, or formed from the scale) and where the value goes.
+//
 // Two kernels are templates over the one thing their entries differ in.  The encoder reads its segment lengths from a by-value struct
 // (clc_rans_lanes_encode, P <= 32) or from device memory (clc_rans_lanes_encode_list, any P).  The Gaussian step lands a (row, channel)
 // in a dense [rows][ldh] map (clc_rans_lanes_decode_gauss) or, through a pixel list, in an NHWC latent (clc_ar_lanes_decode).
-#include "common.h"
+#include "coder_device.h"
 
 namespace {
-constexpr int kLanes = 64;
-constexpr uint64_t kL = 1ull << 31;
+using namespace coder;
+constexpr int kLanes = LaneCoder::kLanes;
+constexpr uint64_t kL = LaneCoder::kL;
+constexpr int kStateWords = LaneCoder::kStateWords;
 
 struct LanesTables {
   const int32_t* cdfs; int cdf_stride, n_rows;
@@ -35,34 +41,17 @@ struct LanesDecArgs {
   int32_t* symbols; long ld_sym;
 };
 
-constexpr int kStateWords = 2 * kLanes + 2;
-
 __device__ __forceinline__ int clamp_int(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 __global__ __launch_bounds__(64) void rans_lanes_decode_kernel(const LanesDecArgs a) {
   const int lane = threadIdx.x;
   const int wid = blockIdx.x;   // (b, w)
   const int b = wid / a.W, w = wid - b * a.W;
-  const int first = a.spans[2 * wid], cnt = a.spans[2 * wid + 1];
-  const uint32_t* wp = a.words + (first > 0 ? first : 0);
-  const uint32_t count = (first >= 0 && cnt > 0) ? (uint32_t)cnt : 0u;   // (a negative first or count reads nothing)
-  uint32_t* st = a.state + (long)kStateWords * wid;
-  uint64_t x = (uint64_t)st[2 * lane] | ((uint64_t)st[2 * lane + 1] << 32);
-  uint32_t pos = st[2 * kLanes];
+  LaneCoder d;
+  d.open(a.words, a.spans, a.state, wid, lane);
   const int32_t* idx = a.indexes + (long)b * a.ld_idx;
   int32_t* out = a.symbols + (long)b * a.ld_sym;
-  const unsigned long long below = (1ull << lane) - 1ull;
   const int chunks = (a.n + kLanes - 1) / kLanes;
-  // renorm of the lanes that `need` it: they take the next words in ascending lane order; a word at or past the count is zero
-  auto take = [&](bool need) {
-    const unsigned long long m = __ballot(need);
-    if (need) {
-      const uint32_t i = pos + (uint32_t)__popcll(m & below);
-      const uint32_t v = i < count ? wp[i] : 0u;
-      x = (x << 32) | v;
-    }
-    pos += (uint32_t)__popcll(m);
-  };
   // the next round's row is known before this round's state is: fetched one round ahead
   int ci_next = 0, size_next = 2, off_next = 0;
   auto fetch = [&](int q) {
@@ -80,48 +69,10 @@ __global__ __launch_bounds__(64) void rans_lanes_decode_kernel(const LanesDecArg
     const bool active = j < a.n;
     const int ci = ci_next, size = size_next, off = off_next;
     fetch(q + a.W);
-    const int32_t* cdf = a.t.cdfs + (long)ci * a.t.cdf_stride;
-    const int maxv = size - 2;
-    // sub-step 0, the symbol: the largest s <= max_value with cdf[s] <= cf
-    int s = 0;
-    if (active) {
-      const uint32_t cf = (uint32_t)x & 0xFFFFu;
-      int lo = 0, hi = maxv;
-#pragma unroll 1
-      for (int it = 0; it < 32 && lo < hi; ++it) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((uint32_t)cdf[mid] <= cf) lo = mid; else hi = mid - 1;
-      }
-      s = lo;
-      const uint32_t start = (uint32_t)cdf[s], freq = (uint32_t)(cdf[s + 1] - cdf[s]);
-      x = (uint64_t)freq * (x >> 16) + cf - start;
-    }
-    take(active && x < kL);
-    const bool esc = active && s == maxv;
-    uint32_t value = (uint32_t)s;
-    if (__ballot(esc)) {   // the tail's escape: sub-steps 1 .. — the count (one nibble; a second after a 15), then the payload nibbles
-      int nb = 0, base = 2;
-      uint32_t raw = 0;
-#pragma unroll 1
-      for (int t = 1; t < 19; ++t) {
-        const bool cnt_op = esc && (t == 1 || (t == 2 && nb == 15));
-        const int k = t - base;
-        const bool pay_op = esc && !cnt_op && t >= 2 && k < (nb < 16 ? nb : 16);
-        const bool op = cnt_op || pay_op;
-        if (!__ballot(op)) break;
-        const uint32_t v = (uint32_t)x & 15u;
-        if (op) x >>= 4;
-        take(op && x < kL);
-        if (cnt_op) { nb += (int)v; if (t == 2) base = 3; }
-        if (pay_op && k < 8) raw |= v << (4 * k);
-      }
-      if (esc) value = (raw & 1u) ? ~(raw >> 1) : (raw >> 1) + (uint32_t)maxv;   // (-v - 1 == ~v)
-    }
+    const uint32_t value = d.round(a.t.cdfs + (long)ci * a.t.cdf_stride, size - 2, active);
     if (active) out[j] = (int32_t)(value + (uint32_t)off);
   }
-  st[2 * lane] = (uint32_t)x;
-  st[2 * lane + 1] = (uint32_t)(x >> 32);
-  if (lane == 0) st[2 * kLanes] = pos;
+  d.close(lane);
 }
 
 struct LanesSegList { int P; const int32_t* n; };   // clc_rans_lanes_segments with the lengths in device memory
@@ -228,13 +179,11 @@ __global__ __launch_bounds__(64) void rans_lanes_encode_kernel(const LanesEncArg
 
 // ---- the slice step of the Gaussian-conditional models: index, decode, de-quantise in one launch ----
 // rans_lanes_decode_kernel with the row index formed here (quantize_build_indexes_kernel's, entropy.hip) and the symbol leaving as
-// y_hat = (float)symbol + mu.  The coder's part is that kernel's, statement for statement: it is repeated, not shared, so that the
-// kernel of the table-coded stream keeps its code.
+// y_hat = (float)symbol + mu.
 //
 // WHERE a (row, channel) lands is the template's parameter.  LanesDenseRows: at r * ldh + c, the slice models' map.  LanesPixelList: the
 // rows of an image are the pixels of a step of the context model's schedule, row p of image b lands at pixel pix[p] = (h, w) of the
-// NHWC latent, ((b H + h) W + w) ldh + c (ar_commit_kernel's expression), and a pair outside the map is decoded and not written.
-constexpr float kScaleBound = 0.11f;
+// NHWC latent, pixel_of(...) * ldh + c (ar_commit_kernel's place), and a pair outside the map is decoded and not written.
 constexpr int kMaxScales = 256;
 
 struct LanesGaussArgs {
@@ -259,10 +208,8 @@ struct LanesPixelList {
   static constexpr bool kEveryRow = false;
   const int32_t* pix;   // [P][2]: (h, w) of the image's row p
   int H, W;
-  __device__ __forceinline__ long at(int b, long, int p, int c, long ldh) const {   // -1: outside the map
-    const int h = pix[2 * p], w = pix[2 * p + 1];
-    if (h < 0 || h >= H || w < 0 || w >= W) return -1;
-    return (((long)b * H + h) * W + w) * ldh + c;
+  __device__ __forceinline__ long at(int b, long, int p, int c, long ldh) const {   // negative: outside the map (c - ldh, and c < C <= ldh)
+    return pixel_of(pix, p, b, H, W) * ldh + c;
   }
 };
 
@@ -275,24 +222,10 @@ __global__ __launch_bounds__(64) void rans_lanes_decode_gauss_kernel(const Lanes
   __syncthreads();
   const int wid = blockIdx.x;   // (b, w)
   const int b = wid / a.W, w = wid - b * a.W;
-  const int first = a.spans[2 * wid], cnt = a.spans[2 * wid + 1];
-  const uint32_t* wp = a.words + (first > 0 ? first : 0);
-  const uint32_t count = (first >= 0 && cnt > 0) ? (uint32_t)cnt : 0u;   // (a negative first or count reads nothing)
-  uint32_t* st = a.state + (long)kStateWords * wid;
-  uint64_t x = (uint64_t)st[2 * lane] | ((uint64_t)st[2 * lane + 1] << 32);
-  uint32_t pos = st[2 * kLanes];
+  LaneCoder d;
+  d.open(a.words, a.spans, a.state, wid, lane);
   const long row0 = (long)b * (a.n / a.C);   // the image's first row of the [rows][C] maps
-  const unsigned long long below = (1ull << lane) - 1ull;
   const int chunks = (a.n + kLanes - 1) / kLanes;
-  auto take = [&](bool need) {
-    const unsigned long long m = __ballot(need);
-    if (need) {
-      const uint32_t i = pos + (uint32_t)__popcll(m & below);
-      const uint32_t v = i < count ? wp[i] : 0u;
-      x = (x << 32) | v;
-    }
-    pos += (uint32_t)__popcll(m);
-  };
   // A round's row does not depend on the coder state, but finding it is a chain of its own — the scale's load, a search of up to eight
   // dependent LDS reads, the loads of cdf size and offset — and one wave alone hides none of it behind anything.  So the wave's rounds
   // run in GROUPS of kGroup: at a group's last round the indexes of the next group's rounds are searched together (kGroup independent
@@ -377,51 +310,14 @@ __global__ __launch_bounds__(64) void rans_lanes_decode_gauss_kernel(const Lanes
       load_scales(q + a.W + kGroup * a.W);
     }
     fetch_row(q + a.W, (int)((pack >> (8 * g)) & 255u));
-    const int32_t* cdf = a.t.cdfs + (long)ci * a.t.cdf_stride;
-    const int maxv = size - 2;
-    int s = 0;
-    if (active) {
-      const uint32_t cf = (uint32_t)x & 0xFFFFu;
-      int lo = 0, hi = maxv;
-#pragma unroll 1
-      for (int it = 0; it < 32 && lo < hi; ++it) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((uint32_t)cdf[mid] <= cf) lo = mid; else hi = mid - 1;
-      }
-      s = lo;
-      const uint32_t start = (uint32_t)cdf[s], freq = (uint32_t)(cdf[s + 1] - cdf[s]);
-      x = (uint64_t)freq * (x >> 16) + cf - start;
-    }
-    take(active && x < kL);
-    const bool esc = active && s == maxv;
-    uint32_t value = (uint32_t)s;
-    if (__ballot(esc)) {
-      int nb = 0, base = 2;
-      uint32_t raw = 0;
-#pragma unroll 1
-      for (int t = 1; t < 19; ++t) {
-        const bool cnt_op = esc && (t == 1 || (t == 2 && nb == 15));
-        const int k = t - base;
-        const bool pay_op = esc && !cnt_op && t >= 2 && k < (nb < 16 ? nb : 16);
-        const bool op = cnt_op || pay_op;
-        if (!__ballot(op)) break;
-        const uint32_t v = (uint32_t)x & 15u;
-        if (op) x >>= 4;
-        take(op && x < kL);
-        if (cnt_op) { nb += (int)v; if (t == 2) base = 3; }
-        if (pay_op && k < 8) raw |= v << (4 * k);
-      }
-      if (esc) value = (raw & 1u) ? ~(raw >> 1) : (raw >> 1) + (uint32_t)maxv;
-    }
+    const uint32_t value = d.round(a.t.cdfs + (long)ci * a.t.cdf_stride, size - 2, active);
     if (active) {
       const int32_t sym = (int32_t)(value + (uint32_t)off);
       if (Landing::kEveryRow || at >= 0) a.y_hat[at] = (float)sym + m_;
       if (a.symbols) a.symbols[(long)b * a.ld_sym + j] = sym;
     }
   }
-  st[2 * lane] = (uint32_t)x;
-  st[2 * lane + 1] = (uint32_t)(x >> 32);
-  if (lane == 0) st[2 * kLanes] = pos;
+  d.close(lane);
 }
 
 // ---- the encoder's wave streams, back to back ----
@@ -465,8 +361,29 @@ __global__ __launch_bounds__(64) void rans_lanes_pack_kernel(const LanesPackArgs
   }
 }
 
-bool lanes_tables_ok(const int32_t* cdfs, int cdf_stride, int n_rows, const int32_t* cdf_sizes, const int32_t* offsets) {
-  return cdfs && cdf_sizes && offsets && cdf_stride >= 2 && n_rows >= 1;
+// what every coder entry checks of its table, its wave count and its grid, under the entry's name `who`
+int lanes_entry_ok(const char* who, const LanesTables& t, int W, int B) {
+  CLC_CHECK(t.cdfs && t.cdf_sizes && t.offsets, "%s: null table pointer", who);
+  CLC_CHECK(t.cdf_stride >= 2 && t.n_rows >= 1, "%s: the table needs cdf_stride >= 2 and n_rows >= 1 (got %d, %d)", who, t.cdf_stride, t.n_rows);
+  CLC_CHECK(W >= 1 && W <= CLC_RANS_LANES_MAX_W, "%s: W must be between 1 and %d waves (got %d)", who, CLC_RANS_LANES_MAX_W, W);
+  CLC_CHECK((long)B * W < (1l << 24), "%s: B * W must be below 2^24", who);
+  return 0;
+}
+
+// the launch of clc_rans_lanes_decode_gauss and clc_ar_lanes_decode, which differ in where a (row, channel) lands
+template <class Landing>
+int launch_decode_gauss(const float* scale, long ldsc, const float* mu, long ldmu, int C, int n, int B, const float* scale_table, int n_scales,
+                        const LanesTables& t, const uint32_t* words, const int32_t* spans, clc_rans_lanes_state* state, int W, float* y_hat, long ldh,
+                        int32_t* symbols, long ld_sym, const Landing& place, hipStream_t st) {
+  LanesGaussArgs a = {};
+  a.scale = scale; a.ldsc = ldsc; a.mu = mu; a.ldmu = ldmu; a.C = C; a.n = n; a.W = W;
+  a.table = scale_table; a.n_scales = n_scales;
+  a.t = t;
+  a.words = words; a.spans = spans; a.state = reinterpret_cast<uint32_t*>(state);
+  a.y_hat = y_hat; a.ldh = ldh; a.symbols = symbols; a.ld_sym = ld_sym;
+  hipLaunchKernelGGL(rans_lanes_decode_gauss_kernel<Landing>, dim3(B * W), dim3(kLanes), 0, st, a, place);
+  CLC_LAUNCH_CHECK();
+  return 0;
 }
 }  // namespace
 
@@ -477,16 +394,14 @@ extern "C" int clc_rans_lanes_decode_step(const int32_t* indexes, long ld_idx, i
                                           clc_rans_lanes_state* state, int W, int32_t* symbols, long ld_sym, clc_stream_t stream) {
   static_assert(sizeof(clc_rans_lanes_state) == 4 * kStateWords, "rans_lanes_decode_kernel: a state is 64 x u64 and (pos, pad)");
   CLC_CHECK(indexes && words && spans && state && symbols, "clc_rans_lanes_decode_step: null pointer");
-  CLC_CHECK(cdfs && cdf_sizes && offsets, "clc_rans_lanes_decode_step: null table pointer");
-  CLC_CHECK(cdf_stride >= 2 && n_rows >= 1, "clc_rans_lanes_decode_step: the table needs cdf_stride >= 2 and n_rows >= 1 (got %d, %d)", cdf_stride, n_rows);
-  CLC_CHECK(W >= 1 && W <= CLC_RANS_LANES_MAX_W, "clc_rans_lanes_decode_step: W must be between 1 and %d waves (got %d)", CLC_RANS_LANES_MAX_W, W);
+  const LanesTables t = {cdfs, cdf_stride, n_rows, cdf_sizes, offsets};
+  if (lanes_entry_ok("clc_rans_lanes_decode_step", t, W, B)) return -1;
   CLC_CHECK(n >= 0 && B > 0, "clc_rans_lanes_decode_step: n must not be negative and B must be positive (got %d, %d)", n, B);
   CLC_CHECK(ld_idx >= n && ld_sym >= n, "clc_rans_lanes_decode_step: ld_idx or ld_sym < n");
-  CLC_CHECK((long)B * W < (1l << 24), "clc_rans_lanes_decode_step: B * W must be below 2^24");
   if (n == 0) return 0;   // an empty segment contributes nothing
   LanesDecArgs a = {};
   a.indexes = indexes; a.ld_idx = ld_idx; a.n = n; a.W = W;
-  a.t = {cdfs, cdf_stride, n_rows, cdf_sizes, offsets};
+  a.t = t;
   a.words = words; a.spans = spans; a.state = reinterpret_cast<uint32_t*>(state); a.symbols = symbols; a.ld_sym = ld_sym;
   hipLaunchKernelGGL(rans_lanes_decode_kernel, dim3(B * W), dim3(kLanes), 0, ST, a);
   CLC_LAUNCH_CHECK();
@@ -497,9 +412,8 @@ extern "C" int clc_rans_lanes_encode(const int32_t* symbols, const int32_t* inde
                                             const int32_t* cdfs, int cdf_stride, int n_rows, const int32_t* cdf_sizes, const int32_t* offsets,
                                             uint32_t* out, const int32_t* regions, int32_t* result, clc_stream_t stream) {
   CLC_CHECK(symbols && indexes && out && regions && result, "clc_rans_lanes_encode: null pointer");
-  CLC_CHECK(cdfs && cdf_sizes && offsets, "clc_rans_lanes_encode: null table pointer");
-  CLC_CHECK(cdf_stride >= 2 && n_rows >= 1, "clc_rans_lanes_encode: the table needs cdf_stride >= 2 and n_rows >= 1 (got %d, %d)", cdf_stride, n_rows);
-  CLC_CHECK(W >= 1 && W <= CLC_RANS_LANES_MAX_W, "clc_rans_lanes_encode: W must be between 1 and %d waves (got %d)", CLC_RANS_LANES_MAX_W, W);
+  const LanesTables t = {cdfs, cdf_stride, n_rows, cdf_sizes, offsets};
+  if (lanes_entry_ok("clc_rans_lanes_encode", t, W, B)) return -1;
   CLC_CHECK(B > 0, "clc_rans_lanes_encode: B must be positive (got %d)", B);
   CLC_CHECK(segs.P >= 0 && segs.P <= CLC_RANS_LANES_MAX_SEGMENTS, "clc_rans_lanes_encode: P must be between 0 and %d segments (got %d)",
             CLC_RANS_LANES_MAX_SEGMENTS, segs.P);
@@ -510,10 +424,9 @@ extern "C" int clc_rans_lanes_encode(const int32_t* symbols, const int32_t* inde
   }
   CLC_CHECK(total < (1l << 27), "clc_rans_lanes_encode: %ld symbols per image; a region's 128 + 10 n words must stay below 2^31", total);
   CLC_CHECK(ld >= total, "clc_rans_lanes_encode: ld < the segments' total (%ld < %ld)", ld, total);
-  CLC_CHECK((long)B * W < (1l << 24), "clc_rans_lanes_encode: B * W must be below 2^24");
   LanesEncArgs<clc_rans_lanes_segments> a = {};
   a.symbols = symbols; a.indexes = indexes; a.ld = ld;
-  a.t = {cdfs, cdf_stride, n_rows, cdf_sizes, offsets};
+  a.t = t;
   a.out = out; a.regions = regions; a.result = result; a.W = W; a.segs = segs;
   hipLaunchKernelGGL(rans_lanes_encode_kernel<clc_rans_lanes_segments>, dim3(B * W), dim3(kLanes), 0, ST, a);
   CLC_LAUNCH_CHECK();
@@ -525,27 +438,17 @@ extern "C" int clc_rans_lanes_decode_gauss(const float* scale, long ldsc, const 
                                            const int32_t* offsets, const uint32_t* words, const int32_t* spans, clc_rans_lanes_state* state, int W,
                                            float* y_hat, long ldh, int32_t* symbols, long ld_sym, clc_stream_t stream) {
   CLC_CHECK(scale && mu && scale_table && words && spans && state && y_hat, "clc_rans_lanes_decode_gauss: null pointer");
-  CLC_CHECK(cdfs && cdf_sizes && offsets, "clc_rans_lanes_decode_gauss: null table pointer");
-  CLC_CHECK(cdf_stride >= 2 && n_rows >= 1, "clc_rans_lanes_decode_gauss: the table needs cdf_stride >= 2 and n_rows >= 1 (got %d, %d)", cdf_stride, n_rows);
+  const LanesTables t = {cdfs, cdf_stride, n_rows, cdf_sizes, offsets};
+  if (lanes_entry_ok("clc_rans_lanes_decode_gauss", t, W, B)) return -1;
   CLC_CHECK(n_scales > 1 && n_scales <= kMaxScales, "clc_rans_lanes_decode_gauss: n_scales must be between 2 and %d (got %d)", kMaxScales, n_scales);
-  CLC_CHECK(W >= 1 && W <= CLC_RANS_LANES_MAX_W, "clc_rans_lanes_decode_gauss: W must be between 1 and %d waves (got %d)", CLC_RANS_LANES_MAX_W, W);
   CLC_CHECK(n >= 0 && B > 0, "clc_rans_lanes_decode_gauss: n must not be negative and B must be positive (got %d, %d)", n, B);
   CLC_CHECK(n < (1 << 30), "clc_rans_lanes_decode_gauss: n must be below 2^30 symbols per image (got %d)", n);
   CLC_CHECK(C > 0 && n % C == 0, "clc_rans_lanes_decode_gauss: n must be whole rows of C > 0 channels (got n = %d, C = %d)", n, C);
   CLC_CHECK(ldsc >= C && ldmu >= C && ldh >= C, "clc_rans_lanes_decode_gauss: ldsc, ldmu or ldh < C");
   CLC_CHECK(!symbols || ld_sym >= n, "clc_rans_lanes_decode_gauss: ld_sym < n");
-  CLC_CHECK((long)B * W < (1l << 24), "clc_rans_lanes_decode_gauss: B * W must be below 2^24");
   if (n == 0) return 0;   // an empty segment contributes nothing
-  LanesGaussArgs a = {};
-  a.scale = scale; a.ldsc = ldsc; a.mu = mu; a.ldmu = ldmu; a.C = C; a.n = n; a.W = W;
-  a.table = scale_table; a.n_scales = n_scales;
-  a.t = {cdfs, cdf_stride, n_rows, cdf_sizes, offsets};
-  a.words = words; a.spans = spans; a.state = reinterpret_cast<uint32_t*>(state);
-  a.y_hat = y_hat; a.ldh = ldh; a.symbols = symbols; a.ld_sym = ld_sym;
-  const LanesDenseRows place = {};
-  hipLaunchKernelGGL(rans_lanes_decode_gauss_kernel<LanesDenseRows>, dim3(B * W), dim3(kLanes), 0, ST, a, place);
-  CLC_LAUNCH_CHECK();
-  return 0;
+  return launch_decode_gauss(scale, ldsc, mu, ldmu, C, n, B, scale_table, n_scales, t, words, spans, state, W, y_hat, ldh, symbols, ld_sym,
+                             LanesDenseRows{}, ST);
 }
 
 extern "C" int clc_ar_lanes_decode(const float* gp, long ldg, int M, const int32_t* pix, int P, int B, int H, int W_map, const float* scale_table,
@@ -553,10 +456,9 @@ extern "C" int clc_ar_lanes_decode(const float* gp, long ldg, int M, const int32
                                    const uint32_t* words, const int32_t* spans, clc_rans_lanes_state* state, int W, float* y_hat, long ldh,
                                    int32_t* symbols, long ld_sym, clc_stream_t stream) {
   CLC_CHECK(gp && scale_table && words && spans && state && y_hat, "clc_ar_lanes_decode: null pointer");
-  CLC_CHECK(cdfs && cdf_sizes && offsets, "clc_ar_lanes_decode: null table pointer");
-  CLC_CHECK(cdf_stride >= 2 && n_rows >= 1, "clc_ar_lanes_decode: the table needs cdf_stride >= 2 and n_rows >= 1 (got %d, %d)", cdf_stride, n_rows);
+  const LanesTables t = {cdfs, cdf_stride, n_rows, cdf_sizes, offsets};
+  if (lanes_entry_ok("clc_ar_lanes_decode", t, W, B)) return -1;
   CLC_CHECK(n_scales > 1 && n_scales <= kMaxScales, "clc_ar_lanes_decode: n_scales must be between 2 and %d (got %d)", kMaxScales, n_scales);
-  CLC_CHECK(W >= 1 && W <= CLC_RANS_LANES_MAX_W, "clc_ar_lanes_decode: W must be between 1 and %d waves (got %d)", CLC_RANS_LANES_MAX_W, W);
   CLC_CHECK(P >= 0 && B > 0 && H > 0 && W_map > 0 && M > 0, "clc_ar_lanes_decode: P must not be negative and B, H, W and M must be positive (got %d, %d, %d, %d, %d)",
             P, B, H, W_map, M);
   CLC_CHECK((long)P * M < (1l << 30), "clc_ar_lanes_decode: n = P * M must be below 2^30 symbols per image (got %ld)", (long)P * M);
@@ -566,35 +468,24 @@ extern "C" int clc_ar_lanes_decode(const float* gp, long ldg, int M, const int32
   CLC_CHECK((long)B * H * W_map < (1l << 31), "clc_ar_lanes_decode: B * H * W must be below 2^31");
   const int n = P * M;
   CLC_CHECK(!symbols || ld_sym >= n, "clc_ar_lanes_decode: ld_sym < n");
-  CLC_CHECK((long)B * W < (1l << 24), "clc_ar_lanes_decode: B * W must be below 2^24");
   if (n == 0) return 0;   // an empty step contributes nothing
-  LanesGaussArgs a = {};
-  a.scale = gp; a.ldsc = ldg; a.mu = gp + M; a.ldmu = ldg; a.C = M; a.n = n; a.W = W;
-  a.table = scale_table; a.n_scales = n_scales;
-  a.t = {cdfs, cdf_stride, n_rows, cdf_sizes, offsets};
-  a.words = words; a.spans = spans; a.state = reinterpret_cast<uint32_t*>(state);
-  a.y_hat = y_hat; a.ldh = ldh; a.symbols = symbols; a.ld_sym = ld_sym;
-  const LanesPixelList place = {pix, H, W_map};
-  hipLaunchKernelGGL(rans_lanes_decode_gauss_kernel<LanesPixelList>, dim3(B * W), dim3(kLanes), 0, ST, a, place);
-  CLC_LAUNCH_CHECK();
-  return 0;
+  return launch_decode_gauss(gp, ldg, gp + M, ldg, M, n, B, scale_table, n_scales, t, words, spans, state, W, y_hat, ldh, symbols, ld_sym,
+                             LanesPixelList{pix, H, W_map}, ST);
 }
 
 extern "C" int clc_rans_lanes_encode_list(const int32_t* symbols, const int32_t* indexes, long ld, int B, const int32_t* seg_len, int P, int W,
                                           const int32_t* cdfs, int cdf_stride, int n_rows, const int32_t* cdf_sizes, const int32_t* offsets,
                                           uint32_t* out, const int32_t* regions, int32_t* result, clc_stream_t stream) {
   CLC_CHECK(symbols && indexes && out && regions && result, "clc_rans_lanes_encode_list: null pointer");
-  CLC_CHECK(cdfs && cdf_sizes && offsets, "clc_rans_lanes_encode_list: null table pointer");
-  CLC_CHECK(cdf_stride >= 2 && n_rows >= 1, "clc_rans_lanes_encode_list: the table needs cdf_stride >= 2 and n_rows >= 1 (got %d, %d)", cdf_stride, n_rows);
-  CLC_CHECK(W >= 1 && W <= CLC_RANS_LANES_MAX_W, "clc_rans_lanes_encode_list: W must be between 1 and %d waves (got %d)", CLC_RANS_LANES_MAX_W, W);
+  const LanesTables t = {cdfs, cdf_stride, n_rows, cdf_sizes, offsets};
+  if (lanes_entry_ok("clc_rans_lanes_encode_list", t, W, B)) return -1;
   CLC_CHECK(B > 0, "clc_rans_lanes_encode_list: B must be positive (got %d)", B);
   CLC_CHECK(P >= 0, "clc_rans_lanes_encode_list: P must not be negative (got %d)", P);
   CLC_CHECK(P == 0 || seg_len, "clc_rans_lanes_encode_list: null segment list");
   CLC_CHECK(ld >= 0 && ld < (1l << 27), "clc_rans_lanes_encode_list: ld must be between 0 and 2^27 - 1 (got %ld); a region's 128 + 10 n words must stay below 2^31", ld);
-  CLC_CHECK((long)B * W < (1l << 24), "clc_rans_lanes_encode_list: B * W must be below 2^24");
   LanesEncArgs<LanesSegList> a = {};
   a.symbols = symbols; a.indexes = indexes; a.ld = ld;
-  a.t = {cdfs, cdf_stride, n_rows, cdf_sizes, offsets};
+  a.t = t;
   a.out = out; a.regions = regions; a.result = result; a.W = W; a.segs = {P, seg_len};
   hipLaunchKernelGGL(rans_lanes_encode_kernel<LanesSegList>, dim3(B * W), dim3(kLanes), 0, ST, a);
   CLC_LAUNCH_CHECK();
