@@ -24,6 +24,8 @@ file.  Same bitstreams, re-staged for the MI355X:
               stream's host halves are _Engine's, shared by both engines.
   container   `pack` / `unpack` / `write_file` / `read_file`: a self-describing byte layout around {"strings", "shape"}
               (the reference only counts len(strings[k][0]), eval_CLC.py:337).
+  sequence    `pack_sequence` / `unpack_sequence`: the CLV1 container of a coded video, what ScaleSpaceFlow.compress returns for a list
+              of frames in either stream format (the end-to-end calls are clc_amd/frames.py's).
 
 Streams are byte-identical to model.compress() per image (tests/test_codec_service_gpu.py), which in turn is pinned to the
 reference's own compress() by tests/golden/codec_*.npz.
@@ -176,6 +178,100 @@ def write_file(path, strings, shape, image_hw, n_refs=0, model_id=0, kernel_conf
 def read_file(path, strict: bool = True):
     with open(path, "rb") as f:
         return unpack(f.read(), strict)
+
+
+# ------------------------------------------------------------------------------------- sequence container (ssf2020)
+SEQ_MAGIC = b"CLV1"
+_SEQ_HEAD = "<BBBBIHHHHHH"   # version, kernel-config tag, lanes, bit depth, kernel-config hash, frames, batch, H, W, Hp, Wp
+_SEQ_HEAD_LEN = 4 + struct.calcsize(_SEQ_HEAD)
+
+
+def _sequence_groups(t, strings):
+    """frame t's string lists in the container's order: keyframe y, z; later frames motion y, z, residual y, z"""
+    return [strings[0], strings[1]] if t == 0 else [strings["motion"][0], strings["motion"][1], strings["residual"][0], strings["residual"][1]]
+
+
+def pack_sequence(frame_strings, shape_infos, *, lanes, image_hw, bit_depth=None, kernel_config_=None) -> bytes:
+    """What ScaleSpaceFlow.compress returned -> one blob, little endian:
+
+        b"CLV1" | u8 version = 1 | u8 kernel-config tag | u8 lanes (0: the default stream format) | u8 bit depth (0: not recorded) |
+        u32 kernel-config hash | u16 frames | u16 batch | u16 H | u16 W (true size) | u16 Hp | u16 Wp (coded size, multiples of 128) |
+        per frame, per string list (keyframe: y, z; later frames: motion y, z, residual y, z), per image: u32 length | bytes
+
+    The z sizes are not stored: every one is (Hp / 128, Wp / 128).  kernel_config_: the state that encoded (default: this call's)."""
+    F = len(frame_strings)
+    if F < 1 or F != len(shape_infos) or F >= 1 << 16:
+        raise ValueError(f"pack_sequence: frame count: {F} frame strings for {len(shape_infos)} shape infos (1 .. 65535 of each)")
+    lanes_n = 0 if lanes is None else coding.lanes_count(lanes, "pack_sequence")
+    bits = 0 if bit_depth is None else int(bit_depth)
+    if bit_depth is not None and not 8 <= bits <= 16:
+        raise ValueError(f"pack_sequence: bit_depth must be 8 .. 16 or None (got bit_depth={bit_depth!r})")
+    zh, zw = (int(v) for v in shape_infos[0])
+    H, W, Hp, Wp = int(image_hw[0]), int(image_hw[1]), 128 * zh, 128 * zw
+    if not (0 < H <= Hp < 1 << 16 and 0 < W <= Wp < 1 << 16):
+        raise ValueError(f"pack_sequence: image_hw {(H, W)} does not fit the coded size {(Hp, Wp)} (128 x the z size {(zh, zw)}; u16 fields)")
+    for t in range(1, F):
+        for k in ("motion", "residual"):
+            if tuple(int(v) for v in shape_infos[t][k]) != (zh, zw):
+                raise ValueError(f"pack_sequence: frame {t}'s {k} z size {tuple(shape_infos[t][k])} is not the keyframe's {(zh, zw)}")
+    B = len(frame_strings[0][0])
+    tag, h = kernel_config_ if kernel_config_ is not None else kernel_config()
+    parts = [SEQ_MAGIC, struct.pack(_SEQ_HEAD, 1, tag & 0xFF, lanes_n, bits, h, F, B, H, W, Hp, Wp)]
+    for t, strings in enumerate(frame_strings):
+        for g, group in enumerate(_sequence_groups(t, strings)):
+            if len(group) != B or not 0 < B < 1 << 16:
+                raise ValueError(f"pack_sequence: frame {t}, string list {g} holds {len(group)} strings, the keyframe's y list {B} (the batch)")
+            for s in group:
+                parts += [struct.pack("<I", len(s)), bytes(s)]
+    return b"".join(parts)
+
+
+def unpack_sequence(blob: bytes, strict: bool = True):
+    """-> (frame_strings, shape_infos, meta) as ScaleSpaceFlow.decompress takes them; meta: frames, batch, image_hw, padded_hw, lanes
+    (None: the default format), bit_depth (None: not recorded), kernel_config_tag / _hash, same_kernel_config.  Refused by name: a
+    wrong magic or version, a blob cut short, trailing bytes, a frame count that disagrees with the strings; strict (default) also
+    another kernel state's blob (KernelConfigMismatch)."""
+    blob = bytes(blob)
+    if len(blob) < 4 or blob[:4] != SEQ_MAGIC:
+        raise ValueError(f"unpack_sequence: wrong magic {blob[:4]!r}: not a {SEQ_MAGIC!r} sequence container")
+    if len(blob) < _SEQ_HEAD_LEN:
+        raise ValueError(f"unpack_sequence: the blob is cut short: {len(blob)} bytes, the header alone is {_SEQ_HEAD_LEN}")
+    ver, tag, lanes_n, bits, h, F, B, H, W, Hp, Wp = struct.unpack(_SEQ_HEAD, blob[4:_SEQ_HEAD_LEN])
+    if ver != 1:
+        raise ValueError(f"unpack_sequence: unsupported version {ver} (this build reads version 1)")
+    if F < 1 or B < 1 or Hp % 128 or Wp % 128 or not (0 < H <= Hp and 0 < W <= Wp) or lanes_n > ans.LANES_MAX_W or bits not in (0,) + tuple(range(8, 17)):
+        raise ValueError(f"unpack_sequence: malformed header (frames {F}, batch {B}, size {(H, W)} in {(Hp, Wp)}, lanes {lanes_n}, bit depth {bits})")
+    pos, shape = _SEQ_HEAD_LEN, torch.Size([Hp // 128, Wp // 128])
+    frame_strings, shape_infos = [], []
+    for t in range(F):
+        if pos == len(blob):
+            raise ValueError(f"unpack_sequence: the frame count {F} disagrees with the strings: the blob ends after {t} whole frames")
+        groups = []
+        for g in range(2 if t == 0 else 4):
+            group = []
+            for b in range(B):
+                n = struct.unpack("<I", blob[pos:pos + 4])[0] if pos + 4 <= len(blob) else None
+                if n is None or pos + 4 + n > len(blob):
+                    raise ValueError(f"unpack_sequence: the blob is cut short inside frame {t}, string list {g}, image {b} (at byte {pos} of {len(blob)})")
+                group.append(blob[pos + 4:pos + 4 + n])
+                pos += 4 + n
+            groups.append(group)
+        if t == 0:
+            frame_strings.append(groups)
+            shape_infos.append(shape)
+        else:
+            frame_strings.append({"motion": groups[0:2], "residual": groups[2:4]})
+            shape_infos.append({"motion": shape, "residual": shape})
+    if pos != len(blob):
+        raise ValueError(f"unpack_sequence: {len(blob) - pos} trailing bytes after the {F} frames the header counts")
+    now, now_h = kernel_config()
+    meta = {"frames": F, "batch": B, "image_hw": (H, W), "padded_hw": (Hp, Wp), "lanes": lanes_n or None, "bit_depth": bits or None,
+            "kernel_config_tag": tag, "kernel_config_hash": h, "same_kernel_config": tag == (now & 0xFF) and h == now_h}
+    if strict and not meta["same_kernel_config"]:
+        raise KernelConfigMismatch(f"the sequence was encoded under kernel-config tag {tag} (hash {h:08x}), this build / tuning state decodes under "
+                                   f"tag {now} (hash {now_h:08x}): the decoder would leave the encoder's bit-exact means / scales; pass "
+                                   "strict=False to read the streams anyway")
+    return frame_strings, shape_infos, meta
 
 
 # --------------------------------------------------------------------------------------------------- engine

@@ -308,6 +308,10 @@ SIGNATURES = {
     "clc_ss_warp_fwd": (_i, [fp, _i, _i, _i, _i, fp, _i, fp, _i, fp, _i, fp]),
     "clc_ss_warp_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "clc_ss_warp_bwd": (_i, [fp, _i, _i, _i, _i, fp, _i, fp, _i, fp, _i, fp, _i, fp, _i, fp, fp, _sz, fp]),
+    "clc_yuv420_to_rgb": (_i, [fp, fp, fp, _i, _i, _i, _i, _i, fp, _l, _i, _i, fp]),
+    "clc_rgb_to_yuv420": (_i, [fp, _l, _i, _i, _i, _i, _i, _i, fp, fp, fp, fp]),
+    "clc_plane_sse_workspace_bytes": (_sz, [_i, _l]),
+    "clc_plane_sse": (_i, [fp, fp, _i, _i, _l, fp, fp, _sz, fp]),
 }
 
 

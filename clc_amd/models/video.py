@@ -19,8 +19,14 @@ layers.Conv2d does not give: their inputs are zero-padded to 4 / 8 channels and 
 Parameter keeps CompressAI's shape; autograd slices its gradient), so they run on the aligned 5x5 kernel.  The keyframe head keeps the
 patch rows (the image takes no gradient).
 
-Plain autograd and the model's own compress / decompress only: TrainEngine, graphed_training, CodecEngine and the lanes streams do
-not take this model.
+THE LANES STREAM (``compress(frames, lanes=W)`` / ``decompress(..., lanes=W)``; DESIGN 30, clc_amd/ans.py: lanes_pack) is opt-in: every
+y string becomes the CLN1 container with ONE segment, the latent's h w planes symbols in NHWC order; z stays the default stream.  The
+device decoder finishes a latent with one clc_rans_lanes_decode_gauss, so a whole sequence decodes with no device -> host copy and no
+synchronize between its first and its last launch (the default format takes one hop per latent, 2 F - 1 for F frames).  With
+lanes=None nothing of it runs and the bytes are the default format's.
+
+Plain autograd and the model's own compress / decompress only: TrainEngine, graphed_training and CodecEngine do not take this model.
+Video frames come in and go out as YUV 4:2:0 sample planes through clc_amd/frames.py; codec.pack_sequence is the container.
 """
 from __future__ import annotations
 
@@ -35,6 +41,8 @@ from ..layers import conv, deconv
 from ..ops import ACT_NONE, ACT_RELU, CL
 from ..scale_space import gaussian_taps, scale_space_volume, scale_space_warp
 from .clc import CompressionModel, _resize_registered_buffers
+from .coding import (check_stream_ends, device_ends, lanes_check, lanes_count, lanes_parse, lanes_strings, refuse_lanes_strings,
+                     upload_streams)
 
 __all__ = ["ScaleSpaceFlow"]
 
@@ -147,34 +155,84 @@ class Hyperprior(CompressionModel):
         return y_hat, {"y": y_likelihoods, "z": z_likelihoods}
 
     @torch.no_grad()
-    def compress(self, y):
+    def compress(self, y, lanes=None):
+        """lanes=None: one host-coded y stream per image.  lanes=W: the lanes stream, one segment of the latent's symbols in NHWC
+        order, encoded on the device (two downloads: the header, the packed words); pass the same W to decompress."""
+        Wn = lanes_count(lanes, "Hyperprior.compress")
         z = self.hyper_encoder(y)
         z_strings = self.entropy_bottleneck.compress(z)
         z_hat = self.entropy_bottleneck.decompress(z_strings, z.size()[-2:])
         scales = self.hyper_decoder_scale(z_hat)
         means = self.hyper_decoder_mean(z_hat)
         gc = self.gaussian_conditional
-        cdf, ln, off = gc.host_tables()
         sym, idx, _ = gc.quantize_and_index(y, means, scales)
         y_hat = sym.to(torch.float32) + means   # formed as decompress forms it: the two sides run one chain
+        if Wn is not None:   # the int32 buffers stay on the device
+            return y_hat, {"strings": [self._lanes_y_strings(sym, idx, Wn), z_strings], "shape": z.size()[-2:]}
+        cdf, ln, off = gc.host_tables()
         sym = sym.contiguous().cpu().numpy()   # [N, C, H, W]: the element order of CompressAI's symbols[i].reshape(-1)
         idx = idx.contiguous().cpu().numpy()
         y_strings = [ans.encode(sym[i].reshape(-1), idx[i].reshape(-1), cdf, ln, off) for i in range(sym.shape[0])]
         return y_hat, {"strings": [y_strings, z_strings], "shape": z.size()[-2:]}
 
+    def _lanes_y_strings(self, sym, idx, W):
+        """quantize_build_indexes' int32 buffers (NCHW views of NHWC memory) -> one lanes string per image: one clc_rans_lanes_encode
+        with the latent as its one segment, one clc_rans_lanes_pack, then two device -> host copies (the header, the packed words)"""
+        gc = self.gaussian_conditional
+        B = sym.shape[0]
+        flat = lambda t: t.permute(0, 2, 3, 1).reshape(B, -1)   # (the buffer's own order: a view)
+        out, _, result = ops.rans_lanes_encode(flat(sym), flat(idx), [int(sym[0].numel())], W, (gc._quantized_cdf, gc._cdf_length, gc._offset))
+        packed, header = ops.rans_lanes_pack(out, result)
+        head = header.cpu().numpy()
+        words = packed[:int(head[B * W])].cpu().numpy() if (head[:B * W] >= 0).all() else np.zeros(0, np.int32)
+        return lanes_strings(head, words, B, W)   # (raises by name on a negative code)
+
+    def _decode_lanes(self, subs, z_strings, shape, device_coder=True, out=None):
+        """The decoder over parsed lanes streams (subs[b][w]: bytes; coding.lanes_parse) -> (y_hat, state).  The z strings are decoded
+        on the host and uploaded, which waits on nothing the device computes.
+        device_coder: one pinned upload of every wave stream's states, spans and words, the two hyper-decoder chains and ONE
+        clc_rans_lanes_decode_gauss — no download, no synchronize; state is the device's int32 [B, W, 130] as the decode left it.
+        Host coder: one index download and one ans.LanesDecoder per image; state is the list of decoders.
+        out: a pixel-major [B, planes, h, w] map to write, e.g. a channel slice of a wider buffer."""
+        if len(subs) != len(z_strings):
+            raise ValueError(f"decompress: {len(subs)} y streams for {len(z_strings)} z streams")
+        z_hat = self.entropy_bottleneck.decompress(z_strings, shape)
+        gc = self.gaussian_conditional
+        if device_coder:
+            state, spans, words = upload_streams(subs, 2 * ans.LANES, z_hat.device)   # a wave stream starts with its 64 lane states
+        scales = self.hyper_decoder_scale(z_hat)
+        means = self.hyper_decoder_mean(z_hat)
+        if device_coder:
+            tables = (gc._quantized_cdf, gc._cdf_length, gc._offset)
+            return ops.rans_lanes_decode_gauss(scales, means, gc.scale_table, tables, words, spans, state, y_hat=out), state
+        decoders = [ans.LanesDecoder(img) for img in subs]
+        cdf, ln, off = gc.host_tables()
+        idx = gc.build_indexes(scales).permute(0, 2, 3, 1).contiguous().cpu().numpy()   # NHWC: the segment's order
+        sym = np.stack([d.decode(idx[b].reshape(-1), cdf, ln, off).reshape(idx.shape[1:]) for b, d in enumerate(decoders)])
+        y_hat = torch.from_numpy(sym).to(z_hat.device).permute(0, 3, 1, 2).to(torch.float32) + means
+        return (y_hat if out is None else out.copy_(y_hat)), decoders
+
     @torch.no_grad()
-    def decompress(self, strings, shape):
+    def decompress(self, strings, shape, lanes=None, device_coder=True, out=None):
+        """lanes=None: the one-stream format, one hop.  lanes=W: the lanes stream of compress(y, lanes=W), its headers parsed before
+        any device work; device_coder=False decodes the same format on the host coder (ans.LanesDecoder): the oracle and the
+        fallback.  out: the pixel-major map y_hat is written into (the lanes kernel writes it in place at its leading dimension)."""
+        Wn = lanes_count(lanes, "Hyperprior.decompress")
         assert isinstance(strings, (list, tuple)) and len(strings) == 2
+        if Wn is not None:
+            return self._decode_lanes(lanes_parse(strings[0], Wn), strings[1], shape, device_coder, out)[0]
+        refuse_lanes_strings(strings[0])
         z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
         scales = self.hyper_decoder_scale(z_hat)
         means = self.hyper_decoder_mean(z_hat)
         gc = self.gaussian_conditional
         cdf, ln, off = gc.host_tables()
         idx = gc.build_indexes(scales).contiguous().cpu().numpy()
-        out = np.empty(idx.shape, dtype=np.float32)
+        sym = np.empty(idx.shape, dtype=np.float32)
         for i, s in enumerate(strings[0]):
-            out[i] = ans.decode(s, idx[i].reshape(-1), cdf, ln, off).reshape(idx.shape[1:])
-        return torch.from_numpy(out).to(z_hat.device).contiguous(memory_format=CL) + means
+            sym[i] = ans.decode(s, idx[i].reshape(-1), cdf, ln, off).reshape(idx.shape[1:])
+        y_hat = torch.from_numpy(sym).to(z_hat.device).contiguous(memory_format=CL) + means
+        return y_hat if out is None else out.copy_(y_hat)
 
 
 class ScaleSpaceFlow(CompressionModel):
@@ -203,6 +261,7 @@ class ScaleSpaceFlow(CompressionModel):
         self.sigma0 = float(sigma0)
         self.num_levels = int(num_levels)
         self.scale_field_shift = scale_field_shift
+        self.planes = int(planes)
 
     # ---- argument checks ----
     @staticmethod
@@ -252,27 +311,99 @@ class ScaleSpaceFlow(CompressionModel):
 
     # ---- codec ----
     @torch.no_grad()
-    def compress(self, frames):
+    def compress(self, frames, lanes=None):
         """-> (frame_strings, shape_infos): the keyframe's [y_strings, z_strings] and z size, then per frame
-        {"motion": [y, z], "residual": [y, z]} and {"motion": z size, "residual": z size}"""
+        {"motion": [y, z], "residual": [y, z]} and {"motion": z size, "residual": z size}.  lanes=W: every y string is the lanes
+        stream (Hyperprior.compress); pass the same W to decompress."""
+        Wn = lanes_count(lanes, "ScaleSpaceFlow.compress")
         frames = self._prep(frames)
-        y_hat, item = self.img_hyperprior.compress(self.img_encoder(frames[0]))
+        y_hat, item = self.img_hyperprior.compress(self.img_encoder(frames[0]), lanes=Wn)
         x_ref = self.img_decoder(y_hat)
         frame_strings, shape_infos = [item["strings"]], [item["shape"]]
         for x in frames[1:]:
-            y_m_hat, m = self.motion_hyperprior.compress(self.motion_encoder(torch.cat((x, x_ref), dim=1)))
+            y_m_hat, m = self.motion_hyperprior.compress(self.motion_encoder(torch.cat((x, x_ref), dim=1)), lanes=Wn)
             x_pred = self._predict(x_ref, y_m_hat)
-            y_r_hat, r = self.res_hyperprior.compress(self.res_encoder(x - x_pred))
+            y_r_hat, r = self.res_hyperprior.compress(self.res_encoder(x - x_pred), lanes=Wn)
             x_ref = x_pred + self.res_decoder(torch.cat((y_r_hat, y_m_hat), dim=1))
             frame_strings.append({"motion": m["strings"], "residual": r["strings"]})
             shape_infos.append({"motion": m["shape"], "residual": r["shape"]})
         return frame_strings, shape_infos
 
+    @staticmethod
+    def _latents(t, strings, shapes):
+        """the coded latents of frame t in decoding order: [(name, [y strings, z strings], z size)]"""
+        if t == 0:
+            return [("keyframe", strings, shapes)]
+        return [(k, strings[k], shapes[k]) for k in ("motion", "residual")]
+
     @torch.no_grad()
-    def decompress(self, frame_strings, shape_infos):
-        """-> the list of reconstructions, unclamped as forward returns them"""
+    def _decompress_lanes(self, frame_strings, shape_infos, Wn, device_coder, check):
+        parsed = []   # every frame's headers, before any device work
+        for t, (strings, shapes) in enumerate(zip(frame_strings, shape_infos)):
+            row = []
+            for name, s, shape in self._latents(t, strings, shapes):
+                try:
+                    row.append((name, lanes_parse(s[0], Wn), s[1], shape))
+                except ValueError as e:
+                    raise ValueError(f"frame {t}, {name} latent: {e}") from None
+            parsed.append(row)
+        ends = []   # (frame, latent, wave streams, coder state) of every latent
+        (name, subs, zs, shape), = parsed[0]
+        y_hat, state = self.img_hyperprior._decode_lanes(subs, zs, shape, device_coder)
+        ends.append((0, name, subs, state))
+        x_ref = self.img_decoder(y_hat)
+        recs = [x_ref]
+        P = self.planes
+        for t in range(1, len(parsed)):
+            (mn, m_subs, m_zs, m_shape), (rn, r_subs, r_zs, r_shape) = parsed[t]
+            # ONE [B, 2 planes, h, w] buffer per frame, (residual | motion): each latent is decoded into its half, no torch.cat
+            both = torch.empty((len(m_subs), 2 * P, 8 * int(m_shape[0]), 8 * int(m_shape[1])), device=x_ref.device, dtype=torch.float32,
+                               memory_format=CL)
+            y_m_hat, state = self.motion_hyperprior._decode_lanes(m_subs, m_zs, m_shape, device_coder, out=both[:, P:])
+            ends.append((t, mn, m_subs, state))
+            x_pred = self._predict(x_ref, y_m_hat)
+            _, state = self.res_hyperprior._decode_lanes(r_subs, r_zs, r_shape, device_coder, out=both[:, :P])
+            ends.append((t, rn, r_subs, state))
+            x_ref = x_pred + self.res_decoder(both)
+            recs.append(x_ref)
+        if check:
+            self._check_ends(ends, device_coder)
+        return recs
+
+    @staticmethod
+    def _check_ends(ends, device_coder):
+        """coding.check_stream_ends over every wave stream of every latent of every frame, after the last frame's launches; the
+        device coder's states are gathered on the device and come down in ONE copy.  Raises naming the frame and the latent."""
+        if device_coder:
+            x, pos = device_ends(torch.cat([state for *_, state in ends]))
+        lo = 0
+        for t, name, subs, state in ends:
+            try:
+                if device_coder:
+                    hi = lo + len(subs)
+                    check_stream_ends(x[lo:hi], pos[lo:hi], [[len(blob) // 4 for blob in img] for img in subs], ans.LANES_STREAM.noun)
+                    lo = hi
+                else:
+                    lanes_check(state, subs)
+            except ValueError as e:
+                raise ValueError(f"frame {t}, {name} latent: {e}") from None
+
+    @torch.no_grad()
+    def decompress(self, frame_strings, shape_infos, lanes=None, device_coder=True, check=True):
+        """-> the list of reconstructions, unclamped as forward returns them.  lanes=None: the default format, one hop per latent
+        (2 F - 1 for F frames).  lanes=W: the strings of compress(frames, lanes=W); every frame's headers are parsed first, and with
+        device_coder=True there is no device -> host copy and no synchronize between the keyframe's first launch and the last
+        frame's last, whatever F; check=True adds exactly ONE download after that, the final coder states of every stream of every
+        frame, and raises ValueError naming the frame, the latent and the wave streams that did not end where a whole stream ends
+        (not a checksum).  device_coder=False runs the same format on the host coder: the oracle and the fallback."""
+        Wn = lanes_count(lanes, "ScaleSpaceFlow.decompress")
         if len(frame_strings) < 1 or len(frame_strings) != len(shape_infos):
             raise ValueError(f"ScaleSpaceFlow.decompress: {len(frame_strings)} frame strings for {len(shape_infos)} shape infos (at least one of each)")
+        if Wn is not None:
+            return self._decompress_lanes(frame_strings, shape_infos, Wn, device_coder, check)
+        for t, (strings, shapes) in enumerate(zip(frame_strings, shape_infos)):
+            for _name, s, _shape in self._latents(t, strings, shapes):
+                refuse_lanes_strings(s[0])
         x_ref = self.img_decoder(self.img_hyperprior.decompress(frame_strings[0], shape_infos[0]))
         recs = [x_ref]
         for strings, shapes in zip(frame_strings[1:], shape_infos[1:]):

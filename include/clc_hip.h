@@ -1029,6 +1029,34 @@ int clc_ss_warp_bwd(const float* vol, int N, int H, int W, int D, const float* f
                     float* dflow /* or NULL */, int lddf, float* dscale /* or NULL */, int ldds, float* dvol /* or NULL */, void* ws, size_t ws_bytes,
                     clc_stream_t stream);
 
+/* ---- video frame I/O: planar YUV 4:2:0 integer samples <-> the model's f32 RGB frames, and plane SSE (csrc/frame_io.hip) ---- *
+ * Sample planes: bytes at bit_depth == 8, 16-bit words read as unsigned at 9 <= bit_depth <= 16, samples in [0, max],
+ * max = 2^bit_depth - 1; y is [N][H][W], u and v are [N][H/2][W/2], dense; H and W even.  rgb is pixel-major f32 [N][Hp][Wp] with
+ * 3 channels at a leading dimension ld >= 3 (in floats); Hp >= H, Wp >= W, both even.
+ * Colour: BT.709 full range, Kr, Kg, Kb = 0.2126, 0.7152, 0.0722; constants are the double expressions rounded once to f32.  The f32
+ * operation order (nothing else is fused):
+ *   sample -> float:  s = (float)sample * (1 / max)
+ *   x2 chroma sample a quarter of a step from tap n towards tap a1 (b behind n, a2 after a1; indices clamped; rows first, then along
+ *   the row):  CLC_CHROMA_BILINEAR fmaf(1/4, a1, 3/4 * n);  CLC_CHROMA_BICUBIC fmaf(-27/256, b, fmaf(-9/256, a2, fmaf(67/256, a1, 225/256 * n)))
+ *   (F.interpolate(scale_factor=2, align_corners=False); bicubic with torch's A = -0.75)
+ *   YCbCr -> RGB:  r = fmaf(2 - 2 Kr, cr - 0.5, y);  b = fmaf(2 - 2 Kb, cb - 0.5, y);  g = fmaf(-Kb, b, fmaf(-Kr, r, y)) * (1 / Kg)
+ *   RGB -> YCbCr:  r, g, b clamped to [0, 1];  y = fmaf(Kb, b, fmaf(Kg, g, Kr * r));  cb = fmaf(0.5 / (1 - Kb), b - y, 0.5);
+ *                  cr = fmaf(0.5 / (1 - Kr), r - y, 0.5);  chroma of a 2x2 block ((c00 + c01) + (c10 + c11)) * 0.25
+ *   float -> sample:  rintf(fminf(fmaxf(v, 0), 1) * max), round half to even
+ * clc_yuv420_to_rgb writes the UNCLAMPED frame; output pixel (h, w) is the converted pixel (min(h, H - 1), min(w, W - 1)): replicate
+ * padding by clamped reads.  clc_rgb_to_yuv420 reads the top-left H x W of the Hp x Wp frame (the crop).  At 8 bits neutral chroma is
+ * 127.5, an exact tie: grey lands on 127 or 128 by the last bit of b - y (the definition's property).
+ * clc_plane_sse: out[i] = the exact sum over image i's n samples of (a - b)^2, in 64-bit integers (two stages, no atomics: the same
+ * whatever the order); ws holds the partial sums.  Stream-ordered launches; nothing is allocated; capturable. */
+#define CLC_CHROMA_BILINEAR 0
+#define CLC_CHROMA_BICUBIC 1
+int clc_yuv420_to_rgb(const void* y, const void* u, const void* v, int bit_depth, int N, int H, int W, int mode, float* rgb, long ld, int Hp, int Wp,
+                      clc_stream_t stream);
+int clc_rgb_to_yuv420(const float* rgb, long ld, int Hp, int Wp, int N, int H, int W, int bit_depth, void* y, void* u, void* v, clc_stream_t stream);
+size_t clc_plane_sse_workspace_bytes(int N, long n);   /* 0 and clc_last_error on refused sizes */
+int clc_plane_sse(const void* a, const void* b, int bit_depth, int N, long n /* samples per image */, int64_t* out /* [N] */, void* ws, size_t ws_bytes,
+                  clc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
