@@ -32,6 +32,7 @@ reference's own compress() by tests/golden/codec_*.npz.
 """
 from __future__ import annotations
 
+import math
 import struct
 import time
 from concurrent.futures import ThreadPoolExecutor
@@ -272,6 +273,52 @@ def unpack_sequence(blob: bytes, strict: bool = True):
                                    f"tag {now} (hash {now_h:08x}): the decoder would leave the encoder's bit-exact means / scales; pass "
                                    "strict=False to read the streams anyway")
     return frame_strings, shape_infos, meta
+
+
+SEQ_Q_MAGIC = b"CLVQ"
+
+
+def pack_sequence_q(blob: bytes, qs) -> bytes:
+    """A CLV1 blob coded under per-frame qualities (variable rate) -> the wrapper, little endian:
+
+        b"CLVQ" | u16 frames | frames x f32 q | the CLV1 blob as pack_sequence wrote it
+
+    CLV1 itself is unchanged (its version stays 1): a reader that knows no qualities refuses the wrapper by its magic.  qs: one finite
+    float per frame of the inner blob."""
+    blob = bytes(blob)
+    if len(blob) < _SEQ_HEAD_LEN or blob[:4] != SEQ_MAGIC:
+        raise ValueError(f"pack_sequence_q: the inner blob is not a whole {SEQ_MAGIC!r} container (magic {blob[:4]!r}, {len(blob)} bytes)")
+    F = struct.unpack(_SEQ_HEAD, blob[4:_SEQ_HEAD_LEN])[5]
+    qs = [float(q) for q in qs]
+    if len(qs) != F:
+        raise ValueError(f"pack_sequence_q: {len(qs)} qualities for the {F} frames the inner header counts")
+    if not all(math.isfinite(q) for q in qs):
+        raise ValueError(f"pack_sequence_q: non-finite q in {qs}")
+    return b"".join([SEQ_Q_MAGIC, struct.pack(f"<H{F}f", F, *qs), blob])
+
+
+def unpack_sequence_q(blob: bytes):
+    """-> (the inner CLV1 blob for unpack_sequence, [q per frame]).  Refused by name: a wrong magic, a blob cut short, a count that
+    disagrees with the inner header, a non-finite q."""
+    blob = bytes(blob)
+    if len(blob) < 4 or blob[:4] != SEQ_Q_MAGIC:
+        raise ValueError(f"unpack_sequence_q: wrong magic {blob[:4]!r}: not a {SEQ_Q_MAGIC!r} container")
+    if len(blob) < 6:
+        raise ValueError(f"unpack_sequence_q: the blob is cut short: {len(blob)} bytes, the frame count alone ends at byte 6")
+    F = struct.unpack("<H", blob[4:6])[0]
+    end = 6 + 4 * F
+    if len(blob) < end + _SEQ_HEAD_LEN:
+        raise ValueError(f"unpack_sequence_q: the blob is cut short: {len(blob)} bytes, {F} qualities and the inner header end at byte {end + _SEQ_HEAD_LEN}")
+    qs = list(struct.unpack(f"<{F}f", blob[6:end]))
+    inner = blob[end:]
+    if inner[:4] != SEQ_MAGIC:
+        raise ValueError(f"unpack_sequence_q: wrong inner magic {inner[:4]!r}: the wrapper holds a {SEQ_MAGIC!r} container")
+    inner_frames = struct.unpack(_SEQ_HEAD, inner[4:_SEQ_HEAD_LEN])[5]
+    if inner_frames != F:
+        raise ValueError(f"unpack_sequence_q: the frame count {F} disagrees with the inner header's {inner_frames}")
+    if not all(math.isfinite(q) for q in qs):
+        raise ValueError(f"unpack_sequence_q: non-finite q in {qs}")
+    return inner, qs
 
 
 # --------------------------------------------------------------------------------------------------- engine

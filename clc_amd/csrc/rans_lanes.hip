@@ -197,6 +197,7 @@ struct LanesGaussArgs {
   uint32_t* state;
   float* y_hat; long ldh;
   int32_t* symbols; long ld_sym;   // symbols may be null
+  const float* step;               // [C]: the quantisation step per channel; read by the kStep instantiations only
 };
 
 struct LanesDenseRows {
@@ -213,7 +214,11 @@ struct LanesPixelList {
   }
 };
 
-template <class Landing>
+// kStep (variable-rate coding; clc_rans_lanes_decode_gauss_step): the row index is that of max(scale, 0.11) / step[c] and the symbol
+// leaves as y_hat = (float)symbol * step[c] + mu, a rounded multiply and a rounded add — clc_quantize_build_indexes_step's expression.  The
+// step of a round is fetched where its scale (for the index) and its mu (for the value) are; words, spans, states, clamps and loop
+// bounds are the unit-step kernel's, and with kStep false every added line is compiled out.
+template <class Landing, bool kStep = false>
 __global__ __launch_bounds__(64) void rans_lanes_decode_gauss_kernel(const LanesGaussArgs a, const Landing place) {
   __shared__ float tb[kMaxScales];
   const int lane = threadIdx.x;
@@ -245,13 +250,18 @@ __global__ __launch_bounds__(64) void rans_lanes_decode_gauss_kernel(const Lanes
   const int j0 = w * kLanes + lane;   // (< 2^10 + 64)
   Place ahead = {j0 / a.C, j0 % a.C}, row = ahead;   // of the next round load_scales / fetch_row is called for
   float sc[kGroup] = {};
+  float sq[kStep ? kGroup : 1];   // kStep: the steps of the group's rounds
   auto load_scales = [&](int q0) {   // the scales of rounds q0, q0 + W, ...: called for consecutive groups
 #pragma unroll
     for (int g = 0; g < kGroup; ++g) {
       const long q = (long)q0 + (long)g * a.W;
       const long j = q * kLanes + lane;
       sc[g] = 0.f;
-      if (q < chunks && j < a.n) sc[g] = a.scale[(row0 + ahead.p) * a.ldsc + ahead.c];
+      if constexpr (kStep) sq[g] = 1.f;
+      if (q < chunks && j < a.n) {
+        sc[g] = a.scale[(row0 + ahead.p) * a.ldsc + ahead.c];
+        if constexpr (kStep) sq[g] = a.step[ahead.c];
+      }
       advance(ahead);
     }
   };
@@ -261,7 +271,11 @@ __global__ __launch_bounds__(64) void rans_lanes_decode_gauss_kernel(const Lanes
     float sg[kGroup];
     int pos[kGroup];
 #pragma unroll
-    for (int g = 0; g < kGroup; ++g) { sg[g] = fmaxf(sc[g], kScaleBound); pos[g] = 0; }
+    for (int g = 0; g < kGroup; ++g) {
+      sg[g] = fmaxf(sc[g], kScaleBound);
+      if constexpr (kStep) sg[g] = sg[g] / sq[g];
+      pos[g] = 0;
+    }
 #pragma unroll 1
     for (int step = top; step >= 1; step >>= 1) {
 #pragma unroll
@@ -278,7 +292,7 @@ __global__ __launch_bounds__(64) void rans_lanes_decode_gauss_kernel(const Lanes
   };
   int ci_next = 0, size_next = 2, off_next = 0;
   long at_next = 0;
-  float mu_next = 0.f;
+  float mu_next = 0.f, step_next = 1.f;
   auto fetch_row = [&](int q, int index) {   // called for consecutive rounds
     const long j = (long)q * kLanes + lane;
     if (q < chunks && j < a.n) {
@@ -288,6 +302,7 @@ __global__ __launch_bounds__(64) void rans_lanes_decode_gauss_kernel(const Lanes
       size_next = clamp_int(a.t.cdf_sizes[ci_next], 2, a.t.cdf_stride);
       off_next = a.t.offsets[ci_next];
       mu_next = a.mu[r * a.ldmu + c];
+      if constexpr (kStep) step_next = a.step[c];
       at_next = place.at(b, r, row.p, c, a.ldh);
     }
     advance(row);
@@ -303,7 +318,7 @@ __global__ __launch_bounds__(64) void rans_lanes_decode_gauss_kernel(const Lanes
     const bool active = j < a.n;
     const int ci = ci_next, size = size_next, off = off_next;
     const long at = at_next;
-    const float m_ = mu_next;
+    const float m_ = mu_next, s_ = step_next;
     g = (g + 1) & (kGroup - 1);
     if (g == 0) {   // (uniform) the next round opens a group
       pack = search();
@@ -313,7 +328,11 @@ __global__ __launch_bounds__(64) void rans_lanes_decode_gauss_kernel(const Lanes
     const uint32_t value = d.round(a.t.cdfs + (long)ci * a.t.cdf_stride, size - 2, active);
     if (active) {
       const int32_t sym = (int32_t)(value + (uint32_t)off);
-      if (Landing::kEveryRow || at >= 0) a.y_hat[at] = (float)sym + m_;
+      if constexpr (kStep) {
+        if (Landing::kEveryRow || at >= 0) a.y_hat[at] = (float)sym * s_ + m_;
+      } else {
+        if (Landing::kEveryRow || at >= 0) a.y_hat[at] = (float)sym + m_;
+      }
       if (a.symbols) a.symbols[(long)b * a.ld_sym + j] = sym;
     }
   }
@@ -374,14 +393,21 @@ int lanes_entry_ok(const char* who, const LanesTables& t, int W, int B) {
 template <class Landing>
 int launch_decode_gauss(const float* scale, long ldsc, const float* mu, long ldmu, int C, int n, int B, const float* scale_table, int n_scales,
                         const LanesTables& t, const uint32_t* words, const int32_t* spans, clc_rans_lanes_state* state, int W, float* y_hat, long ldh,
-                        int32_t* symbols, long ld_sym, const Landing& place, hipStream_t st) {
+                        int32_t* symbols, long ld_sym, const Landing& place, hipStream_t st, const float* step = nullptr) {
   LanesGaussArgs a = {};
   a.scale = scale; a.ldsc = ldsc; a.mu = mu; a.ldmu = ldmu; a.C = C; a.n = n; a.W = W;
   a.table = scale_table; a.n_scales = n_scales;
   a.t = t;
   a.words = words; a.spans = spans; a.state = reinterpret_cast<uint32_t*>(state);
-  a.y_hat = y_hat; a.ldh = ldh; a.symbols = symbols; a.ld_sym = ld_sym;
-  hipLaunchKernelGGL(rans_lanes_decode_gauss_kernel<Landing>, dim3(B * W), dim3(kLanes), 0, st, a, place);
+  a.y_hat = y_hat; a.ldh = ldh; a.symbols = symbols; a.ld_sym = ld_sym; a.step = step;
+  bool stepped = false;
+  if constexpr (Landing::kEveryRow) {   // (the context models' pixel-list landing has no step entry: no such instantiation)
+    if (step) {
+      hipLaunchKernelGGL((rans_lanes_decode_gauss_kernel<Landing, true>), dim3(B * W), dim3(kLanes), 0, st, a, place);
+      stepped = true;
+    }
+  }
+  if (!stepped) hipLaunchKernelGGL((rans_lanes_decode_gauss_kernel<Landing, false>), dim3(B * W), dim3(kLanes), 0, st, a, place);
   CLC_LAUNCH_CHECK();
   return 0;
 }
@@ -433,22 +459,41 @@ extern "C" int clc_rans_lanes_encode(const int32_t* symbols, const int32_t* inde
   return 0;
 }
 
+// clc_rans_lanes_decode_gauss and clc_rans_lanes_decode_gauss_step: one set of checks under the entry's name; step == nullptr is the unit step
+static int decode_gauss_entry(const char* who, const float* scale, long ldsc, const float* mu, long ldmu, const float* step, int C, int n, int B,
+                              const float* scale_table, int n_scales, const int32_t* cdfs, int cdf_stride, int n_rows, const int32_t* cdf_sizes,
+                              const int32_t* offsets, const uint32_t* words, const int32_t* spans, clc_rans_lanes_state* state, int W,
+                              float* y_hat, long ldh, int32_t* symbols, long ld_sym, hipStream_t st) {
+  CLC_CHECK(scale && mu && scale_table && words && spans && state && y_hat, "%s: null pointer", who);
+  const LanesTables t = {cdfs, cdf_stride, n_rows, cdf_sizes, offsets};
+  if (lanes_entry_ok(who, t, W, B)) return -1;
+  CLC_CHECK(n_scales > 1 && n_scales <= kMaxScales, "%s: n_scales must be between 2 and %d (got %d)", who, kMaxScales, n_scales);
+  CLC_CHECK(n >= 0 && B > 0, "%s: n must not be negative and B must be positive (got %d, %d)", who, n, B);
+  CLC_CHECK(n < (1 << 30), "%s: n must be below 2^30 symbols per image (got %d)", who, n);
+  CLC_CHECK(C > 0 && n % C == 0, "%s: n must be whole rows of C > 0 channels (got n = %d, C = %d)", who, n, C);
+  CLC_CHECK(ldsc >= C && ldmu >= C && ldh >= C, "%s: ldsc, ldmu or ldh < C", who);
+  CLC_CHECK(!symbols || ld_sym >= n, "%s: ld_sym < n", who);
+  if (n == 0) return 0;   // an empty segment contributes nothing
+  return launch_decode_gauss(scale, ldsc, mu, ldmu, C, n, B, scale_table, n_scales, t, words, spans, state, W, y_hat, ldh, symbols, ld_sym,
+                             LanesDenseRows{}, st, step);
+}
+
 extern "C" int clc_rans_lanes_decode_gauss(const float* scale, long ldsc, const float* mu, long ldmu, int C, int n, int B, const float* scale_table,
                                            int n_scales, const int32_t* cdfs, int cdf_stride, int n_rows, const int32_t* cdf_sizes,
                                            const int32_t* offsets, const uint32_t* words, const int32_t* spans, clc_rans_lanes_state* state, int W,
                                            float* y_hat, long ldh, int32_t* symbols, long ld_sym, clc_stream_t stream) {
-  CLC_CHECK(scale && mu && scale_table && words && spans && state && y_hat, "clc_rans_lanes_decode_gauss: null pointer");
-  const LanesTables t = {cdfs, cdf_stride, n_rows, cdf_sizes, offsets};
-  if (lanes_entry_ok("clc_rans_lanes_decode_gauss", t, W, B)) return -1;
-  CLC_CHECK(n_scales > 1 && n_scales <= kMaxScales, "clc_rans_lanes_decode_gauss: n_scales must be between 2 and %d (got %d)", kMaxScales, n_scales);
-  CLC_CHECK(n >= 0 && B > 0, "clc_rans_lanes_decode_gauss: n must not be negative and B must be positive (got %d, %d)", n, B);
-  CLC_CHECK(n < (1 << 30), "clc_rans_lanes_decode_gauss: n must be below 2^30 symbols per image (got %d)", n);
-  CLC_CHECK(C > 0 && n % C == 0, "clc_rans_lanes_decode_gauss: n must be whole rows of C > 0 channels (got n = %d, C = %d)", n, C);
-  CLC_CHECK(ldsc >= C && ldmu >= C && ldh >= C, "clc_rans_lanes_decode_gauss: ldsc, ldmu or ldh < C");
-  CLC_CHECK(!symbols || ld_sym >= n, "clc_rans_lanes_decode_gauss: ld_sym < n");
-  if (n == 0) return 0;   // an empty segment contributes nothing
-  return launch_decode_gauss(scale, ldsc, mu, ldmu, C, n, B, scale_table, n_scales, t, words, spans, state, W, y_hat, ldh, symbols, ld_sym,
-                             LanesDenseRows{}, ST);
+  return decode_gauss_entry("clc_rans_lanes_decode_gauss", scale, ldsc, mu, ldmu, nullptr, C, n, B, scale_table, n_scales, cdfs, cdf_stride, n_rows,
+                            cdf_sizes, offsets, words, spans, state, W, y_hat, ldh, symbols, ld_sym, ST);
+}
+
+extern "C" int clc_rans_lanes_decode_gauss_step(const float* scale, long ldsc, const float* mu, long ldmu, const float* step, int C, int n, int B,
+                                                const float* scale_table, int n_scales, const int32_t* cdfs, int cdf_stride, int n_rows,
+                                                const int32_t* cdf_sizes, const int32_t* offsets, const uint32_t* words, const int32_t* spans,
+                                                clc_rans_lanes_state* state, int W, float* y_hat, long ldh, int32_t* symbols, long ld_sym,
+                                                clc_stream_t stream) {
+  CLC_CHECK(step, "clc_rans_lanes_decode_gauss_step: step is NULL (the unit-step entry is clc_rans_lanes_decode_gauss)");
+  return decode_gauss_entry("clc_rans_lanes_decode_gauss_step", scale, ldsc, mu, ldmu, step, C, n, B, scale_table, n_scales, cdfs, cdf_stride, n_rows,
+                            cdf_sizes, offsets, words, spans, state, W, y_hat, ldh, symbols, ld_sym, ST);
 }
 
 extern "C" int clc_ar_lanes_decode(const float* gp, long ldg, int M, const int32_t* pix, int P, int B, int H, int W_map, const float* scale_table,

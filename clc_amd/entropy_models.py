@@ -245,31 +245,48 @@ class GaussianConditional(EntropyModel):
         self._cdf_length = (pmf_length + 2).to(dev)
         self._host_tables = None
 
-    def likelihood_and_ste(self, y, scales, means, training=None, noise=None, lik_out=None):
+    def likelihood_and_ste(self, y, scales, means, training=None, noise=None, lik_out=None, step=None):
         """(likelihood, ste_round(y - means) + means) in one kernel (CLC_run.py:569-571).  noise: pre-drawn U(-1/2, 1/2) of y's
-        shape (the model draws all slices' noise in one launch); drawn here when None."""
+        shape (the model draws all slices' noise in one launch); drawn here when None.
+        step [C]: the quantisation step per channel -> (likelihood of the bin of that width,
+        step * ste_round((y - means) / step) + means), differentiable in step; None: the unit-step kernels, as before."""
         training = self.training if training is None else training
         if training and noise is None:
             noise = torch.empty_like(y, memory_format=ops.CL).uniform_(-0.5, 0.5)
         if not training:
             noise = None
+        if step is not None:
+            if lik_out is not None:
+                raise ValueError("GaussianConditional.likelihood_and_ste: lik_out is not built for the step kernels")
+            return ops.gaussian_likelihood_step(y, scales, means, step, noise, training)
         return ops.gaussian_likelihood(y, scales, means, noise, training, lik_out)
 
-    def forward(self, inputs, scales, means=None, training=None):
+    def forward(self, inputs, scales, means=None, training=None, step=None):
+        """step [C]: the quantisation step per channel; the training output is inputs + step * noise, the eval output the dequantised
+        value with its straight-through gradients.  None: the unit-step path, untouched."""
         training = self.training if training is None else training
         if means is None:
             means = torch.zeros_like(inputs, memory_format=ops.CL)
         noise = torch.empty_like(inputs, memory_format=ops.CL).uniform_(-0.5, 0.5) if training else None
+        if step is not None:
+            lik, y_hat = ops.gaussian_likelihood_step(inputs, scales, means, step, noise, training)
+            return (inputs + step.reshape(1, -1, 1, 1) * noise if training else y_hat), lik
         lik, y_hat = ops.gaussian_likelihood(inputs, scales, means, noise, training)
         outputs = inputs + noise if training else y_hat.detach()
         return outputs, lik
 
-    def build_indexes(self, scales):
-        _, idx, _ = ops.quantize_build_indexes(scales, torch.zeros_like(scales, memory_format=ops.CL), scales, self.scale_table)
+    def build_indexes(self, scales, step=None):
+        zeros = torch.zeros_like(scales, memory_format=ops.CL)
+        if step is not None:
+            return ops.quantize_build_indexes_step(scales, zeros, scales, self.scale_table, step)[1]
+        _, idx, _ = ops.quantize_build_indexes(scales, zeros, scales, self.scale_table)
         return idx
 
-    def quantize_and_index(self, y, means, scales):
-        """symbols, indexes, y_hat = quantize(y,'symbols',means), build_indexes(scales), symbols+means — one kernel."""
+    def quantize_and_index(self, y, means, scales, step=None):
+        """symbols, indexes, y_hat = quantize(y,'symbols',means), build_indexes(scales), symbols+means — one kernel.
+        step [C]: symbols of (y - means) / step, indexes of scales / step, y_hat = symbols * step + means."""
+        if step is not None:
+            return ops.quantize_build_indexes_step(y, means, scales, self.scale_table, step)
         return ops.quantize_build_indexes(y, means, scales, self.scale_table)
 
 

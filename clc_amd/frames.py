@@ -20,6 +20,7 @@ No file reading: a raw .yuv file is numpy.fromfile plus a reshape on the caller'
 from __future__ import annotations
 
 import math
+import struct
 
 import torch
 
@@ -177,31 +178,49 @@ def _check_sequence(who, planes, bit_depth):
     return shape
 
 
-def encode_yuv420(model, planes, bit_depth=8, lanes=4, mode="bilinear"):
+def encode_yuv420(model, planes, bit_depth=8, lanes=4, mode="bilinear", q=None):
     """A list of (Y, U, V) device planes -> one CLV1 container (codec.pack_sequence): yuv420_to_rgb pads each frame to the next
-    multiples of 128 (replicate), model.compress(frames, lanes=lanes) codes them.  lanes=None: the default stream format."""
+    multiples of 128 (replicate), model.compress(frames, lanes=lanes) codes them.  lanes=None: the default stream format.
+    q (variable rate; a model built with rate_levels > 0): one quality for every frame or a list of one per frame -> the CLVQ wrapper
+    around the same container (codec.pack_sequence_q), which carries the qualities as f32 — the values the frames are coded under."""
     from . import codec
+    from .vbr import check_quality, frame_qualities
 
     N, H, W = _check_sequence("encode_yuv420", planes, bit_depth)
     _mode("encode_yuv420", mode)
     Hp, Wp = -(-H // 128) * 128, -(-W // 128) * 128
+    if q is None:
+        frames = [yuv420_to_rgb(*p, bit_depth=bit_depth, mode=mode, size=(Hp, Wp)) for p in planes]
+        frame_strings, shape_infos = model.compress(frames, lanes=lanes)
+        return codec.pack_sequence(frame_strings, shape_infos, lanes=lanes, image_hw=(H, W), bit_depth=bit_depth)
+    qs = frame_qualities(q, len(planes), "encode_yuv420")
+    table_owner = getattr(model, "img_hyperprior", model)   # every refusal of q comes before the first launch
+    qs = [check_quality(table_owner, qt, f"encode_yuv420 (frame {t})") for t, qt in enumerate(qs)]
+    qs = [struct.unpack("<f", struct.pack("<f", float(qt)))[0] for qt in qs]   # the decoder reads f32: code under what it will read
     frames = [yuv420_to_rgb(*p, bit_depth=bit_depth, mode=mode, size=(Hp, Wp)) for p in planes]
-    frame_strings, shape_infos = model.compress(frames, lanes=lanes)
-    return codec.pack_sequence(frame_strings, shape_infos, lanes=lanes, image_hw=(H, W), bit_depth=bit_depth)
+    frame_strings, shape_infos = model.compress(frames, lanes=lanes, q=qs)
+    return codec.pack_sequence_q(codec.pack_sequence(frame_strings, shape_infos, lanes=lanes, image_hw=(H, W), bit_depth=bit_depth), qs)
 
 
 def decode_yuv420(model, blob, mode="bilinear", bit_depth=None):
     """A CLV1 container -> the list of (Y, U, V) of the true size: codec.unpack_sequence, model.decompress under the container's lanes,
     then rgb_to_yuv420 crops and quantises.  bit_depth: default the container's.  mode: the encoder's chroma mode, checked by name;
-    the way back is the 2x2 mean under both."""
+    the way back is the 2x2 mean under both.  A CLVQ wrapper (encode_yuv420(..., q=)) is recognised by its magic and decoded under
+    the qualities it carries."""
     from . import codec
 
     _mode("decode_yuv420", mode)
+    qs = None
+    if bytes(blob[:4]) == codec.SEQ_Q_MAGIC:
+        blob, qs = codec.unpack_sequence_q(blob)
     frame_strings, shape_infos, meta = codec.unpack_sequence(blob)
     bit_depth = meta["bit_depth"] if bit_depth is None else bit_depth
     if bit_depth is None:
         raise ValueError("decode_yuv420: the container records no bit depth; pass bit_depth=")
-    recs = model.decompress(frame_strings, shape_infos, lanes=meta["lanes"])
+    if qs is None:
+        recs = model.decompress(frame_strings, shape_infos, lanes=meta["lanes"])
+    else:
+        recs = model.decompress(frame_strings, shape_infos, lanes=meta["lanes"], q=qs)
     return [rgb_to_yuv420(x, meta["image_hw"], bit_depth=bit_depth) for x in recs]
 
 

@@ -212,6 +212,12 @@ SIGNATURES = {
     "clc_eb_lik_bwd": (_i, [fp, _i, fp, _i, fp, _i, fp, _pp, _pp, _pp, _pp, _pp, _pp, fp, _i, _l, _i, _i, fp]),
     "clc_eb_aux": (_i, [fp, _pp, _pp, _pp, fp, fp, fp, _i, fp]),
     "clc_quantize_build_indexes": (_i, [fp, _i, fp, _i, fp, _i, fp, _i, fp, fp, fp, _i, _l, _i, fp]),
+    "clc_gauss_lik_step_fwd": (_i, [fp, _i, fp, _i, fp, _i, fp, _i, fp, fp, _i, fp, _i, _l, _i, _i, fp, _i, fp]),
+    "clc_gauss_lik_step_bwd_workspace_bytes": (_sz, [_l, _i]),
+    "clc_gauss_lik_step_bwd": (_i, [fp, _i, fp, _i, fp, _i, fp, _i, fp, _i, fp, fp, _i, fp, _i, fp, _i, fp, _l, _i, _i, fp, _i, fp, _sz, fp]),
+    "clc_quantize_build_indexes_step": (_i, [fp, _i, fp, _i, fp, _i, fp, fp, _i, fp, fp, fp, _i, _l, _i, fp]),
+    "clc_gauss_rate_sweep_workspace_bytes": (_sz, [_i, _l, _i, _i]),
+    "clc_gauss_rate_sweep": (_i, [fp, _i, fp, _i, fp, _i, fp, _i, _i, _l, _i, fp, fp, _sz, fp]),
     "clc_log2_sum_partials": (_i, [fp, _i, _l, _i, fp, _i, fp]),
     "clc_scaled_recip": (_i, [fp, _i, _l, _i, fp, _f, fp, _i, fp]),
     "clc_scaled_diff": (_i, [fp, fp, _l, fp, _f, fp, fp]),
@@ -299,6 +305,7 @@ SIGNATURES = {
     "clc_rans_lanes_decode_step": (_i, [fp, _l, _i, _i, fp, _i, _i, fp, fp, fp, fp, fp, _i, fp, _l, fp]),
     "clc_rans_lanes_encode": (_i, [fp, fp, _l, _i, LanesSegments, _i, fp, _i, _i, fp, fp, fp, fp, fp, fp]),
     "clc_rans_lanes_decode_gauss": (_i, [fp, _l, fp, _l, _i, _i, _i, fp, _i, fp, _i, _i, fp, fp, fp, fp, fp, _i, fp, _l, fp, _l, fp]),
+    "clc_rans_lanes_decode_gauss_step": (_i, [fp, _l, fp, _l, fp, _i, _i, _i, fp, _i, fp, _i, _i, fp, fp, fp, fp, fp, _i, fp, _l, fp, _l, fp]),
     "clc_rans_lanes_pack": (_i, [fp, _l, fp, _i, _i, fp, _l, fp, fp]),
     "clc_ar_lanes_decode": (_i, [fp, _l, _i, fp, _i, _i, _i, _i, fp, _i, fp, _i, _i, fp, fp, fp, fp, fp, _i, fp, _l, fp, _l, fp]),
     "clc_rans_lanes_encode_list": (_i, [fp, fp, _l, _i, fp, _i, _i, fp, _i, _i, fp, fp, fp, fp, fp, fp]),

@@ -30,6 +30,7 @@ from .. import ans, ops
 from ..entropy_models import EntropyBottleneck, GaussianConditional
 from ..layers import GDN, CheckerboardMaskedConv2d, Conv2d, MaskedConv2d, conv, deconv
 from ..ops import ACT_LRELU, ACT_NONE, ACT_RELU, CL
+from ..vbr import StepTable, model_step, refuse_rate_levels
 from .clc import CompressionModel, _resize_registered_buffers, get_scale_table
 from .coding import (CodeInputs, HostSymbols, coded_item, decoder_start, lanes_check, lanes_count, lanes_parse, lanes_strings, linear_filters,
                      open_decoders, refuse_lanes_strings, upload_streams)
@@ -40,9 +41,14 @@ class ScaleHyperprior(CompressionModel):
 
     _h_act = ACT_RELU
 
-    def __init__(self, N=128, M=192, **kwargs):
+    def __init__(self, N=128, M=192, rate_levels=0, **kwargs):
         super().__init__(entropy_bottleneck_channels=N)
         self._check_channels(N, M)
+        rate_levels = int(rate_levels)
+        if rate_levels < 0:
+            raise ValueError(f"{type(self).__name__}: rate_levels must not be negative (got {rate_levels})")
+        if rate_levels:   # VARIABLE RATE: a table of quantisation steps for y; without it no module and no state_dict key
+            self.y_step = StepTable(M, rate_levels)
         self.g_a = nn.Sequential(conv(3, N), GDN(N), conv(N, N), GDN(N), conv(N, N), GDN(N), conv(N, M))
         self.g_s = nn.Sequential(deconv(M, N), GDN(N, inverse=True), deconv(N, N), GDN(N, inverse=True), deconv(N, N), GDN(N, inverse=True),
                                  deconv(N, 3))
@@ -97,48 +103,109 @@ class ScaleHyperprior(CompressionModel):
         """(scales, means or None) of y from z_hat"""
         return self._hyper_synthesis(z_hat), None
 
-    def forward(self, x):
+    def _step(self, q, who):
+        """the step vector of quality q from the model's step table (vbr.model_step: None for q None, refusals by name)"""
+        return model_step(self, q, f"{type(self).__name__}.{who}")
+
+    def forward(self, x, q=None):
+        """q: the quality, a float in [0, rate_levels - 1] (higher: finer steps, more bits); None: the fixed-rate model.  With q the
+        eval x_hat is decoded from step * ste_round((y - mu) / step) + mu, so the distortion reaches the step table too."""
+        step = self._step(q, "forward")
         x = self._prep(x)
         y = self._analysis(x)
         z = self._hyper_analysis(y)
         z_hat, z_likelihoods = self.entropy_bottleneck(z)
         scales_hat, means_hat = self._params(z_hat)
-        y_hat, y_likelihoods = self.gaussian_conditional(y, scales_hat, means=means_hat)
+        if step is None:
+            y_hat, y_likelihoods = self.gaussian_conditional(y, scales_hat, means=means_hat)
+        else:
+            y_hat, y_likelihoods = self.gaussian_conditional(y, scales_hat, means=means_hat, step=step)
         x_hat = self._synthesis(y_hat)
-        return {"x_hat": x_hat, "likelihoods": {"y": y_likelihoods, "z": z_likelihoods}}
+        out = {"x_hat": x_hat, "likelihoods": {"y": y_likelihoods, "z": z_likelihoods}}
+        if step is not None:
+            out["q"] = q
+        return out
 
     # ---- codec: one y stream and one z stream per image, on the host rANS coder ----
     def _zeros_like(self, t):
         return torch.zeros_like(t, memory_format=CL)
 
+    def _encode_y(self, y, means, scales_hat, step):
+        """the y strings of a batch under a step vector (None: the unit step)"""
+        gc = self.gaussian_conditional
+        cdf, ln, off = gc.host_tables()
+        sym, idx, _ = gc.quantize_and_index(y, means, scales_hat) if step is None else gc.quantize_and_index(y, means, scales_hat, step=step)
+        sym = sym.contiguous().cpu().numpy()   # [N, C, H, W]: the element order of CompressAI's symbols[i].reshape(-1)
+        idx = idx.contiguous().cpu().numpy()
+        return [ans.encode(sym[i].reshape(-1), idx[i].reshape(-1), cdf, ln, off) for i in range(sym.shape[0])]
+
+    def rate_sweep(self, y, means, scales_hat, qs):
+        """estimated bits of y per image under each quality of qs (at most 16) -> f32 [B, len(qs)] on the device: one
+        ops.gauss_rate_sweep over the step vectors"""
+        steps = torch.stack([self._step(q, "rate_sweep") for q in qs])
+        return ops.gauss_rate_sweep(y, means, scales_hat, steps)
+
+    def _compress_to_target(self, y, means, scales_hat, z_strings, target_bytes):
+        """THE BYTE BUDGET: the finest of 16 evenly spaced qualities whose estimate plus the z bytes fits every image, then the encode;
+        while an image's actual bytes exceed the target, the next coarser candidate — 16 encodes at most -> (y strings, q)"""
+        who = f"{type(self).__name__}.compress"
+        qs = self.y_step.candidates(16)
+        z_bytes = np.array([len(s) for s in z_strings], dtype=np.float64)
+        est = self.rate_sweep(y, means, scales_hat, qs).double().cpu().numpy() / 8.0 + z_bytes[:, None]   # [B, 16] bytes
+        fits = (est <= target_bytes).all(axis=0)
+        k = int(np.nonzero(fits)[0].max()) if fits.any() else 0
+        while True:
+            y_strings = self._encode_y(y, means, scales_hat, self._step(qs[k], "compress"))
+            sizes = [len(a) + len(b) for a, b in zip(y_strings, z_strings)]
+            if max(sizes) <= target_bytes:
+                return y_strings, qs[k]
+            if k == 0:
+                raise ValueError(f"{who}: target_bytes={target_bytes} is out of reach: at the coarsest step (q=0) the images take "
+                                 f"{sizes} bytes, of which z takes {[len(s) for s in z_strings]}")
+            k -= 1
+
     @torch.no_grad()
-    def compress(self, x):
+    def compress(self, x, q=None, target_bytes=None):
+        """q: the quality (see forward); target_bytes=T: the finest quality at which y and z of EVERY image of the batch fit T bytes
+        together (the chosen q is in the result; ValueError naming the sizes if the coarsest does not fit).  The result carries "q"
+        when a step was used; pass it to decompress."""
+        who = f"{type(self).__name__}.compress"
+        if q is not None and target_bytes is not None:
+            raise ValueError(f"{who}: q and target_bytes exclude each other (got q={q!r}, target_bytes={target_bytes!r})")
+        if target_bytes is not None:
+            if isinstance(target_bytes, bool) or not isinstance(target_bytes, int) or target_bytes < 1:
+                raise ValueError(f"{who}: target_bytes must be a positive int, the bytes of one image (got {target_bytes!r})")
+            if getattr(self, "y_step", None) is None:
+                raise ValueError(f"{who}: target_bytes={target_bytes} needs a step table — build the model with rate_levels > 0")
+        step = self._step(q, "compress")
         x = self._prep(x)
         y = self._analysis(x)
         z = self._hyper_analysis(y)
         z_strings = self.entropy_bottleneck.compress(z)
         z_hat = self.entropy_bottleneck.decompress(z_strings, z.size()[-2:])
         scales_hat, means_hat = self._params(z_hat)
-        gc = self.gaussian_conditional
-        cdf, ln, off = gc.host_tables()
-        sym, idx, _ = gc.quantize_and_index(y, means_hat if means_hat is not None else self._zeros_like(y), scales_hat)
-        sym = sym.contiguous().cpu().numpy()   # [N, C, H, W]: the element order of CompressAI's symbols[i].reshape(-1)
-        idx = idx.contiguous().cpu().numpy()
-        y_strings = [ans.encode(sym[i].reshape(-1), idx[i].reshape(-1), cdf, ln, off) for i in range(sym.shape[0])]
-        return coded_item(y_strings, z_strings, z.size()[-2:])
+        means = means_hat if means_hat is not None else self._zeros_like(y)
+        if target_bytes is not None:
+            y_strings, q = self._compress_to_target(y, means, scales_hat, z_strings, target_bytes)
+            return coded_item(y_strings, z_strings, z.size()[-2:], q=q)
+        y_strings = self._encode_y(y, means, scales_hat, step)
+        return coded_item(y_strings, z_strings, z.size()[-2:]) if step is None else coded_item(y_strings, z_strings, z.size()[-2:], q=q)
 
     @torch.no_grad()
-    def decompress(self, strings, shape):
+    def decompress(self, strings, shape, q=None):
+        step = self._step(q, "decompress")
         assert isinstance(strings, (list, tuple)) and len(strings) == 2
         z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
         scales_hat, means_hat = self._params(z_hat)
         gc = self.gaussian_conditional
         cdf, ln, off = gc.host_tables()
-        idx = gc.build_indexes(scales_hat).contiguous().cpu().numpy()
+        idx = (gc.build_indexes(scales_hat) if step is None else gc.build_indexes(scales_hat, step=step)).contiguous().cpu().numpy()
         out = np.empty(idx.shape, dtype=np.float32)
         for i, s in enumerate(strings[0]):
             out[i] = ans.decode(s, idx[i].reshape(-1), cdf, ln, off).reshape(idx.shape[1:])
         y_hat = torch.from_numpy(out).to(z_hat.device).contiguous(memory_format=CL)
+        if step is not None:   # the encoder's expression: a rounded multiply, then a rounded add
+            y_hat = y_hat * step.reshape(1, -1, 1, 1)
         if means_hat is not None:
             y_hat = y_hat + means_hat
         return {"x_hat": self._synthesis(y_hat).clamp_(0, 1)}
@@ -256,6 +323,7 @@ class JointAutoregressiveHierarchicalPriors(CodeInputs, MeanScaleHyperprior):
     stream, one raster pixel at a time for the whole batch."""
 
     def __init__(self, N=192, M=192, **kwargs):
+        refuse_rate_levels(type(self).__name__, kwargs)   # the context models code y under the unit step only
         if M % 12:
             raise ValueError(f"{type(self).__name__} needs M % 12 == 0 (then 10M/3, 8M/3 and 3M/2 are whole and multiples of 4, the "
                              f"kernels' aligned path); got M = {M}" + (": M = 320 (mbt2018 qualities 5-8) is not built" if M == 320 else ""))

@@ -40,6 +40,7 @@ from ..entropy_models import EntropyBottleneck, GaussianConditional
 from ..layers import conv, deconv
 from ..ops import ACT_NONE, ACT_RELU, CL
 from ..scale_space import gaussian_taps, scale_space_volume, scale_space_warp
+from ..vbr import StepTable, check_quality, frame_qualities, model_step
 from .clc import CompressionModel, _resize_registered_buffers
 from .coding import (check_stream_ends, device_ends, lanes_check, lanes_count, lanes_parse, lanes_strings, refuse_lanes_strings,
                      upload_streams)
@@ -136,37 +137,65 @@ class HyperDecoderWithQReLU(nn.Module):
 
 
 class Hyperprior(CompressionModel):
-    """mean-scale hyperprior of one latent: y -> (y_hat, {"y", "z"} likelihoods); compress / decompress on the host rANS coder"""
+    """mean-scale hyperprior of one latent: y -> (y_hat, {"y", "z"} likelihoods); compress / decompress on the host rANS coder.
+    rate_levels > 0 (VARIABLE RATE): a StepTable ``y_step`` for the latent, and ``q`` on forward / compress / decompress —
+    the quality, a float in [0, rate_levels - 1]; q=None is the fixed-rate path with today's launches."""
 
-    def __init__(self, planes=192, mid_planes=192):
+    def __init__(self, planes=192, mid_planes=192, rate_levels=0):
         super().__init__(entropy_bottleneck_channels=mid_planes)
+        if int(rate_levels) < 0:
+            raise ValueError(f"Hyperprior: rate_levels must not be negative (got {rate_levels})")
+        if int(rate_levels):
+            self.y_step = StepTable(planes, int(rate_levels))
         self.hyper_encoder = HyperEncoder(planes, mid_planes, planes)
         self.hyper_decoder_mean = HyperDecoder(planes, mid_planes, planes)
         self.hyper_decoder_scale = HyperDecoderWithQReLU(planes, mid_planes, planes)
         self.gaussian_conditional = GaussianConditional(None)
 
-    def forward(self, y):
+    def forward(self, y, q=None):
+        step = model_step(self, q, "Hyperprior.forward")
         z = self.hyper_encoder(y)
         z_hat, z_likelihoods = self.entropy_bottleneck(z)
         scales = self.hyper_decoder_scale(z_hat)
         means = self.hyper_decoder_mean(z_hat)
         # (likelihood of the noisy / dequantised y, ste_round(y - means) + means) in one kernel
-        y_likelihoods, y_hat = self.gaussian_conditional.likelihood_and_ste(y, scales, means)
+        if step is None:
+            y_likelihoods, y_hat = self.gaussian_conditional.likelihood_and_ste(y, scales, means)
+        else:
+            y_likelihoods, y_hat = self.gaussian_conditional.likelihood_and_ste(y, scales, means, step=step)
         return y_hat, {"y": y_likelihoods, "z": z_likelihoods}
 
+    @staticmethod
+    def _dequantise(sym, means, step):
+        """y_hat from decoded symbols, as every side of the codec forms it in torch ops: (float)symbol + mean, and under a step
+        (float)symbol * step + mean as two rounded operations — clc_quantize_build_indexes_step's expression"""
+        vals = sym.to(torch.float32)
+        if step is not None:
+            vals = vals * step.reshape(1, -1, 1, 1)
+        return vals + means
+
     @torch.no_grad()
-    def compress(self, y, lanes=None):
+    def rate_sweep(self, y, qs):
+        """estimated bits of y per image under each quality of qs (at most 16) -> f32 [B, len(qs)] on the device, one
+        ops.gauss_rate_sweep: what a per-frame byte budget would be chosen from (z's bits are not in it)"""
+        steps = torch.stack([model_step(self, q, "Hyperprior.rate_sweep") for q in qs])
+        z_hat, _ = self.entropy_bottleneck(self.hyper_encoder(y), training=False)
+        return ops.gauss_rate_sweep(y, self.hyper_decoder_mean(z_hat), self.hyper_decoder_scale(z_hat), steps)
+
+    @torch.no_grad()
+    def compress(self, y, lanes=None, q=None):
         """lanes=None: one host-coded y stream per image.  lanes=W: the lanes stream, one segment of the latent's symbols in NHWC
-        order, encoded on the device (two downloads: the header, the packed words); pass the same W to decompress."""
+        order, encoded on the device (two downloads: the header, the packed words); pass the same W — and the same q — to decompress."""
         Wn = lanes_count(lanes, "Hyperprior.compress")
+        step = model_step(self, q, "Hyperprior.compress")
         z = self.hyper_encoder(y)
         z_strings = self.entropy_bottleneck.compress(z)
         z_hat = self.entropy_bottleneck.decompress(z_strings, z.size()[-2:])
         scales = self.hyper_decoder_scale(z_hat)
         means = self.hyper_decoder_mean(z_hat)
         gc = self.gaussian_conditional
-        sym, idx, _ = gc.quantize_and_index(y, means, scales)
-        y_hat = sym.to(torch.float32) + means   # formed as decompress forms it: the two sides run one chain
+        sym, idx, _ = gc.quantize_and_index(y, means, scales) if step is None else gc.quantize_and_index(y, means, scales, step=step)
+        y_hat = self._dequantise(sym, means, step)   # formed as decompress forms it: the two sides run one chain
         if Wn is not None:   # the int32 buffers stay on the device
             return y_hat, {"strings": [self._lanes_y_strings(sym, idx, Wn), z_strings], "shape": z.size()[-2:]}
         cdf, ln, off = gc.host_tables()
@@ -187,7 +216,7 @@ class Hyperprior(CompressionModel):
         words = packed[:int(head[B * W])].cpu().numpy() if (head[:B * W] >= 0).all() else np.zeros(0, np.int32)
         return lanes_strings(head, words, B, W)   # (raises by name on a negative code)
 
-    def _decode_lanes(self, subs, z_strings, shape, device_coder=True, out=None):
+    def _decode_lanes(self, subs, z_strings, shape, device_coder=True, out=None, step=None):
         """The decoder over parsed lanes streams (subs[b][w]: bytes; coding.lanes_parse) -> (y_hat, state).  The z strings are decoded
         on the host and uploaded, which waits on nothing the device computes.
         device_coder: one pinned upload of every wave stream's states, spans and words, the two hyper-decoder chains and ONE
@@ -204,43 +233,51 @@ class Hyperprior(CompressionModel):
         means = self.hyper_decoder_mean(z_hat)
         if device_coder:
             tables = (gc._quantized_cdf, gc._cdf_length, gc._offset)
-            return ops.rans_lanes_decode_gauss(scales, means, gc.scale_table, tables, words, spans, state, y_hat=out), state
+            if step is None:
+                return ops.rans_lanes_decode_gauss(scales, means, gc.scale_table, tables, words, spans, state, y_hat=out), state
+            return ops.rans_lanes_decode_gauss(scales, means, gc.scale_table, tables, words, spans, state, y_hat=out, step=step), state
         decoders = [ans.LanesDecoder(img) for img in subs]
         cdf, ln, off = gc.host_tables()
-        idx = gc.build_indexes(scales).permute(0, 2, 3, 1).contiguous().cpu().numpy()   # NHWC: the segment's order
+        idx = gc.build_indexes(scales) if step is None else gc.build_indexes(scales, step=step)
+        idx = idx.permute(0, 2, 3, 1).contiguous().cpu().numpy()   # NHWC: the segment's order
         sym = np.stack([d.decode(idx[b].reshape(-1), cdf, ln, off).reshape(idx.shape[1:]) for b, d in enumerate(decoders)])
-        y_hat = torch.from_numpy(sym).to(z_hat.device).permute(0, 3, 1, 2).to(torch.float32) + means
+        y_hat = self._dequantise(torch.from_numpy(sym).to(z_hat.device).permute(0, 3, 1, 2), means, step)
         return (y_hat if out is None else out.copy_(y_hat)), decoders
 
     @torch.no_grad()
-    def decompress(self, strings, shape, lanes=None, device_coder=True, out=None):
+    def decompress(self, strings, shape, lanes=None, device_coder=True, out=None, q=None):
         """lanes=None: the one-stream format, one hop.  lanes=W: the lanes stream of compress(y, lanes=W), its headers parsed before
         any device work; device_coder=False decodes the same format on the host coder (ans.LanesDecoder): the oracle and the
         fallback.  out: the pixel-major map y_hat is written into (the lanes kernel writes it in place at its leading dimension)."""
         Wn = lanes_count(lanes, "Hyperprior.decompress")
+        step = model_step(self, q, "Hyperprior.decompress")
         assert isinstance(strings, (list, tuple)) and len(strings) == 2
         if Wn is not None:
-            return self._decode_lanes(lanes_parse(strings[0], Wn), strings[1], shape, device_coder, out)[0]
+            return self._decode_lanes(lanes_parse(strings[0], Wn), strings[1], shape, device_coder, out, step)[0]
         refuse_lanes_strings(strings[0])
         z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
         scales = self.hyper_decoder_scale(z_hat)
         means = self.hyper_decoder_mean(z_hat)
         gc = self.gaussian_conditional
         cdf, ln, off = gc.host_tables()
-        idx = gc.build_indexes(scales).contiguous().cpu().numpy()
+        idx = (gc.build_indexes(scales) if step is None else gc.build_indexes(scales, step=step)).contiguous().cpu().numpy()
         sym = np.empty(idx.shape, dtype=np.float32)
         for i, s in enumerate(strings[0]):
             sym[i] = ans.decode(s, idx[i].reshape(-1), cdf, ln, off).reshape(idx.shape[1:])
-        y_hat = torch.from_numpy(sym).to(z_hat.device).contiguous(memory_format=CL) + means
+        y_hat = self._dequantise(torch.from_numpy(sym).to(z_hat.device).contiguous(memory_format=CL), means, step)
         return y_hat if out is None else out.copy_(y_hat)
 
 
 class ScaleSpaceFlow(CompressionModel):
     """ScaleSpaceFlow(num_levels=5, sigma0=1.5, scale_field_shift=1.0): ``scale_field_shift`` is stored and unused, as in CompressAI.
-    mid_planes / planes (multiples of 4; 128 / 192 in the published model) size the sub-networks."""
+    mid_planes / planes (multiples of 4; 128 / 192 in the published model) size the sub-networks.
+    rate_levels > 0 (VARIABLE RATE): one StepTable inside each of the three hyperpriors, and ``q`` on forward / compress /
+    decompress: a float for every frame or a list of one float per frame; one q serves both latents of a P-frame."""
 
-    def __init__(self, num_levels=5, sigma0=1.5, scale_field_shift=1.0, mid_planes=128, planes=192):
+    def __init__(self, num_levels=5, sigma0=1.5, scale_field_shift=1.0, mid_planes=128, planes=192, rate_levels=0):
         super().__init__()
+        if int(rate_levels) < 0:
+            raise ValueError(f"ScaleSpaceFlow: rate_levels must not be negative (got {rate_levels})")
         if int(num_levels) != num_levels or num_levels < 1:
             raise ValueError(f"ScaleSpaceFlow: num_levels must be an integer >= 1 (got num_levels={num_levels})")
         if num_levels > 8:
@@ -251,13 +288,13 @@ class ScaleSpaceFlow(CompressionModel):
                              f"mid_planes={mid_planes}, planes={planes}")
         self.img_encoder = Encoder(3, mid_planes, planes)
         self.img_decoder = Decoder(3, planes, mid_planes)
-        self.img_hyperprior = Hyperprior(planes, planes)
+        self.img_hyperprior = Hyperprior(planes, planes, rate_levels)
         self.res_encoder = Encoder(3, mid_planes, planes, input_grad=True)
         self.res_decoder = Decoder(3, 2 * planes, mid_planes)
-        self.res_hyperprior = Hyperprior(planes, planes)
+        self.res_hyperprior = Hyperprior(planes, planes, rate_levels)
         self.motion_encoder = Encoder(2 * 3, mid_planes, planes, input_grad=True)
         self.motion_decoder = Decoder(2 + 1, planes, mid_planes)
-        self.motion_hyperprior = Hyperprior(planes, planes)
+        self.motion_hyperprior = Hyperprior(planes, planes, rate_levels)
         self.sigma0 = float(sigma0)
         self.num_levels = int(num_levels)
         self.scale_field_shift = scale_field_shift
@@ -286,44 +323,56 @@ class ScaleSpaceFlow(CompressionModel):
         volume = scale_space_volume(x_ref, self.sigma0, self.num_levels)
         return scale_space_warp(volume, info[:, :2], info[:, 2:3])
 
+    def _qualities(self, q, frames, who):
+        """one checked quality per frame (None: the fixed-rate path) — before any device work"""
+        qs = frame_qualities(q, frames, f"ScaleSpaceFlow.{who}")
+        for t, qt in enumerate(qs):
+            if qt is not None:
+                check_quality(self.img_hyperprior, qt, f"ScaleSpaceFlow.{who} (frame {t})")
+        return qs
+
     # ---- training / evaluation forward ----
-    def forward(self, frames):
+    def forward(self, frames, q=None):
+        qs = self._qualities(q, len(frames) if isinstance(frames, (list, tuple)) else 0, "forward")
         frames = self._prep(frames)
-        x_hat, lik = self.forward_keyframe(frames[0])
+        x_hat, lik = self.forward_keyframe(frames[0], qs[0])
         recs, liks = [x_hat], [lik]
         x_ref = x_hat.detach()
-        for x in frames[1:]:
-            x_ref, lik = self.forward_inter(x, x_ref)
+        for x, qt in zip(frames[1:], qs[1:]):
+            x_ref, lik = self.forward_inter(x, x_ref, qt)
             recs.append(x_ref)
             liks.append(lik)
         return {"x_hat": recs, "likelihoods": liks}
 
-    def forward_keyframe(self, x):
-        y_hat, lik = self.img_hyperprior(self.img_encoder(x))
+    def forward_keyframe(self, x, q=None):
+        y_hat, lik = self.img_hyperprior(self.img_encoder(x)) if q is None else self.img_hyperprior(self.img_encoder(x), q=q)
         return self.img_decoder(y_hat), {"keyframe": lik}
 
-    def forward_inter(self, x_cur, x_ref):
-        y_m_hat, m_lik = self.motion_hyperprior(self.motion_encoder(torch.cat((x_cur, x_ref), dim=1)))
+    def forward_inter(self, x_cur, x_ref, q=None):
+        kw = {} if q is None else {"q": q}
+        y_m_hat, m_lik = self.motion_hyperprior(self.motion_encoder(torch.cat((x_cur, x_ref), dim=1)), **kw)
         x_pred = self._predict(x_ref, y_m_hat)
-        y_r_hat, r_lik = self.res_hyperprior(self.res_encoder(x_cur - x_pred))
+        y_r_hat, r_lik = self.res_hyperprior(self.res_encoder(x_cur - x_pred), **kw)
         x_rec = x_pred + self.res_decoder(torch.cat((y_r_hat, y_m_hat), dim=1))
         return x_rec, {"motion": m_lik, "residual": r_lik}
 
     # ---- codec ----
     @torch.no_grad()
-    def compress(self, frames, lanes=None):
+    def compress(self, frames, lanes=None, q=None):
         """-> (frame_strings, shape_infos): the keyframe's [y_strings, z_strings] and z size, then per frame
         {"motion": [y, z], "residual": [y, z]} and {"motion": z size, "residual": z size}.  lanes=W: every y string is the lanes
-        stream (Hyperprior.compress); pass the same W to decompress."""
+        stream (Hyperprior.compress); pass the same W to decompress.  q: the quality, one float or one per frame (needs
+        rate_levels > 0); the strings do not carry it — pass the same q to decompress (frames.encode_yuv420 stores it)."""
         Wn = lanes_count(lanes, "ScaleSpaceFlow.compress")
+        qs = self._qualities(q, len(frames) if isinstance(frames, (list, tuple)) else 0, "compress")
         frames = self._prep(frames)
-        y_hat, item = self.img_hyperprior.compress(self.img_encoder(frames[0]), lanes=Wn)
+        y_hat, item = self.img_hyperprior.compress(self.img_encoder(frames[0]), lanes=Wn, q=qs[0])
         x_ref = self.img_decoder(y_hat)
         frame_strings, shape_infos = [item["strings"]], [item["shape"]]
-        for x in frames[1:]:
-            y_m_hat, m = self.motion_hyperprior.compress(self.motion_encoder(torch.cat((x, x_ref), dim=1)), lanes=Wn)
+        for x, qt in zip(frames[1:], qs[1:]):
+            y_m_hat, m = self.motion_hyperprior.compress(self.motion_encoder(torch.cat((x, x_ref), dim=1)), lanes=Wn, q=qt)
             x_pred = self._predict(x_ref, y_m_hat)
-            y_r_hat, r = self.res_hyperprior.compress(self.res_encoder(x - x_pred), lanes=Wn)
+            y_r_hat, r = self.res_hyperprior.compress(self.res_encoder(x - x_pred), lanes=Wn, q=qt)
             x_ref = x_pred + self.res_decoder(torch.cat((y_r_hat, y_m_hat), dim=1))
             frame_strings.append({"motion": m["strings"], "residual": r["strings"]})
             shape_infos.append({"motion": m["shape"], "residual": r["shape"]})
@@ -337,7 +386,7 @@ class ScaleSpaceFlow(CompressionModel):
         return [(k, strings[k], shapes[k]) for k in ("motion", "residual")]
 
     @torch.no_grad()
-    def _decompress_lanes(self, frame_strings, shape_infos, Wn, device_coder, check):
+    def _decompress_lanes(self, frame_strings, shape_infos, Wn, device_coder, check, qs):
         parsed = []   # every frame's headers, before any device work
         for t, (strings, shapes) in enumerate(zip(frame_strings, shape_infos)):
             row = []
@@ -349,7 +398,11 @@ class ScaleSpaceFlow(CompressionModel):
             parsed.append(row)
         ends = []   # (frame, latent, wave streams, coder state) of every latent
         (name, subs, zs, shape), = parsed[0]
-        y_hat, state = self.img_hyperprior._decode_lanes(subs, zs, shape, device_coder)
+        # the step vectors each frame needs — the keyframe's one, a later frame's (motion, residual) — None without q
+        steps = [(model_step(self.img_hyperprior, qt, "ScaleSpaceFlow.decompress"),) if t == 0 else
+                 tuple(model_step(h, qt, "ScaleSpaceFlow.decompress") for h in (self.motion_hyperprior, self.res_hyperprior))
+                 for t, qt in enumerate(qs)]
+        y_hat, state = self.img_hyperprior._decode_lanes(subs, zs, shape, device_coder, step=steps[0][0])
         ends.append((0, name, subs, state))
         x_ref = self.img_decoder(y_hat)
         recs = [x_ref]
@@ -359,10 +412,10 @@ class ScaleSpaceFlow(CompressionModel):
             # ONE [B, 2 planes, h, w] buffer per frame, (residual | motion): each latent is decoded into its half, no torch.cat
             both = torch.empty((len(m_subs), 2 * P, 8 * int(m_shape[0]), 8 * int(m_shape[1])), device=x_ref.device, dtype=torch.float32,
                                memory_format=CL)
-            y_m_hat, state = self.motion_hyperprior._decode_lanes(m_subs, m_zs, m_shape, device_coder, out=both[:, P:])
+            y_m_hat, state = self.motion_hyperprior._decode_lanes(m_subs, m_zs, m_shape, device_coder, out=both[:, P:], step=steps[t][0])
             ends.append((t, mn, m_subs, state))
             x_pred = self._predict(x_ref, y_m_hat)
-            _, state = self.res_hyperprior._decode_lanes(r_subs, r_zs, r_shape, device_coder, out=both[:, :P])
+            _, state = self.res_hyperprior._decode_lanes(r_subs, r_zs, r_shape, device_coder, out=both[:, :P], step=steps[t][1])
             ends.append((t, rn, r_subs, state))
             x_ref = x_pred + self.res_decoder(both)
             recs.append(x_ref)
@@ -389,7 +442,7 @@ class ScaleSpaceFlow(CompressionModel):
                 raise ValueError(f"frame {t}, {name} latent: {e}") from None
 
     @torch.no_grad()
-    def decompress(self, frame_strings, shape_infos, lanes=None, device_coder=True, check=True):
+    def decompress(self, frame_strings, shape_infos, lanes=None, device_coder=True, check=True, q=None):
         """-> the list of reconstructions, unclamped as forward returns them.  lanes=None: the default format, one hop per latent
         (2 F - 1 for F frames).  lanes=W: the strings of compress(frames, lanes=W); every frame's headers are parsed first, and with
         device_coder=True there is no device -> host copy and no synchronize between the keyframe's first launch and the last
@@ -399,17 +452,18 @@ class ScaleSpaceFlow(CompressionModel):
         Wn = lanes_count(lanes, "ScaleSpaceFlow.decompress")
         if len(frame_strings) < 1 or len(frame_strings) != len(shape_infos):
             raise ValueError(f"ScaleSpaceFlow.decompress: {len(frame_strings)} frame strings for {len(shape_infos)} shape infos (at least one of each)")
+        qs = self._qualities(q, len(frame_strings), "decompress")
         if Wn is not None:
-            return self._decompress_lanes(frame_strings, shape_infos, Wn, device_coder, check)
+            return self._decompress_lanes(frame_strings, shape_infos, Wn, device_coder, check, qs)
         for t, (strings, shapes) in enumerate(zip(frame_strings, shape_infos)):
             for _name, s, _shape in self._latents(t, strings, shapes):
                 refuse_lanes_strings(s[0])
-        x_ref = self.img_decoder(self.img_hyperprior.decompress(frame_strings[0], shape_infos[0]))
+        x_ref = self.img_decoder(self.img_hyperprior.decompress(frame_strings[0], shape_infos[0], q=qs[0]))
         recs = [x_ref]
-        for strings, shapes in zip(frame_strings[1:], shape_infos[1:]):
-            y_m_hat = self.motion_hyperprior.decompress(strings["motion"], shapes["motion"])
+        for strings, shapes, qt in zip(frame_strings[1:], shape_infos[1:], qs[1:]):
+            y_m_hat = self.motion_hyperprior.decompress(strings["motion"], shapes["motion"], q=qt)
             x_pred = self._predict(x_ref, y_m_hat)
-            y_r_hat = self.res_hyperprior.decompress(strings["residual"], shapes["residual"])
+            y_r_hat = self.res_hyperprior.decompress(strings["residual"], shapes["residual"], q=qt)
             x_ref = x_pred + self.res_decoder(torch.cat((y_r_hat, y_m_hat), dim=1))
             recs.append(x_ref)
         return recs

@@ -2252,6 +2252,131 @@ def quantize_build_indexes(y, mu, scale, scale_table):
     return sym.permute(0, 3, 1, 2), idx.permute(0, 3, 1, 2), y_hat
 
 
+# ---- the quantisation step (variable-rate coding; csrc/qstep.hip): step [C] > 0, one per channel ----
+
+
+def _step_vector(step, Cc, like, who):
+    """the one check of a step vector: a contiguous f32 [C] on the latent's device; refused by name otherwise"""
+    return _step_tensor(step, (Cc,), like, who, "step")
+
+
+def _step_tensor(step, shape, like, who, name):
+    if not isinstance(step, torch.Tensor):
+        raise TypeError(f"{who}: {name} must be a tensor of one quantisation step per channel (got {type(step).__name__})")
+    if tuple(step.shape) != tuple(shape):
+        raise ValueError(f"{who}: {name} must have shape {list(shape)}, one step per channel (got {list(step.shape)})")
+    if step.dtype != torch.float32:
+        raise ValueError(f"{who}: {name} must be float32 (got {step.dtype})")
+    _require_gpu(like, who)
+    if step.device != like.device:
+        raise ValueError(f"{who}: {name} is on {step.device}, the latent on {like.device}")
+    return step.contiguous()
+
+
+def _step_candidates(steps, Cc, like, who):
+    """the check of a rate sweep's candidates: [K, C] of 1 <= K <= 16 step vectors"""
+    if not isinstance(steps, torch.Tensor) or steps.dim() != 2:
+        raise ValueError(f"{who}: steps must be a [K, C] tensor of candidate step vectors")
+    if not 1 <= steps.shape[0] <= 16:
+        raise ValueError(f"{who}: between 1 and 16 candidates per launch (got K={steps.shape[0]})")
+    return _step_tensor(steps, (steps.shape[0], Cc), like, who, "steps")
+
+
+class _GaussLikStepFn(Function):
+    """_GaussLikFn with a quantisation step per channel, a differentiable input."""
+
+    @staticmethod
+    def forward(ctx, y, scale, mu, step, noise, training):
+        y, yp, N, H, W, Cc, ldy = nhwc(y)
+        scale, sp, *_a, ldsc = nhwc(scale)
+        mu, mp, *_b, ldmu = nhwc(mu)
+        rows = N * H * W
+        lik = new_act(N, Cc, H, W, y)
+        y_hat = new_act(N, Cc, H, W, y)
+        npn, ldn = (None, 0)
+        if training:
+            noise, npn, *_c, ldn = nhwc(noise)
+        _lib.check(_L().clc_gauss_lik_step_fwd(yp, ldy, mp, ldmu, sp, ldsc, npn, ldn, step.data_ptr(), lik.data_ptr(), Cc, y_hat.data_ptr(), Cc,
+                                               rows, Cc, 0 if training else 1, None, 0, _stream()), "clc_gauss_lik_step_fwd")
+        ctx.training = training
+        ctx.save_for_backward(y, scale, mu, step, noise if training else None)
+        return lik, y_hat
+
+    @staticmethod
+    def backward(ctx, dlik, dyhat):
+        y, scale, mu, step, noise = ctx.saved_tensors
+        y, yp, N, H, W, Cc, ldy = nhwc(y)
+        scale, sp, *_a, ldsc = nhwc(scale)
+        mu, mp, *_b, ldmu = nhwc(mu)
+        if dlik is None:   # only y_hat was used downstream
+            dlik = torch.zeros((N, Cc, H, W), device=y.device, dtype=torch.float32).contiguous(memory_format=CL)
+        dlik, dlp, *_c, lddl = nhwc(dlik)
+        rows = N * H * W
+        npn, ldn = (None, 0)
+        if ctx.training:
+            noise, npn, *_d, ldn = nhwc(noise)
+        dy = new_act(N, Cc, H, W, y) if ctx.training else None
+        both = new_act(2 * N, Cc, H, W, y)   # (d(mu) and d(scale) as the halves of one buffer, as in _GaussLikFn)
+        dmu = both[:N] if ctx.training else None
+        dsc = both[N:]
+        dstep = torch.empty(Cc, device=y.device, dtype=torch.float32)
+        hat_p, ldg = None, 0
+        if dyhat is not None:
+            dyhat, hat_p, *_e, ldg = nhwc(dyhat)
+        nbytes = _L().clc_gauss_lik_step_bwd_workspace_bytes(rows, Cc)
+        ws = torch.empty(max(nbytes // 4, 1), device=y.device, dtype=torch.float32)
+        _lib.check(_L().clc_gauss_lik_step_bwd(dlp, lddl, yp, ldy, mp, ldmu, sp, ldsc, npn, ldn, step.data_ptr(),
+                                               dy.data_ptr() if dy is not None else None, Cc, dmu.data_ptr() if dmu is not None else None, Cc,
+                                               dsc.data_ptr(), Cc, dstep.data_ptr(), rows, Cc, 0 if ctx.training else 1, hat_p, ldg,
+                                               ws.data_ptr(), nbytes, _stream()), "clc_gauss_lik_step_bwd")
+        if dy is None:   # eval: y reaches the loss through the straight-through y_hat only
+            dy = dyhat
+        return dy, dsc, dmu, dstep, None, None
+
+
+def gaussian_likelihood_step(y, scale, mu, step, noise, training):
+    """-> (likelihood, y_hat) under the quantisation step ``step`` [C] (differentiable): y_hat = step * ste_round((y - mu) / step) + mu,
+    the likelihood of the bin of width step around it (training: around y + step * noise).  step == 1: ops.gaussian_likelihood's bits."""
+    step = _step_vector(step, y.shape[1], y, "gaussian_likelihood_step")
+    return _GaussLikStepFn.apply(y, scale, mu, step, noise, bool(training))
+
+
+def quantize_build_indexes_step(y, mu, scale, scale_table, step):
+    """quantize_build_indexes under a step: symbols = rint((y - mu) / step), indexes = the table row of max(scale, 0.11) / step,
+    y_hat = symbols * step + mu (a rounded multiply, a rounded add) — the encoder's and the decoder's one expression."""
+    step = _step_vector(step, y.shape[1], y, "quantize_build_indexes_step").detach()
+    y, yp, N, H, W, Cc, ldy = nhwc(y)
+    mu, mp, *_a, ldmu = nhwc(mu)
+    scale, sp, *_b, ldsc = nhwc(scale)
+    rows = N * H * W
+    sym = torch.empty((N, H, W, Cc), device=y.device, dtype=torch.int32)
+    idx = torch.empty((N, H, W, Cc), device=y.device, dtype=torch.int32)
+    y_hat = new_act(N, Cc, H, W, y)
+    _lib.check(_L().clc_quantize_build_indexes_step(yp, ldy, mp, ldmu, sp, ldsc, step.data_ptr(), scale_table.data_ptr(), scale_table.numel(),
+                                                    sym.data_ptr(), idx.data_ptr(), y_hat.data_ptr(), Cc, rows, Cc, _stream()),
+               "clc_quantize_build_indexes_step")
+    return sym.permute(0, 3, 1, 2), idx.permute(0, 3, 1, 2), y_hat
+
+
+def gauss_rate_sweep(y, mu, scale, steps):
+    """The estimated bits of every image of y [B, C, H, W] under each of K candidate step vectors steps [K, C], one launch pair ->
+    f32 [B, K] = - sum log2 of the eval likelihood.  Column k equals the K = 1 call with that candidate and image b alone equals image b
+    of the batch, bit for bit."""
+    steps = _step_candidates(steps, y.shape[1], y, "gauss_rate_sweep").detach()
+    K = steps.shape[0]
+    y, yp, N, H, W, Cc, ldy = nhwc(y)
+    mu, mp, *_a, ldmu = nhwc(mu)
+    scale, sp, *_b, ldsc = nhwc(scale)
+    bits = torch.empty((N, K), device=y.device, dtype=torch.float32)
+    nbytes = _L().clc_gauss_rate_sweep_workspace_bytes(N, H * W, Cc, K)
+    if nbytes == 0:
+        _lib.check(-1, "clc_gauss_rate_sweep_workspace_bytes")
+    ws = torch.empty(nbytes // 4, device=y.device, dtype=torch.float32)
+    _lib.check(_L().clc_gauss_rate_sweep(yp, ldy, mp, ldmu, sp, ldsc, steps.data_ptr(), K, N, H * W, Cc, bits.data_ptr(), ws.data_ptr(), nbytes,
+                                         _stream()), "clc_gauss_rate_sweep")
+    return bits
+
+
 # --------------------------------------------------------------------------------- RD loss pieces
 
 
@@ -3138,19 +3263,23 @@ def rans_lanes_encode_list(symbols, indexes, segments, W, tables, out=None, regi
     return out, regions, result
 
 
-def rans_lanes_decode_gauss(scale, mu, scale_table, tables, words, spans, state, y_hat=None, symbols=None):
+def rans_lanes_decode_gauss(scale, mu, scale_table, tables, words, spans, state, y_hat=None, symbols=None, step=None):
     """clc_rans_lanes_decode_gauss: the next segment of the lanes stream for a Gaussian-conditional slice — what quantize_build_indexes'
     index half, rans_lanes_decode_step, the int -> float conversion and the add of the mean do, in one launch.  scale / mu: float maps
     [B, C, H, W] stored pixel-major (any leading dimension); the segment holds each image's n = H W C symbols, pixels in raster order with
     channels inner.  scale_table: the non-decreasing float table [2 .. 256] of the indexes; tables, words, spans, state as for
     rans_lanes_decode_step.  y_hat: a pixel-major float [B, C, H, W] map to write (default: a new one); symbols: an optional contiguous
-    int32 device tensor of B equal blocks of at least n elements that receives the decoded symbols.  -> y_hat = symbols + mu."""
+    int32 device tensor of B equal blocks of at least n elements that receives the decoded symbols.  -> y_hat = symbols + mu.
+    step [C]: the quantisation step per channel (clc_rans_lanes_decode_gauss_step): the indexes of scale / step and
+    y_hat = symbols * step + mu, quantize_build_indexes_step's expression; None: the unit-step kernel, as before."""
     who = "rans_lanes_decode_gauss"
     for t, what in ((scale, "scale"), (mu, "mu")):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.dim() != 4:
             raise ValueError(f"{who}: {what} must be a float32 [B, C, H, W] device tensor")
     if scale.shape != mu.shape:
         raise ValueError(f"{who}: scale and mu must have one shape (got {tuple(scale.shape)}, {tuple(mu.shape)})")
+    if step is not None:
+        step = _step_vector(step, scale.shape[1], scale, who).detach()
     if (not isinstance(scale_table, torch.Tensor) or scale_table.dtype != torch.float32 or not scale_table.is_cuda
             or not scale_table.is_contiguous() or not 2 <= scale_table.numel() <= 256):
         raise ValueError(f"{who}: scale_table must be a contiguous float32 device tensor of 2 .. 256 entries")
@@ -3178,6 +3307,11 @@ def rans_lanes_decode_gauss(scale, mu, scale_table, tables, words, spans, state,
             raise ValueError(f"{who}: symbols must be a contiguous int32 device tensor of B = {B} equal image blocks of at least n = {n} elements")
         symp, lds = symbols.data_ptr(), symbols.numel() // B
     if n == 0:
+        return y_hat
+    if step is not None:
+        _lib.check(_L().clc_rans_lanes_decode_gauss_step(sp, ldsc, mp, ldmu, step.data_ptr(), Cc, n, B, scale_table.data_ptr(), scale_table.numel(),
+                                                         cp, stride, rows, lp, op, words.data_ptr(), spans.data_ptr(), state.data_ptr(), W, hp, ldh,
+                                                         symp, lds, _stream()), "clc_rans_lanes_decode_gauss_step")
         return y_hat
     _lib.check(_L().clc_rans_lanes_decode_gauss(sp, ldsc, mp, ldmu, Cc, n, B, scale_table.data_ptr(), scale_table.numel(), cp, stride, rows, lp,
                                                 op, words.data_ptr(), spans.data_ptr(), state.data_ptr(), W, hp, ldh, symp, lds, _stream()),

@@ -360,6 +360,45 @@ int clc_quantize_build_indexes(const float* y, int ldy, const float* mu, int ldm
                                const float* scale_table, int n_scales, int32_t* symbols, int32_t* indexes,
                                float* y_hat, int ldh, long rows, int C, clc_stream_t stream);
 
+/* ---- the quantisation step: variable-rate coding on the Gaussian-conditional kernels (csrc/qstep.hip) ----
+ * step[C] > 0: one quantisation step per channel, a contiguous device f32 vector shared by all rows.
+ *   sigma = max(scale, 0.11);  t = (y - mu) / step[c] (true division);  q = rintf(t)
+ *   y_hat = q * step[c] + mu — a rounded multiply followed by a rounded add, never an fmaf (the library is built with contraction off);
+ *           as a differentiable value step * ste_round(t) + mu: d y_hat/dy = 1, d y_hat/dmu = 0, d y_hat/dstep = q - t
+ *   y_in  = y + step[c] * noise (mode 0, training) | y_hat (mode 1, eval);  v = |y_in - mu|
+ *   lik   = max(Phi((step[c] / 2 - v) / sigma) - Phi((-step[c] / 2 - v) / sigma), 1e-9), both LowerBound gradient rules as in clc_gauss_lik_bwd
+ *   INT path: symbol = (int) q;  index = the row of max(scale, 0.11) / step[c] in the scale table (a quotient below table[0] takes row 0,
+ *           one above the last entry or a NaN quotient the last row; fmaxf drops a NaN SCALE, which is coded as 0.11) — a symbol
+ *           round((y - mu) / step) under N(0, sigma^2) is a unit-step symbol under sigma / step, so the unit-step tables serve.  The
+ *           likelihood uses sigma / step as it is; the coder's table clamps it to its first row: the one place the two part company.
+ * With step == 1.0f everywhere every output equals the unit-step entry's, bit for bit.  Every entry is stream-ordered, allocates
+ * nothing, uses no float atomics and can be captured; a refused argument is named in clc_last_error before any launch.
+ *
+ * clc_gauss_lik_step_fwd: clc_gauss_lik_fwd with the step (same outputs, same partials: clc_gauss_lik_partials).
+ * clc_gauss_lik_step_bwd: dy, dmu, dscale as clc_gauss_lik_bwd, and dstep[C] = the sum over all rows of
+ *           g (pa + pb) / (2 sigma)  +  g dlik/dv sign(y_in - mu) w  +  g_hat (q - t),   w = noise (mode 0) | q (mode 1),
+ *   the half width, y_in and y_hat paths (g: dlik after the likelihood bound's rule; g_hat, optional: the upstream gradient of y_hat,
+ *   also added to dy).  dy, dmu may be NULL.  Two fixed stages — per (row block, channel) partials in ws, then four ascending quarter sums added in order — so
+ *   dstep is the same bits run to run.  ws: clc_gauss_lik_step_bwd_workspace_bytes(rows, C) bytes (0 and clc_last_error on bad sizes).
+ * clc_quantize_build_indexes_step: clc_quantize_build_indexes with the INT path above.
+ * clc_gauss_rate_sweep: the estimate of the coded bits of B images under K candidate step vectors in one launch pair:
+ *   bits[b][k] = - sum over image b's rows_per_image rows and C channels of log2 lik (mode 1) under steps[k][C], 1 <= K <= 16.
+ *   y, mu, scale: [B rows_per_image][ld] pixel-major.  The partition and the order of every sum depend on (rows_per_image, C) alone:
+ *   column k of a K-wide call equals the K = 1 call with that candidate, and image b alone equals image b of the batch, bit for bit. */
+int clc_gauss_lik_step_fwd(const float* y, int ldy, const float* mu, int ldmu, const float* scale, int ldsc, const float* noise, int ldn,
+                           const float* step, float* lik, int ldl, float* y_hat, int ldh, long rows, int C, int mode, float* bits_partial,
+                           int n_partials, clc_stream_t stream);
+size_t clc_gauss_lik_step_bwd_workspace_bytes(long rows, int C);
+int clc_gauss_lik_step_bwd(const float* dlik, int lddl, const float* y, int ldy, const float* mu, int ldmu, const float* scale, int ldsc,
+                           const float* noise, int ldn, const float* step, float* dy, int lddy, float* dmu, int lddmu, float* dscale, int lddsc,
+                           float* dstep, long rows, int C, int mode, const float* g_hat, int ldg, void* ws, size_t ws_bytes, clc_stream_t stream);
+int clc_quantize_build_indexes_step(const float* y, int ldy, const float* mu, int ldmu, const float* scale, int ldsc, const float* step,
+                                    const float* scale_table, int n_scales, int32_t* symbols, int32_t* indexes, float* y_hat, int ldh,
+                                    long rows, int C, clc_stream_t stream);
+size_t clc_gauss_rate_sweep_workspace_bytes(int B, long rows_per_image, int C, int K);
+int clc_gauss_rate_sweep(const float* y, int ldy, const float* mu, int ldmu, const float* scale, int ldsc, const float* steps, int K, int B,
+                         long rows_per_image, int C, float* bits /* [B][K] */, void* ws, size_t ws_bytes, clc_stream_t stream);
+
 /* rate / distortion reductions and their gradients (train_CLC.py:43-57). g_dev points at the upstream
  * gradient of the loss (a device scalar), so the backward never reads back to the host. */
 int clc_log2_sum_partials(const float* x, int ld, long rows, int C, float* partials, int n_partials, clc_stream_t stream);
@@ -987,6 +1026,15 @@ int clc_rans_lanes_decode_gauss(const float* scale, long ldsc, const float* mu, 
                                 const int32_t* offsets, const uint32_t* words, const int32_t* spans /* [B][W][2] */,
                                 clc_rans_lanes_state* state /* [B][W] */, int W, float* y_hat, long ldh, int32_t* symbols /* or NULL */,
                                 long ld_sym, clc_stream_t stream);
+/* clc_rans_lanes_decode_gauss under a quantisation step per channel (step[C] > 0, device memory; see the quantisation-step entries above):
+ * the index is that of max(scale, 0.11) / step[c] and y_hat[r ldh + c] = (float)symbol * step[c] + mu[r ldmu + c], a rounded multiply
+ * and a rounded add — clc_quantize_build_indexes_step's expression, bit for bit.  Everything else, argument for argument, is
+ * clc_rans_lanes_decode_gauss's; with step == 1.0f so are the outputs. */
+int clc_rans_lanes_decode_gauss_step(const float* scale, long ldsc, const float* mu, long ldmu, const float* step, int C, int n, int B,
+                                     const float* scale_table, int n_scales, const int32_t* cdfs, int cdf_stride, int n_rows,
+                                     const int32_t* cdf_sizes, const int32_t* offsets, const uint32_t* words, const int32_t* spans /* [B][W][2] */,
+                                     clc_rans_lanes_state* state /* [B][W] */, int W, float* y_hat, long ldh, int32_t* symbols /* or NULL */,
+                                     long ld_sym, clc_stream_t stream);
 int clc_rans_lanes_pack(const uint32_t* words, long n_words, const int32_t* result /* [B][W][2] */, int B, int W, uint32_t* packed,
                         long capacity, int32_t* header /* [B W + 1] */, clc_stream_t stream);
 int clc_ar_lanes_decode(const float* gp, long ldg, int M, const int32_t* pix /* [P][2] */, int P, int B, int H, int W_map,
