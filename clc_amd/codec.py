@@ -86,7 +86,8 @@ def pack(strings, shape, image_hw, n_refs: int = 0, model_id: int = 0, kernel_co
     (default: the state at the time of this call).
     Version 3 (ref_ids given: the references of a clc_amd.refbank.ReferenceBank): the version-2 header, the hash always present, then
     the bank's id and one index into bank.keys per reference; H x W is the size the bank prepared the references at, so the file
-    decodes with the bank alone (CodecEngine.decompress(items, bank=...))."""
+    decodes with the bank alone (CodecEngine.decompress(items, bank=...)).
+    Version 4 (pack_exact) is the stream of an integer entropy model and is bound to no kernel generation."""
     y, z = strings[0][0], strings[1][0]
     tag, h = kernel_config_ if kernel_config_ is not None else kernel_config()
     if ref_ids is not None:
@@ -105,9 +106,27 @@ def pack(strings, shape, image_hw, n_refs: int = 0, model_id: int = 0, kernel_co
     return head + z + y
 
 
+def pack_exact(strings, shape, image_hw, spec_hash, model_id: int = 0) -> bytes:
+    """VERSION 4: the stream of compress(x, exact=True), whose entropy parameters come from an integer net (clc_amd/intnet.py) and are
+    the same bits under every kernel state and build.  The 28-byte version-2 header with tag byte 0 and, in the u32, the net's
+    spec_hash — the name of the entropy model, not of a kernel generation: unpack does not call check_kernel_config for it."""
+    if isinstance(spec_hash, bool) or not 0 <= int(spec_hash) < 1 << 32:
+        raise ValueError(f"pack_exact: spec_hash must be a u32 (got {spec_hash!r})")
+    y, z = strings[0][0], strings[1][0]
+    head = MAGIC + struct.pack("<BBBBHHHHII", 4, model_id, 0, 0, image_hw[0], image_hw[1], int(shape[0]), int(shape[1]), len(y), len(z))
+    return head + struct.pack("<I", int(spec_hash)) + z + y
+
+
 def pack_item(item: dict, image_hw=None, n_refs=None, model_id: int = 0) -> bytes:
     """pack() of one compress() result, under the kernel state that result was ENCODED with.  A result of the bank path (it carries
-    `ref_ids`, `bank_id`, `image_hw`) is written as version 3; image_hw then defaults to the item's and must equal it."""
+    `ref_ids`, `bank_id`, `image_hw`) is written as version 3; image_hw then defaults to the item's and must equal it.  A result
+    that carries "exact" (compress(x, exact=True)) is written as version 4 (pack_exact)."""
+    if item.get("exact") is not None:
+        if image_hw is None:
+            raise ValueError("pack_item: image_hw is required for an item without reference ids")
+        if item.get("ref_ids") is not None or n_refs:
+            raise ValueError("pack_item: an exact item has no references (version 4 carries none)")
+        return pack_exact(item["strings"], item["shape"], image_hw, item["exact"], model_id)
     ids = item.get("ref_ids")
     if ids is None:
         if image_hw is None:
@@ -138,18 +157,24 @@ def check_kernel_config(meta, what="container"):
 def unpack(blob: bytes, strict: bool = True):
     """-> (strings, shape, meta) as decompress() takes them.  strict (default): refuse a container whose kernel-config tag is not this
     build's (KernelConfigMismatch); strict=False returns it with meta["same_kernel_config"] = False for inspection.  Version 3 adds
-    meta["bank_id"] and meta["ref_ids"]."""
+    meta["bank_id"] and meta["ref_ids"].  Version 4 sets meta["exact_hash"] and meta["same_kernel_config"] = True and is never
+    refused for its kernel state, under strict too: pass meta["exact_hash"] as decompress(..., exact=)."""
     if len(blob) < 24 or blob[:4] != MAGIC:
         raise ValueError("not a CLC1 container (shorter than its 24-byte header, or wrong magic)")
     ver, model_id, n_refs, tag, H, W, zh, zw, ny, nz = struct.unpack("<BBBBHHHHII", blob[4:24])
-    if ver not in (1, 2, 3):
+    if ver not in (1, 2, 3, 4):
         raise ValueError(f"unsupported container version {ver}")
-    hl = {1: 24, 2: 28, 3: 32 + 4 * n_refs}[ver]
+    hl = {1: 24, 2: 28, 3: 32 + 4 * n_refs, 4: 28}[ver]
     if ver == 3 and n_refs == 0:
         raise ValueError("version-3 container without reference ids")
     if len(blob) != hl + ny + nz:
         raise ValueError("truncated / oversized container")
     z, y = blob[hl:hl + nz], blob[hl + nz:hl + nz + ny]
+    if ver == 4:
+        if tag != 0 or n_refs != 0:
+            raise ValueError(f"version-4 container with kernel-config tag {tag} / {n_refs} references (both must be 0)")
+        meta = {"image_hw": (H, W), "n_refs": 0, "model_id": model_id, "exact_hash": struct.unpack("<I", blob[24:28])[0], "same_kernel_config": True}
+        return [[y], [z]], torch.Size([zh, zw]), meta
     now, now_h = kernel_config()
     meta = {"image_hw": (H, W), "n_refs": n_refs, "model_id": model_id, "kernel_config_tag": tag, "same_kernel_config": tag == now}
     if ver >= 2:
@@ -166,6 +191,8 @@ def unpack(blob: bytes, strict: bool = True):
 def unpack_item(blob: bytes, strict: bool = True) -> dict:
     """unpack() as the dict CodecEngine.decompress takes; the header's meta rides along and is checked again where decoding starts."""
     strings, shape, meta = unpack(blob, strict)
+    if "exact_hash" in meta:   # version 4: what model.decompress(..., exact=) takes
+        return {"strings": strings, "shape": shape, "meta": meta, "exact": meta["exact_hash"]}
     return {"strings": strings, "shape": shape, "meta": meta}
 
 
@@ -332,6 +359,9 @@ def check_items(items, lanes):
     """What decompress refuses about its items before any device work: a "lanes" entry other than the call's, and another kernel state's
     container header (`meta`, from unpack_item) or `kernel_config` entry (from compress)."""
     for k, it in enumerate(items):
+        if it.get("exact") is not None or "exact_hash" in (it.get("meta") or {}):
+            raise ValueError(f"decompress: item {k} is an exact stream (integer hyper-synthesis, container version 4): the engines have no "
+                             "integer parameter net — decode it with ScaleHyperprior / MeanScaleHyperprior.decompress(..., exact=)")
         if it.get("lanes") is not None and it["lanes"] != lanes:
             raise ValueError(f"decompress: item {k} was coded with lanes = {it['lanes']}, the call says lanes = {lanes}")
     if lanes is None:

@@ -149,6 +149,14 @@ class LanesSegments(C.Structure):
     _fields_ = [("P", C.c_int), ("n", C.c_int * RANS_LANES_MAX_SEGMENTS)]
 
 
+class IntConvDesc(C.Structure):
+    _fields_ = [("x", fp), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int), ("ldx", C.c_int),
+                ("w_packed", fp), ("bias", fp), ("mult_pos", fp), ("mult_neg", fp), ("shift", fp),
+                ("y", fp), ("Cout", C.c_int), ("ldy", C.c_int), ("transposed", C.c_int), ("out_kind", C.c_int), ("f_out", C.c_int)]
+
+
+INT_OUT_I8, INT_OUT_F32 = 0, 1   # CLC_INT_OUT_*
+
 _i, _l, _f, _d, _sz = C.c_int, C.c_long, C.c_float, C.c_double, C.c_size_t
 _pp = C.POINTER(fp)
 
@@ -319,6 +327,8 @@ SIGNATURES = {
     "clc_rgb_to_yuv420": (_i, [fp, _l, _i, _i, _i, _i, _i, _i, fp, fp, fp, fp]),
     "clc_plane_sse_workspace_bytes": (_sz, [_i, _l]),
     "clc_plane_sse": (_i, [fp, fp, _i, _i, _l, fp, fp, _sz, fp]),
+    "clc_int_conv": (_i, [C.POINTER(IntConvDesc), fp]),
+    "clc_int_quantize": (_i, [fp, _l, _i, fp, fp]),
 }
 
 

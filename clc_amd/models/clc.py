@@ -29,6 +29,7 @@ from ..entropy_models import EntropyBottleneck, GaussianConditional
 from ..layers import (GELU, ConvTransBlock, Conv2d, ResidualBlockUpsample, ResidualBlockWithStride, SWAtten, conv1x1,
                       conv3x3, subpel_conv3x3)
 from ..ops import ACT_GELU, ACT_HALFTANH, ACT_NONE, CL
+from ..intnet import refuse_integer_hyper
 from ..vbr import refuse_rate_levels
 from . import coding
 
@@ -520,6 +521,7 @@ class CLC(_SliceCodec):
     def __init__(self, config=[2, 2, 2, 2, 2, 2], head_dim=[8, 16, 32, 32, 16, 8], drop_path_rate=0, N=128, M=320,
                  num_slices=5, max_support_slices=5, num_ref_frames=3, use_ref=True, **kwargs):
         refuse_rate_levels("CLC", kwargs)
+        refuse_integer_hyper("CLC", kwargs)
         super().__init__(entropy_bottleneck_channels=N)
         if list(config) != [2] * 6 or drop_path_rate != 0 or M != 320 or num_slices != 5:
             raise ValueError("clc_amd.CLC supports the reference configuration: config=[2]*6, drop_path_rate=0, M=320, num_slices=5")
@@ -607,6 +609,7 @@ class TCM(_SliceCodec):
     def __init__(self, config=[2, 2, 2, 2, 2, 2], head_dim=[8, 16, 32, 32, 16, 8], drop_path_rate=0, N=128, M=320,
                  num_slices=5, max_support_slices=5, **kwargs):
         refuse_rate_levels("TCM", kwargs)
+        refuse_integer_hyper("TCM", kwargs)
         super().__init__(entropy_bottleneck_channels=N)
         if list(config) != [2] * 6 or drop_path_rate != 0 or M != 320 or num_slices != 5:
             raise ValueError("clc_amd.TCM supports the reference configuration: config=[2]*6, drop_path_rate=0, M=320, num_slices=5")

@@ -87,9 +87,11 @@ class Elic2022(CodeInputs, CompressionModel):
     docstring for the kernels and the stream order."""
 
     def __init__(self, N=192, M=320, groups=(16, 16, 32, 64, 192), ch_widths=(224, 128), agg_widths=(640, 512), **kwargs):
+        from ..intnet import refuse_integer_hyper
         from ..vbr import refuse_rate_levels
 
         refuse_rate_levels("Elic2022", kwargs)
+        refuse_integer_hyper("Elic2022", kwargs)
         super().__init__(entropy_bottleneck_channels=N)
         groups, ch_widths, agg_widths = tuple(int(c) for c in groups), tuple(int(c) for c in ch_widths), tuple(int(c) for c in agg_widths)
         if len(groups) < 1 or sum(groups) != M:

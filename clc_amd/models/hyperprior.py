@@ -30,6 +30,7 @@ from .. import ans, ops
 from ..entropy_models import EntropyBottleneck, GaussianConditional
 from ..layers import GDN, CheckerboardMaskedConv2d, Conv2d, MaskedConv2d, conv, deconv
 from ..ops import ACT_LRELU, ACT_NONE, ACT_RELU, CL
+from ..intnet import IntegerHyperSynthesis, check_channels, choose_f0, convert, refuse_integer_hyper
 from ..vbr import StepTable, model_step, refuse_rate_levels
 from .clc import CompressionModel, _resize_registered_buffers, get_scale_table
 from .coding import (CodeInputs, HostSymbols, coded_item, decoder_start, lanes_check, lanes_count, lanes_parse, lanes_strings, linear_filters,
@@ -37,13 +38,23 @@ from .coding import (CodeInputs, HostSymbols, coded_item, decoder_start, lanes_c
 
 
 class ScaleHyperprior(CompressionModel):
-    """Balle et al. 2018, scale hyperprior: y ~ N(0, sigma(z)^2)."""
+    """Balle et al. 2018, scale hyperprior: y ~ N(0, sigma(z)^2).
+
+    BUILD-INDEPENDENT STREAMS (``integer_hyper=True``, ``exact=True``; DESIGN 32, clc_amd/intnet.py): the entropy parameters come from
+    ``h_s_int``, an int8 restatement of ``h_s`` on the i8 matrix cores whose outputs are the same bits under every kernel state, build
+    and machine, so a stream coded with ``exact=True`` decodes wherever the integers are — the quantiser, the scale index and the rANS
+    coder downstream were build-independent already.  ``g_a``, ``h_a`` and ``g_s`` stay float: the first two run only in the encoder,
+    and ``g_s``'s rounding moves the reconstruction by float noise across builds but cannot desynchronise the coder."""
 
     _h_act = ACT_RELU
+    _h_slopes = (0.0, 0.0, 0.0)   # the negative-side slopes of h_s's three activations, for the integer net's conversion
+    _h_split = False
 
-    def __init__(self, N=128, M=192, rate_levels=0, **kwargs):
+    def __init__(self, N=128, M=192, rate_levels=0, integer_hyper=False, **kwargs):
         super().__init__(entropy_bottleneck_channels=N)
         self._check_channels(N, M)
+        if integer_hyper:   # refused by name before anything is built
+            check_channels(self._hyper_channels(N, M), type(self).__name__)
         rate_levels = int(rate_levels)
         if rate_levels < 0:
             raise ValueError(f"{type(self).__name__}: rate_levels must not be negative (got {rate_levels})")
@@ -55,6 +66,13 @@ class ScaleHyperprior(CompressionModel):
         self._build_hyper(N, M)
         self.gaussian_conditional = GaussianConditional(None)
         self.N, self.M = int(N), int(M)
+        if integer_hyper:   # zero-filled buffers of the right shapes, so that a checkpoint that holds them loads; without the flag
+            self.h_s_int = IntegerHyperSynthesis(self._hyper_channels(N, M), split=self._h_split)   # no module and no state_dict key
+
+    @staticmethod
+    def _hyper_channels(N, M):
+        """(Cin of h_s, its three layers' Cout)"""
+        return (N, N, N, M)
 
     @staticmethod
     def _check_channels(N, M):
@@ -103,19 +121,69 @@ class ScaleHyperprior(CompressionModel):
         """(scales, means or None) of y from z_hat"""
         return self._hyper_synthesis(z_hat), None
 
+    # ---- the integer parameter net ----
+    def _exact_net(self, who):
+        """h_s_int, filled; refused by name otherwise"""
+        net = getattr(self, "h_s_int", None)
+        if net is None:
+            raise ValueError(f"{who}: exact needs the integer hyper-synthesis net — build the model with integer_hyper=True")
+        net.require_ready(who)
+        return net
+
+    def _check_exact(self, exact, who):
+        """exact of a decoder -> bool: None / False off; True on; an int is the spec_hash the stream was written under"""
+        if exact is None or exact is False:
+            return False
+        net = self._exact_net(who)
+        if exact is not True:
+            if isinstance(exact, bool) or not isinstance(exact, (int, np.integer)):
+                raise TypeError(f"{who}: exact must be True or the stream's spec_hash as an int (got {type(exact).__name__})")
+            if int(exact) != net.spec_hash():
+                raise ValueError(f"{who}: the stream was written under integer net 0x{int(exact):08x}, this model's is 0x{net.spec_hash():08x}")
+        return True
+
+    @torch.no_grad()
+    def integerize(self, x_calib, f_out=8):
+        """Post-training conversion of h_s into h_s_int (intnet.convert): runs the float model on the calibration images up to each h_s
+        layer, records the largest |activation| after layers 1 and 2 and max|z_hat|, and fills the integer buffers -> spec_hash."""
+        who = f"{type(self).__name__}.integerize"
+        net = getattr(self, "h_s_int", None)
+        if net is None:
+            raise ValueError(f"{who}: the model has no integer hyper-synthesis net — build it with integer_hyper=True")
+        x = self._prep(x_calib)
+        z = self._hyper_analysis(self._analysis(x))
+        z_hat = self.entropy_bottleneck(z, training=False)[0]
+        a = self._h_act
+        t1 = self.h_s[0](z_hat, act=a)
+        t2 = self.h_s[2](t1, act=a)
+        amax = [float(t1.abs().max()), float(t2.abs().max())]
+        f0 = choose_f0(float(z_hat.abs().max()))
+        layers = [self.h_s[0], self.h_s[2], self.h_s[4]]
+        net.fill(convert([m.weight.detach().double().cpu().numpy() for m in layers], [m.bias.detach().double().cpu().numpy() for m in layers],
+                         amax, self._h_slopes, f0, f_out), f0, f_out)
+        return net.spec_hash()
+
     def _step(self, q, who):
         """the step vector of quality q from the model's step table (vbr.model_step: None for q None, refusals by name)"""
         return model_step(self, q, f"{type(self).__name__}.{who}")
 
-    def forward(self, x, q=None):
+    def forward(self, x, q=None, exact=False):
         """q: the quality, a float in [0, rate_levels - 1] (higher: finer steps, more bits); None: the fixed-rate model.  With q the
-        eval x_hat is decoded from step * ste_round((y - mu) / step) + mu, so the distortion reaches the step table too."""
+        eval x_hat is decoded from step * ste_round((y - mu) / step) + mu, so the distortion reaches the step table too.
+        exact=True (eval / no_grad only: the integer net takes no gradient): the entropy parameters of h_s_int, what
+        compress(exact=True) codes under."""
         step = self._step(q, "forward")
+        net = None
+        if exact:
+            who = f"{type(self).__name__}.forward"
+            if self.training:
+                raise ValueError(f"{who}: exact=True is refused in training mode — the integer hyper-synthesis net takes no gradient (call model.eval())")
+            net = self._exact_net(who)
         x = self._prep(x)
         y = self._analysis(x)
         z = self._hyper_analysis(y)
         z_hat, z_likelihoods = self.entropy_bottleneck(z)
-        scales_hat, means_hat = self._params(z_hat)
+        scales_hat, means_hat = self._params(z_hat) if net is None else net(z_hat)
         if step is None:
             y_hat, y_likelihoods = self.gaussian_conditional(y, scales_hat, means=means_hat)
         else:
@@ -165,11 +233,13 @@ class ScaleHyperprior(CompressionModel):
             k -= 1
 
     @torch.no_grad()
-    def compress(self, x, q=None, target_bytes=None):
+    def compress(self, x, q=None, target_bytes=None, exact=False):
         """q: the quality (see forward); target_bytes=T: the finest quality at which y and z of EVERY image of the batch fit T bytes
         together (the chosen q is in the result; ValueError naming the sizes if the coarsest does not fit).  The result carries "q"
-        when a step was used; pass it to decompress."""
+        when a step was used; pass it to decompress.  exact=True: the entropy parameters of the integer net h_s_int — a stream that
+        is not tied to this build; the result carries "exact": spec_hash, pass it to decompress (codec.pack_item writes version 4)."""
         who = f"{type(self).__name__}.compress"
+        net = self._exact_net(who) if exact else None
         if q is not None and target_bytes is not None:
             raise ValueError(f"{who}: q and target_bytes exclude each other (got q={q!r}, target_bytes={target_bytes!r})")
         if target_bytes is not None:
@@ -183,20 +253,30 @@ class ScaleHyperprior(CompressionModel):
         z = self._hyper_analysis(y)
         z_strings = self.entropy_bottleneck.compress(z)
         z_hat = self.entropy_bottleneck.decompress(z_strings, z.size()[-2:])
-        scales_hat, means_hat = self._params(z_hat)
+        scales_hat, means_hat = self._params(z_hat) if net is None else net(z_hat)
         means = means_hat if means_hat is not None else self._zeros_like(y)
+        extra = {} if net is None else {"exact": net.spec_hash()}
         if target_bytes is not None:
             y_strings, q = self._compress_to_target(y, means, scales_hat, z_strings, target_bytes)
-            return coded_item(y_strings, z_strings, z.size()[-2:], q=q)
+            return coded_item(y_strings, z_strings, z.size()[-2:], q=q, **extra)
         y_strings = self._encode_y(y, means, scales_hat, step)
-        return coded_item(y_strings, z_strings, z.size()[-2:]) if step is None else coded_item(y_strings, z_strings, z.size()[-2:], q=q)
+        if step is not None:
+            extra["q"] = q
+        return coded_item(y_strings, z_strings, z.size()[-2:], **extra)
 
     @torch.no_grad()
-    def decompress(self, strings, shape, q=None):
+    def decompress(self, strings, shape, q=None, exact=None):
+        """exact: True, or the "exact" hash of the compress result (a hash that is not this model's raises ValueError naming both)"""
+        return {"x_hat": self._synthesis(self._decode_y_hat(strings, shape, q, exact)).clamp_(0, 1)}
+
+    @torch.no_grad()
+    def _decode_y_hat(self, strings, shape, q=None, exact=None):
+        """the part of decompress before g_s -> y_hat"""
         step = self._step(q, "decompress")
+        exact = self._check_exact(exact, f"{type(self).__name__}.decompress")
         assert isinstance(strings, (list, tuple)) and len(strings) == 2
         z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
-        scales_hat, means_hat = self._params(z_hat)
+        scales_hat, means_hat = self.h_s_int(z_hat) if exact else self._params(z_hat)
         gc = self.gaussian_conditional
         cdf, ln, off = gc.host_tables()
         idx = (gc.build_indexes(scales_hat) if step is None else gc.build_indexes(scales_hat, step=step)).contiguous().cpu().numpy()
@@ -208,7 +288,7 @@ class ScaleHyperprior(CompressionModel):
             y_hat = y_hat * step.reshape(1, -1, 1, 1)
         if means_hat is not None:
             y_hat = y_hat + means_hat
-        return {"x_hat": self._synthesis(y_hat).clamp_(0, 1)}
+        return y_hat
 
     def update(self, scale_table=None, force=False):
         if scale_table is None:
@@ -228,6 +308,12 @@ class MeanScaleHyperprior(ScaleHyperprior):
     """Minnen et al. 2018 without the context model: y ~ N(mu(z), sigma(z)^2)."""
 
     _h_act = ACT_LRELU
+    _h_slopes = (0.01, 0.01, 1.0)   # the last layer is linear
+    _h_split = True
+
+    @staticmethod
+    def _hyper_channels(N, M):
+        return (N, M, M * 3 // 2, M * 2)
 
     def _build_hyper(self, N, M):
         self.h_a = nn.Sequential(conv(M, N, stride=1, kernel_size=3), nn.LeakyReLU(inplace=True), conv(N, N), nn.LeakyReLU(inplace=True),
@@ -324,6 +410,7 @@ class JointAutoregressiveHierarchicalPriors(CodeInputs, MeanScaleHyperprior):
 
     def __init__(self, N=192, M=192, **kwargs):
         refuse_rate_levels(type(self).__name__, kwargs)   # the context models code y under the unit step only
+        refuse_integer_hyper(type(self).__name__, kwargs)   # their parameters depend on the coded y too: a follow-up
         if M % 12:
             raise ValueError(f"{type(self).__name__} needs M % 12 == 0 (then 10M/3, 8M/3 and 3M/2 are whole and multiples of 4, the "
                              f"kernels' aligned path); got M = {M}" + (": M = 320 (mbt2018 qualities 5-8) is not built" if M == 320 else ""))

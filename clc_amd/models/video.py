@@ -274,7 +274,12 @@ class ScaleSpaceFlow(CompressionModel):
     rate_levels > 0 (VARIABLE RATE): one StepTable inside each of the three hyperpriors, and ``q`` on forward / compress /
     decompress: a float for every frame or a list of one float per frame; one q serves both latents of a P-frame."""
 
-    def __init__(self, num_levels=5, sigma0=1.5, scale_field_shift=1.0, mid_planes=128, planes=192, rate_levels=0):
+    def __init__(self, num_levels=5, sigma0=1.5, scale_field_shift=1.0, mid_planes=128, planes=192, rate_levels=0, **kwargs):
+        from ..intnet import refuse_integer_hyper
+
+        refuse_integer_hyper("ScaleSpaceFlow", kwargs)   # its hyperpriors' integer nets are a follow-up
+        if set(kwargs) - {"integer_hyper", "exact"}:
+            raise TypeError(f"ScaleSpaceFlow.__init__() got an unexpected keyword argument {sorted(set(kwargs) - {'integer_hyper', 'exact'})[0]!r}")
         super().__init__()
         if int(rate_levels) < 0:
             raise ValueError(f"ScaleSpaceFlow: rate_levels must not be negative (got {rate_levels})")

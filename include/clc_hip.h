@@ -1105,6 +1105,40 @@ size_t clc_plane_sse_workspace_bytes(int N, long n);   /* 0 and clc_last_error o
 int clc_plane_sse(const void* a, const void* b, int bit_depth, int N, long n /* samples per image */, int64_t* out /* [N] */, void* ws, size_t ws_bytes,
                   clc_stream_t stream);
 
+/* ---- integer hyper-synthesis: int8 convolutions on the i8 matrix cores, requantising epilogue fused (csrc/int_conv.hip) ---- *
+ * The entropy parameters of a hyperprior model in integer arithmetic (Balle, Johnston, Minnen, ICLR 2019): integer sums are exact and
+ * order-free, so the parameters are the same bits under every kernel state, build and machine.  tests/intnet_ref.py is the reference.
+ * INPUT (clc_int_quantize): x0 = clamp(rintf(z * 2^f0), -128, 127) as int8, rintf half to even; z dense f32, n elements.
+ * LAYER (clc_int_conv): x int8 NHWC [B][H][W] with Cin channels at leading dimension ldx (bytes); two geometries:
+ *   transposed = 1: 5x5, stride 2, padding 2, output_padding 1 transposed convolution -> [B][2H][2W],
+ *                   out[oh][ow][co] = sum over kh, kw, ci with oh = 2 ih - 2 + kh, ow = 2 iw - 2 + kw of x[ih][iw][ci] * w[ci][co][kh][kw];
+ *   transposed = 0: 3x3, stride 1, padding 1 convolution -> [B][H][W], out[oh][ow][co] = sum of x[oh + kh - 1][ow + kw - 1][ci] * w[co][ci][kh][kw].
+ *   With acc the int32 sum (|acc| <= 25 * 480 * 128 * 127 < 2^28 for the largest shape served; |bias| <= 2^30, so |a| < 2^31):
+ *     a = acc + bias[co];  m = a >= 0 ? mult_pos[co] : mult_neg[co]  (int32, >= 0);
+ *     r = ((int64)a * m + (1 << (shift[co] - 1))) >> shift[co]       (arithmetic shift: round half up; 1 <= shift <= 62; |a * m| < 2^62)
+ *   CLC_INT_OUT_I8:  y int8 NHWC, clamp(r, -128, 127), written as dwords of four channels (y 4-byte aligned, ldy % 4 == 0, in bytes);
+ *   CLC_INT_OUT_F32: y f32 NHWC, (float)clamp(r, -32768, 32767) * 2^-f_out, exact in f32 (y 16-byte aligned, ldy % 4 == 0, in floats).
+ *   mult_neg = 0 is ReLU, mult_neg = round(slope * ...) LeakyReLU, mult_neg = mult_pos no activation.
+ * THE PACKED FILTER w_packed, int8 [Cout / 32][T][Cin / 32][2][32][16] with T = 25 (tap kh * 5 + kw) or 9 (kh * 3 + kw): entry
+ *   [ct][t][kc][h][r][j] is the weight of output channel 32 ct + r, tap t, input channel 32 kc + 16 h + j (built in Python:
+ *   clc_amd/intnet.py pack_filter).  Cin and Cout are multiples of 32; bias / mult_pos / mult_neg / shift are int32 [Cout], 16-byte aligned;
+ *   x and w_packed 16-byte aligned, ldx % 16 == 0.  shift is read on the device and is the caller's to keep in 1 .. 62.
+ * Pixel tiles of 32 may cross image boundaries in a batch; rows beyond B H W are neither read nor written; columns beyond Cout of a row
+ * (ldy > Cout) are not written.  One stream-ordered launch each; nothing is allocated; capturable; bad arguments are refused by name. */
+#define CLC_INT_OUT_I8 0
+#define CLC_INT_OUT_F32 1
+typedef struct {
+  const int8_t* x; int B, H, W, Cin, ldx;
+  const int8_t* w_packed;
+  const int32_t *bias, *mult_pos, *mult_neg, *shift;   /* [Cout] each */
+  void* y; int Cout, ldy;
+  int transposed;                                      /* 1: 5x5 stride-2 transposed; 0: 3x3 stride-1 */
+  int out_kind;                                        /* CLC_INT_OUT_I8 / CLC_INT_OUT_F32 */
+  int f_out;                                           /* CLC_INT_OUT_F32: fractional bits of the output, 0 .. 30 */
+} clc_int_conv_desc;
+int clc_int_conv(const clc_int_conv_desc* d, clc_stream_t stream);
+int clc_int_quantize(const float* z, long n, int f0 /* 0 .. 16 */, int8_t* x0, clc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
