@@ -803,7 +803,8 @@ extern "C" int clc_im2col_small(const float* x, int ldx, int N, int H, int W, in
                                 int OH, int OW, clc_stream_t stream) {
   CLC_CHECK(x && col && N > 0 && H > 0 && W > 0 && C > 0 && ks > 0 && stride > 0, "clc_im2col_small: bad args");
   CLC_CHECK(ldc % 4 == 0 && ldc >= ks * ks * C && aligned16(col), "clc_im2col_small: ldc must be a multiple of 4 and >= ks*ks*C");
-  CLC_CHECK(OH == (H + 2 * pad - ks) / stride + 1 && OW == (W + 2 * pad - ks) / stride + 1, "clc_im2col_small: output dims");
+  // (a window larger than the padded map has no output: C's division truncates (H + 2 pad - ks) / stride towards zero and would grant it one)
+  CLC_CHECK(pad >= 0 && H + 2 * pad >= ks && W + 2 * pad >= ks && OH == (H + 2 * pad - ks) / stride + 1 && OW == (W + 2 * pad - ks) / stride + 1, "clc_im2col_small: output dims");
   const long total = (long)N * OH * OW * (ldc / 4);
   hipLaunchKernelGGL(im2col_small_kernel, dim3(grid_for(total, 4096)), dim3(256), 0, ST, x, ldx, H, W, C, ks, stride, pad, col, ldc, OH, OW, total);
   CLC_LAUNCH_CHECK();
@@ -878,7 +879,9 @@ extern "C" int clc_sqdiff_partials(const float* a, const float* b, long n, float
 
 extern "C" int clc_maxpool2d(const float* x, int ldx, float* y, int ldy, int N, int H, int W, int C, int ks, int stride, int pad, int OH, int OW, clc_stream_t stream) {
   CLC_CHECK(x && y && N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && aligned16(x) && aligned16(y), "clc_maxpool2d: bad args (C, ld multiples of 4)");
-  CLC_CHECK(ks > 0 && stride > 0 && pad >= 0 && 2 * pad <= ks && OH == (H + 2 * pad - ks) / stride + 1 && OW == (W + 2 * pad - ks) / stride + 1, "clc_maxpool2d: output dims");
+  // (as F.max_pool2d: a window larger than the padded map is refused — C's truncating division would give it one output row)
+  CLC_CHECK(ks > 0 && stride > 0 && pad >= 0 && 2 * pad <= ks && H + 2 * pad >= ks && W + 2 * pad >= ks && OH == (H + 2 * pad - ks) / stride + 1 &&
+            OW == (W + 2 * pad - ks) / stride + 1, "clc_maxpool2d: output dims");
   const long total = (long)N * OH * OW * (C / 4);
   hipLaunchKernelGGL(maxpool2d_kernel, dim3(grid_for(total, 256)), dim3(256), 0, ST, x, ldx, y, ldy, H, W, C, ks, stride, pad, OH, OW, total);
   CLC_LAUNCH_CHECK();
