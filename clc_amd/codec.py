@@ -360,8 +360,9 @@ def check_items(items, lanes):
     container header (`meta`, from unpack_item) or `kernel_config` entry (from compress)."""
     for k, it in enumerate(items):
         if it.get("exact") is not None or "exact_hash" in (it.get("meta") or {}):
-            raise ValueError(f"decompress: item {k} is an exact stream (integer hyper-synthesis, container version 4): the engines have no "
-                             "integer parameter net — decode it with ScaleHyperprior / MeanScaleHyperprior.decompress(..., exact=)")
+            raise ValueError(f"decompress: item {k} is an exact stream (integer entropy model, container version 4): the engines have no "
+                             "integer parameter net — decode it with its model's own decompress(..., exact=) (ScaleHyperprior, "
+                             "MeanScaleHyperprior, JointCheckerboardHierarchicalPriors)")
         if it.get("lanes") is not None and it["lanes"] != lanes:
             raise ValueError(f"decompress: item {k} was coded with lanes = {it['lanes']}, the call says lanes = {lanes}")
     if lanes is None:

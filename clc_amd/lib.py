@@ -156,6 +156,21 @@ class IntConvDesc(C.Structure):
 
 
 INT_OUT_I8, INT_OUT_F32 = 0, 1   # CLC_INT_OUT_*
+INT_SRC_PIXEL, INT_SRC_DENSE, INT_SRC_TAPS = 0, 1, 2   # CLC_INT_SRC_*
+INT_ROWS_MAX_TAPS = 25           # CLC_INT_ROWS_MAX_TAPS
+
+
+class IntSrc(C.Structure):
+    _fields_ = [("p", fp), ("ld", C.c_int), ("C", C.c_int), ("kind", C.c_int)]
+
+
+class IntRowsDesc(C.Structure):
+    _fields_ = [("src", IntSrc * 2), ("nsrc", C.c_int),
+                ("pix", fp), ("P", C.c_int), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int),
+                ("taps", C.POINTER(C.c_int)), ("ntaps", C.c_int),
+                ("w_packed", fp), ("bias", fp), ("mult_pos", fp), ("mult_neg", fp), ("shift", fp),
+                ("y", fp), ("Cout", C.c_int), ("ldy", C.c_int), ("out_kind", C.c_int), ("f_out", C.c_int)]
+
 
 _i, _l, _f, _d, _sz = C.c_int, C.c_long, C.c_float, C.c_double, C.c_size_t
 _pp = C.POINTER(fp)
@@ -329,6 +344,7 @@ SIGNATURES = {
     "clc_plane_sse": (_i, [fp, fp, _i, _i, _l, fp, fp, _sz, fp]),
     "clc_int_conv": (_i, [C.POINTER(IntConvDesc), fp]),
     "clc_int_quantize": (_i, [fp, _l, _i, fp, fp]),
+    "clc_int_rows": (_i, [C.POINTER(IntRowsDesc), fp]),
 }
 
 

@@ -30,7 +30,8 @@ from .. import ans, ops
 from ..entropy_models import EntropyBottleneck, GaussianConditional
 from ..layers import GDN, CheckerboardMaskedConv2d, Conv2d, MaskedConv2d, conv, deconv
 from ..ops import ACT_LRELU, ACT_NONE, ACT_RELU, CL
-from ..intnet import IntegerHyperSynthesis, check_channels, choose_f0, convert, refuse_integer_hyper
+from ..intnet import (IntegerContextParameters, IntegerHyperSynthesis, check_channels, check_context_channels, choose_f0, context_spec_hash,
+                      convert, convert_context_model, int_quantize, refuse_integer_context, refuse_integer_hyper)
 from ..vbr import StepTable, model_step, refuse_rate_levels
 from .clc import CompressionModel, _resize_registered_buffers, get_scale_table
 from .coding import (CodeInputs, HostSymbols, coded_item, decoder_start, lanes_check, lanes_count, lanes_parse, lanes_strings, linear_filters,
@@ -134,13 +135,17 @@ class ScaleHyperprior(CompressionModel):
         """exact of a decoder -> bool: None / False off; True on; an int is the spec_hash the stream was written under"""
         if exact is None or exact is False:
             return False
-        net = self._exact_net(who)
+        mine = self._exact_hash(who)
         if exact is not True:
             if isinstance(exact, bool) or not isinstance(exact, (int, np.integer)):
                 raise TypeError(f"{who}: exact must be True or the stream's spec_hash as an int (got {type(exact).__name__})")
-            if int(exact) != net.spec_hash():
-                raise ValueError(f"{who}: the stream was written under integer net 0x{int(exact):08x}, this model's is 0x{net.spec_hash():08x}")
+            if int(exact) != mine:
+                raise ValueError(f"{who}: the stream was written under integer net 0x{int(exact):08x}, this model's is 0x{mine:08x}")
         return True
+
+    def _exact_hash(self, who):
+        """the hash that names the model's integer entropy model; refused by name where it has none or it is not filled"""
+        return self._exact_net(who).spec_hash()
 
     @torch.no_grad()
     def integerize(self, x_calib, f_out=8):
@@ -410,7 +415,8 @@ class JointAutoregressiveHierarchicalPriors(CodeInputs, MeanScaleHyperprior):
 
     def __init__(self, N=192, M=192, **kwargs):
         refuse_rate_levels(type(self).__name__, kwargs)   # the context models code y under the unit step only
-        refuse_integer_hyper(type(self).__name__, kwargs)   # their parameters depend on the coded y too: a follow-up
+        refuse_integer_hyper(type(self).__name__, kwargs)   # their parameters depend on the coded y too: the checkerboard model has
+        refuse_integer_context(type(self).__name__, kwargs)   # integer_context, a keyword of its own; mbt2018 is a follow-up
         if M % 12:
             raise ValueError(f"{type(self).__name__} needs M % 12 == 0 (then 10M/3, 8M/3 and 3M/2 are whole and multiples of 4, the "
                              f"kernels' aligned path); got M = {M}" + (": M = 320 (mbt2018 qualities 5-8) is not built" if M == 320 else ""))
@@ -634,12 +640,13 @@ class JointAutoregressiveHierarchicalPriors(CodeInputs, MeanScaleHyperprior):
         return y_hat
 
     @torch.no_grad()
-    def _decompress_lanes(self, strings, shape, Wn, device_coder, check):
+    def _decompress_lanes(self, strings, shape, Wn, device_coder, check, params_of=None):
+        """params_of: z_hat -> what the passes read as the hyper parameters (default: the float h_s)"""
         subs = lanes_parse(strings[0], Wn)   # the headers, before any device work
         if len(subs) != len(strings[1]):
             raise ValueError(f"decompress: {len(subs)} y streams for {len(strings[1])} z streams")
         z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
-        y_hat, state = self._decode_lanes(subs, self._hyper_synthesis(z_hat), device_coder)
+        y_hat, state = self._decode_lanes(subs, (params_of or self._hyper_synthesis)(z_hat), device_coder)
         x_hat = self._synthesis(y_hat).clamp_(0, 1)
         if check:
             lanes_check(state, subs)
@@ -696,14 +703,110 @@ class JointCheckerboardHierarchicalPriors(JointAutoregressiveHierarchicalPriors)
 
     STREAM ORDER: one rANS stream per image for y — all anchors in raster order, then all non-anchors in raster order, channels inner;
     z as in the other hyperprior models.  This is the project's own order: CompressAI is not a dependency and is not installed where
-    this is built, so nothing here is pinned against its checkerboard classes."""
+    this is built, so nothing here is pinned against its checkerboard classes.
 
-    def __init__(self, N=192, M=192, **kwargs):
+    BUILD-INDEPENDENT STREAMS (``integer_context=True``, ``exact=True``; DESIGN 33, clc_amd/intnet.py): ``h_s_int`` (int8 output) and
+    ``ctx_int`` restate the whole entropy model — h_s, the context layer over the int8-quantised y_hat, entropy_parameters — in int8 on
+    the i8 matrix cores (csrc/int_conv.hip, csrc/int_rows.hip).  The passes, the stream formats and the device decoder are the same
+    code; only the (scales | means) rows come from integer sums, the same bits under every kernel state, build and machine.  M must be
+    a multiple of 192 and N of 32.  Without the flag: no new module, state_dict key, launch or byte."""
+
+    def __init__(self, N=192, M=192, integer_context=False, **kwargs):
+        if integer_context:   # refused by name before anything is built
+            check_context_channels(N, M, type(self).__name__)
         super().__init__(N=N, M=M, **kwargs)
         self.context_prediction = CheckerboardMaskedConv2d(M, 2 * M, kernel_size=5, padding=2, stride=1)
+        if integer_context:   # zero-filled until integerize / load_state_dict; without the flag no module and no state_dict key
+            self.h_s_int = IntegerHyperSynthesis(self._hyper_channels(N, M), int8_out=True)
+            self.ctx_int = IntegerContextParameters(M)
 
     def _ar_encode(self, y, params, order="wavefront"):
         raise NotImplementedError("JointCheckerboardHierarchicalPriors has no autoregressive pass (mask A): the coder is _ckbd_encode / _ckbd_decode")
+
+    # ---- BUILD-INDEPENDENT STREAMS (integer_context=True, exact=True; DESIGN 33): h_s_int's int8 psi map and ctx_int's chain ----
+    def _exact_net(self, who):
+        """(h_s_int, ctx_int), both filled; refused by name otherwise"""
+        hs, cx = getattr(self, "h_s_int", None), getattr(self, "ctx_int", None)
+        if hs is None or cx is None:
+            raise ValueError(f"{who}: exact needs the integer context net — build the model with integer_context=True")
+        hs.require_ready(who)
+        cx.require_ready(who)
+        return hs, cx
+
+    def _exact_hash(self, who):
+        return context_spec_hash(*self._exact_net(who))
+
+    def spec_hash(self):
+        """the u32 that names the integer entropy model (intnet.context_spec_hash)"""
+        return self._exact_hash(f"{type(self).__name__}.spec_hash")
+
+    def _psi(self, z_hat):
+        """h_s_int's int8 psi as the passes take their hyper parameters: a channels-last [B, 2M, H, W] view of the NHWC map"""
+        return self.h_s_int(z_hat).permute(0, 3, 1, 2)
+
+    @torch.no_grad()
+    def integerize(self, x_calib, f_out=8):
+        """Post-training conversion of the whole entropy model (intnet.convert_context_model): runs the float coder's two passes on the
+        calibration images, records max|z_hat|, max|y_hat| and each layer's largest post-activation value — psi and the context
+        layer's output jointly — and fills h_s_int and ctx_int -> the hash."""
+        who = f"{type(self).__name__}.integerize"
+        if getattr(self, "ctx_int", None) is None:
+            raise ValueError(f"{who}: the model has no integer context net — build it with integer_context=True")
+        x = self._prep(x_calib)
+        y = self._analysis(x)
+        z_hat = self.entropy_bottleneck(self._hyper_analysis(y), training=False)[0]
+        a = self._h_act
+        t1 = self.h_s[0](z_hat, act=a)
+        t2 = self.h_s[2](t1, act=a)
+        params = self.h_s[4](t2)
+        amax = {"hs1": float(t1.abs().max()), "hs2": float(t2.abs().max()), "psi": float(params.abs().max()), "ep1": 0.0, "ep2": 0.0}
+        B, _, H, W = y.shape
+        sched = self._pass_schedule(B, H, W, y.device)
+
+        def passes(params, y_hat):
+            for cnt, px, gp in self._ckbd_passes(params, y_hat, sched):
+                for k, name in (("ep1", "h1"), ("ep2", "h2")):
+                    amax[k] = max(amax[k], float(sched.ws[name][:B * cnt].abs().max()))
+                yield cnt, px, gp
+
+        _, _, y_hat = self._encode_passes(who, y, params, passes)
+        amax["ctx"] = float(self.context_prediction(y_hat).abs().max())   # (the layer returns 0 at anchors)
+        np64 = lambda t: t.detach().double().cpu().numpy()
+        hs = [(np64(m.weight), np64(m.bias)) for m in (self.h_s[0], self.h_s[2], self.h_s[4])]
+        ep = [(np64(w), np64(b)) for w, b in linear_filters(self.entropy_parameters)]
+        cp = self.context_prediction
+        hs_layers, ctx_layers, f0, f_y, f_out = convert_context_model(hs, (np64(cp.weight), np64(cp.bias)), ep, amax, float(z_hat.abs().max()),
+                                                                      float(y_hat.abs().max()), self._h_slopes, f_out)
+        self.h_s_int.fill(hs_layers, f0, f_out)
+        self.ctx_int.fill(ctx_layers, f_y, f_out)
+        return self.spec_hash()
+
+    def forward(self, x, exact=False):
+        """exact=True (eval / no_grad only): the likelihoods under the coder's own two-pass integer parameters — the (scales | means)
+        rows of both passes scattered back to a map — and x_hat from the coder's y_hat: the rate of the stream compress(exact=True)
+        writes."""
+        if not exact:
+            return super().forward(x)
+        who = f"{type(self).__name__}.forward"
+        if self.training:
+            raise ValueError(f"{who}: exact=True is refused in training mode — the integer context net takes no gradient (call model.eval())")
+        self._exact_net(who)
+        with torch.no_grad():
+            x = self._prep(x)
+            y = self._analysis(x)
+            z_hat, z_likelihoods = self.entropy_bottleneck(self._hyper_analysis(y))
+            B, M, H, W = y.shape
+            gp_map = torch.empty((B, H, W, 2 * M), device=y.device, dtype=torch.float32)
+
+            def passes(params, y_hat):
+                for cnt, px, gp in self._ckbd_passes(params, y_hat):
+                    gp_map[:, px[:, 0].long(), px[:, 1].long()] = gp[:B * cnt].view(B, cnt, 2 * M)
+                    yield cnt, px, gp
+
+            _, _, y_hat = self._encode_passes(who, y, self._psi(z_hat), passes)
+            scales_hat, means_hat = gp_map.permute(0, 3, 1, 2).chunk(2, 1)
+            _, y_likelihoods = self.gaussian_conditional(y, scales_hat, means=means_hat)
+            return {"x_hat": self._synthesis(y_hat), "likelihoods": {"y": y_likelihoods, "z": z_likelihoods}}
 
     # ---- the two-pass coder ----
     _ckbd_lists = staticmethod(ckbd_lists)
@@ -722,28 +825,45 @@ class JointCheckerboardHierarchicalPriors(JointAutoregressiveHierarchicalPriors)
     def _ckbd_filters(self):
         return linear_filters(self.entropy_parameters)
 
-    def _pass_schedule(self, B, H, W, dev):
-        """the PassSchedule of the two passes: the pixel list's upload, the workspace and the zero context map, in one place"""
+    def _pass_schedule(self, B, H, W, dev, exact=False):
+        """the PassSchedule of the two passes: the pixel list's upload, the workspace and the zero context map, in one place.
+        exact: the integer chain's int8 workspace instead, and no zero map — an anchor pass has no context range"""
         anchors, others = ckbd_pixels(H, W)
         na, nn_, pix = self._ckbd_lists(H, W, dev)
-        sched = PassSchedule((B, H, W, dev), [s for s in (anchors, others) if s], pix, self._ckbd_workspace(B * max(na, nn_), dev))
-        sched.ctx0 = torch.zeros((B, 2 * self.M, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
+        rows = B * max(na, nn_)
+        sched = PassSchedule((B, H, W, dev), [s for s in (anchors, others) if s], pix,
+                             self.ctx_int.workspace(rows, dev) if exact else self._ckbd_workspace(rows, dev))
+        if not exact:
+            sched.ctx0 = torch.zeros((B, 2 * self.M, H, W), device=dev, dtype=torch.float32).contiguous(memory_format=CL)
         return sched
 
     def _ckbd_passes(self, params, y_hat, sched=None):
         """THE SCHEDULE of the checkerboard model, for encoder and decoder alike: the anchors, then the non-anchors; an empty pass is
         skipped.  Pass 1 reads a zero context map, pass 2 the context layer over the anchors that pass 1 committed.  Per pass the
         chain, then (pixels of the pass, its pixel list, its (scales | means) rows) to the caller's body.  sched: the caller's
-        PassSchedule (default: made here, for this call); with one, the passes upload and allocate nothing but the context map."""
+        PassSchedule (default: made here, for this call); with one, the passes upload and allocate nothing but the context map.
+        THE EXACT PATH (params is _psi's int8 map): ctx_int's integer chain writes the same f32 rows in place of _ckbd_chain, and the
+        int8 quantised y_hat stands in place of context_prediction; a pass is an anchor pass or a non-anchor pass by its pixels'
+        parity, so the single pass of a 1x1 latent evaluates the context layer (every tap off the map: its requantised bias)."""
         B, M, H, W = y_hat.shape
-        sched = self._pass_schedule(B, H, W, y_hat.device) if sched is None else sched.check(y_hat)
-        pix, ws, filt = sched.pix, sched.ws, self._ckbd_filters()
+        exact = params.dtype == torch.int8
+        sched = self._pass_schedule(B, H, W, y_hat.device, exact) if sched is None else sched.check(y_hat)
+        pix, ws = sched.pix, sched.ws
+        if exact:
+            net, psi = self.ctx_int, params.permute(0, 2, 3, 1)
+        else:
+            filt = self._ckbd_filters()
         lo = 0
-        for cnt in (len(s) for s in sched.steps):
-            ctx_map = self.context_prediction(y_hat) if lo else sched.ctx0   # (ctx0 is never written)
+        for s in sched.steps:
+            cnt = len(s)
             px = pix[lo:lo + cnt]
+            if exact:
+                anchor = (s[0][0] + s[0][1]) & 1
+                net.chain(px, B, H, W, psi, None if anchor else int_quantize(y_hat, net.f_y), ws)
+            else:
+                ctx_map = self.context_prediction(y_hat) if lo else sched.ctx0   # (ctx0 is never written)
+                self._ckbd_chain(px, B, H, W, params, ctx_map, ws, filt)
             lo += cnt
-            self._ckbd_chain(px, B, H, W, params, ctx_map, ws, filt)
             yield cnt, px, ws["gp"]
 
     def _ckbd_encode(self, y, params):
@@ -779,34 +899,69 @@ class JointCheckerboardHierarchicalPriors(JointAutoregressiveHierarchicalPriors)
         return (H * W + 1) // 2
 
     @torch.no_grad()
-    def compress(self, x, lanes=None):
+    def _exact_inputs(self, x):
+        """_code_inputs with h_s_int's psi map in place of the float hyper parameters"""
+        x = self._prep(x)
+        y = self._analysis(x)
+        z = self._hyper_analysis(y)
+        z_strings = self.entropy_bottleneck.compress(z)
+        z_hat = self.entropy_bottleneck.decompress(z_strings, z.size()[-2:])
+        return y, self._psi(z_hat), z_strings, z.size()[-2:]
+
+    @torch.no_grad()
+    def compress(self, x, lanes=None, exact=False):
         """lanes=None: the one-stream format.  lanes=W: the lanes stream, the same symbols cut into the two passes as segments and encoded
-        on the device; "lanes": W in the result; pass the same W to decompress."""
-        Wn = lanes_count(lanes, f"{type(self).__name__}.compress")
-        y, params, z_strings, z_size = self._code_inputs(x)
+        on the device; "lanes": W in the result; pass the same W to decompress.  exact=True: the entropy parameters of the integer
+        nets — a stream that is not tied to this build, in either format; the result carries "exact": the hash, pass it to
+        decompress (codec.pack_item writes version 4)."""
+        who = f"{type(self).__name__}.compress"
+        Wn = lanes_count(lanes, who)
+        extra = {"exact": self._exact_hash(who)} if exact else {}
+        y, params, z_strings, z_size = self._exact_inputs(x) if exact else self._code_inputs(x)
         sym, idx, _ = self._ckbd_encode(y, params)
         if Wn is not None:   # the buffers stay on the device
-            return coded_item(self._lanes_y_strings(sym, idx, y.shape[2], y.shape[3], Wn), z_strings, z_size, lanes=Wn)
+            return coded_item(self._lanes_y_strings(sym, idx, y.shape[2], y.shape[3], Wn), z_strings, z_size, lanes=Wn, **extra)
         cdf, ln, off = self.gaussian_conditional.host_tables()
         both = torch.stack((sym, idx)).cpu().numpy()   # the one device -> host copy: [2, B, H*W, M], raster pixels, channels inner
         order = self._ckbd_order(y.shape[2], y.shape[3])
         y_strings = [ans.encode(np.ascontiguousarray(both[0, i][order]).reshape(-1), np.ascontiguousarray(both[1, i][order]).reshape(-1), cdf, ln, off)
                      for i in range(both.shape[1])]
-        return coded_item(y_strings, z_strings, z_size)
+        return coded_item(y_strings, z_strings, z_size, **extra)
 
     def _ckbd_decode(self, y_strings, params):
         """The two passes of decompress -> y_hat: _decode_passes over _ckbd_passes, whose larger pass is the non-anchors ((0, 0) is one)"""
         return self._decode_passes(y_strings, params, (params.shape[2] * params.shape[3] + 1) // 2, self._ckbd_passes)
 
     @torch.no_grad()
-    def decompress(self, strings, shape, lanes=None, device_coder=True, check=True):
+    def decompress(self, strings, shape, lanes=None, device_coder=True, check=True, exact=None):
         """lanes, device_coder, check: as for mbt2018 (JointAutoregressiveHierarchicalPriors.decompress); the device decoder takes the
-        two passes with one clc_ar_lanes_decode each."""
-        Wn = lanes_count(lanes, f"{type(self).__name__}.decompress")
+        two passes with one clc_ar_lanes_decode each.  exact: True, or the "exact" hash of the compress result (a hash that is not
+        this model's raises ValueError naming both), on either stream format."""
+        who = f"{type(self).__name__}.decompress"
+        Wn = lanes_count(lanes, who)
+        exact = self._check_exact(exact, who)
         assert isinstance(strings, (list, tuple)) and len(strings) == 2
         if Wn is not None:
-            return self._decompress_lanes(strings, shape, Wn, device_coder, check)
+            return self._decompress_lanes(strings, shape, Wn, device_coder, check, self._psi if exact else None)
         refuse_lanes_strings(strings[0])
         z_hat = self.entropy_bottleneck.decompress(strings[1], shape)
-        y_hat = self._ckbd_decode(strings[0], self._hyper_synthesis(z_hat))
+        y_hat = self._ckbd_decode(strings[0], self._psi(z_hat) if exact else self._hyper_synthesis(z_hat))
         return {"x_hat": self._synthesis(y_hat).clamp_(0, 1)}
+
+    @torch.no_grad()
+    def _decode_y_hat(self, strings, shape, lanes=None, exact=None, device_coder=True, check=True):
+        """the part of decompress before g_s -> y_hat"""
+        who = f"{type(self).__name__}.decompress"
+        Wn = lanes_count(lanes, who)
+        params_of = self._psi if self._check_exact(exact, who) else self._hyper_synthesis
+        assert isinstance(strings, (list, tuple)) and len(strings) == 2
+        if Wn is None:
+            refuse_lanes_strings(strings[0])
+            return self._ckbd_decode(strings[0], params_of(self.entropy_bottleneck.decompress(strings[1], shape)))
+        subs = lanes_parse(strings[0], Wn)
+        if len(subs) != len(strings[1]):
+            raise ValueError(f"decompress: {len(subs)} y streams for {len(strings[1])} z streams")
+        y_hat, state = self._decode_lanes(subs, params_of(self.entropy_bottleneck.decompress(strings[1], shape)), device_coder)
+        if check:
+            lanes_check(state, subs)
+        return y_hat

@@ -1139,6 +1139,44 @@ typedef struct {
 int clc_int_conv(const clc_int_conv_desc* d, clc_stream_t stream);
 int clc_int_quantize(const float* z, long n, int f0 /* 0 .. 16 */, int8_t* x0, clc_stream_t stream);
 
+/* ---- integer context model: the pixel-list int8 GEMM with a tap gather (csrc/int_rows.hip) ---- *
+ * The entropy parameters of mbt2018-checkerboard in the integer arithmetic above, so that its streams are build-independent too;
+ * tests/intctx_ref.py is the reference.  THE ENTROPY MODEL: psi = h_s_int8(z_hat), the three clc_int_conv layers with the LAST one
+ * CLC_INT_OUT_I8 too (a 2M-channel NHWC int8 map at a calibrated scale); then per pass over a pixel list, every layer the requantising
+ * expression of clc_int_conv (a = acc + bias; m by the sign of a; r = (a m + 2^(shift - 1)) >> shift; a clamp):
+ *   yq  = clamp(rintf(y_hat * 2^f_y), -128, 127): clc_int_quantize over the NHWC map of y_hat = symbol + mean after pass 1;
+ *   ctx = int8(requant(sum over the 12 taps (kh + kw odd, (kh, kw) ascending) and M channels of w[co][t][ci] * yq(h + kh - 2, w + kw - 2))),
+ *         a tap off the map contributing 0 — non-anchor passes only ((h + w) even); on a 1x1 latent ctx is the requantised bias;
+ *   h1  = int8(requant(sum over psi at the pixel (K = 2M) [+ ctx (K = 2M), non-anchor passes only])), LeakyReLU through mult_neg;
+ *   h2  = int8(requant(h1: 10M/3 -> 8M/3)), LeakyReLU;   gp = CLC_INT_OUT_F32(requant(h2: 8M/3 -> 2M)), the (scales | means) row.
+ * ROWS (clc_int_rows): r = b * P + p over pix, int32 [P][2] of (h, w) on the device; a listed pixel off the map reads zeros.  The K
+ * axis is nsrc = 1 or 2 ranges in order, each with C channels (a multiple of 32) at leading dimension ld (bytes, >= C, % 16 == 0):
+ *   CLC_INT_SRC_PIXEL: an NHWC int8 map [B][H][W] read at the row's pixel;   CLC_INT_SRC_DENSE: int8 [rows][C], row r;
+ *   CLC_INT_SRC_TAPS:  an NHWC int8 map gathered at the ntaps (1 .. 25) offsets taps[t] = (dh, dw) (HOST memory, int [ntaps][2], each
+ *                      within +-127; copied into the launch), zero off the map: K = ntaps * C, tap-major.
+ * THE PACKED FILTER w_packed, int8 [Cout / 32][K / 32][2][32][16]: entry [ct][kc][h][r][j] is the weight of output channel 32 ct + r and
+ * k = 32 kc + 16 h + j of the concatenated K axis (clc_amd/intnet.py pack_rows).  The total K is at most 65536, so that
+ * |acc| <= K * 128 * 127 <= 2^30 and, with |bias| <= 2^30, |a| < 2^31.  Output as for clc_int_conv: CLC_INT_OUT_I8 int8 [rows][ldy]
+ * (dword stores) or CLC_INT_OUT_F32 f32 [rows][ldy] = clamp(r, +-2^15) * 2^-f_out (16-byte stores); columns beyond Cout and rows beyond
+ * B P are never written.  Vector stores only; one stream-ordered launch; nothing is allocated; capturable; bad arguments are refused
+ * by name before any launch. */
+#define CLC_INT_SRC_PIXEL 0
+#define CLC_INT_SRC_DENSE 1
+#define CLC_INT_SRC_TAPS 2
+#define CLC_INT_ROWS_MAX_TAPS 25
+typedef struct { const int8_t* p; int ld, C, kind; } clc_int_src;
+typedef struct {
+  clc_int_src src[2]; int nsrc;
+  const int32_t* pix; int P, B, H, W;
+  const int* taps; int ntaps;                          /* host memory; read only when a range is CLC_INT_SRC_TAPS */
+  const int8_t* w_packed;
+  const int32_t *bias, *mult_pos, *mult_neg, *shift;   /* [Cout] each */
+  void* y; int Cout, ldy;
+  int out_kind;                                        /* CLC_INT_OUT_I8 / CLC_INT_OUT_F32 */
+  int f_out;                                           /* CLC_INT_OUT_F32: fractional bits of the output, 0 .. 30 */
+} clc_int_rows_desc;
+int clc_int_rows(const clc_int_rows_desc* d, clc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
