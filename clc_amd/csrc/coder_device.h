@@ -12,6 +12,10 @@ constexpr float kScaleBound = 0.11f;   // LowerBound(scale, 0.11) of the Gaussia
 constexpr float kInvSqrt2 = 0.70710678118654752440f;
 constexpr float kInvSqrt2Pi = 0.39894228040143267794f;
 
+// LowerBound's forward, torch.max(x, bound): a NaN x stays NaN (fmaxf would return the bound); every other x gives fmaxf's bits.
+// The coder's index path keeps fmaxf on purpose: encoder and decoder code a NaN scale as the bound.
+__device__ __forceinline__ float bound_below(float x, float bound) { return x < bound ? bound : x; }
+
 __device__ __forceinline__ float std_cum(float x) { return 0.5f * erfcf(-kInvSqrt2 * x); }
 
 // The row of the coder's table for a scale sg that is already bounded below (fmaxf(scale, kScaleBound)):

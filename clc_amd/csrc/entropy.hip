@@ -29,10 +29,10 @@ __global__ __launch_bounds__(256) void gauss_lik_fwd_kernel(const float* __restr
     const float yv = y[r * ldy + c], m = mu[r * ldmu + c];
     const float rq = rintf(yv - m);  // torch.round = round-half-to-even
     const float yin = (mode == 0) ? yv + noise[r * ldn + c] : rq + m;
-    const float sg = fmaxf(scale[r * ldsc + c], kScaleBound);
+    const float sg = bound_below(scale[r * ldsc + c], kScaleBound);
     const float v = fabsf(yin - m);
     const float l = std_cum((0.5f - v) / sg) - std_cum((-0.5f - v) / sg);
-    const float lb = fmaxf(l, kLikBound);
+    const float lb = bound_below(l, kLikBound);
     lik[r * ldl + c] = lb;
     if (y_hat) y_hat[r * ldh + c] = rq + m;
     bits += log2f(lb);
@@ -56,27 +56,29 @@ __global__ __launch_bounds__(256) void gauss_lik_bwd_kernel(const float* __restr
     const int c = (int)(i - r * C);
     const float yv = y[r * ldy + c], m = mu[r * ldmu + c], sc = scale[r * ldsc + c];
     const float yin = (mode == 0) ? yv + noise[r * ldn + c] : rintf(yv - m) + m;
-    const float sg = fmaxf(sc, kScaleBound);
+    const float sg = bound_below(sc, kScaleBound);
     const float d = yin - m, v = fabsf(d);
     const float a = (0.5f - v) / sg, b = (-0.5f - v) / sg;
     const float l = std_cum(a) - std_cum(b);
     float g = dlik[r * lddl + c];
-    // LowerBound(lik, 1e-9): pass if lik >= bound or grad < 0
-    if (!(l >= kLikBound || g < 0.f)) g = 0.f;
+    // an upstream gradient that is not finite makes every gradient of the element NaN (autograd's g * phi(a) - g * phi(b) is NaN or an
+    // infinity by the signs of its two halves; an infinity must not reach an optimizer that zeroes only NaN)
+    if (!(g - g == 0.f)) g = g - g;
+    // LowerBound(lik, 1e-9): pass if lik >= bound or grad < 0, else 0 * g: +0, or NaN if g is
+    if (!(l >= kLikBound || g < 0.f)) g = g - g;
     const float pa = kInvSqrt2Pi * expf(-0.5f * a * a), pb = kInvSqrt2Pi * expf(-0.5f * b * b);
     const float dl_dv = (pb - pa) / sg;
     float dl_dsg = (pb * b - pa * a) / sg;   // d/dsg [Phi(a) - Phi(b)], da/dsg = -a/sg
     float gs = g * dl_dsg;
     // LowerBound(scale, 0.11): pass if scale >= bound or grad < 0
-    if (!(sc >= kScaleBound || gs < 0.f)) gs = 0.f;
+    if (!(sc >= kScaleBound || gs < 0.f)) gs = gs - gs;
     dscale[r * lddsc + c] = gs;
-    float gy = 0.f;
-    if (mode == 0) {
-      const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-      gy = g * dl_dv * sgn;
-    }
+    const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+    const float gv = g * dl_dv * sgn;   // d/d(y_in - mu)
+    const float gy = (mode == 0) ? gv : 0.f;
     if (dy) dy[r * lddy + c] = dy_add ? gy + dy_add[r * ldadd + c] : gy;   // (+ the straight-through gradient of y_hat = round(y - mu) + mu)
-    if (dmu) dmu[r * lddmu + c] = -gy;
+    // eval: mu reaches y_in - mu twice with opposite signs, gv - gv: zero, or NaN where gv is not finite (as autograd's sum)
+    if (dmu) dmu[r * lddmu + c] = (mode == 0) ? -gv : -(gv - gv);
   }
 }
 
@@ -203,7 +205,7 @@ __global__ __launch_bounds__(256) void eb_lik_fwd_kernel(const float* __restrict
     const float sm = tl.out + tu.out;
     const float s = sm > 0.f ? -1.f : (sm < 0.f ? 1.f : 0.f);
     const float l = fabsf(sigmoid_(s * tu.out) - sigmoid_(s * tl.out));
-    lik[r * ldl + ch] = fmaxf(l, kLikBound);
+    lik[r * ldl + ch] = bound_below(l, kLikBound);
     if (z_hat) z_hat[r * ldh + ch] = rq;
   }
 }
@@ -321,7 +323,10 @@ extern "C" int clc_gauss_lik_fwd(const float* y, int ldy, const float* mu, int l
                                  int ldn, float* lik, int ldl, float* y_hat, int ldh, long rows, int C, int mode, float* bits_partial,
                                  int n_partials, clc_stream_t stream) {
   CLC_CHECK(y && mu && scale && lik && rows > 0 && C > 0, "clc_gauss_lik_fwd: bad args");
+  CLC_CHECK(mode == 0 || mode == 1, "clc_gauss_lik_fwd: mode must be 0 (training) or 1 (eval) (got %d)", mode);
   CLC_CHECK(mode == 1 || noise, "clc_gauss_lik_fwd: training mode needs noise");
+  CLC_CHECK(ldy >= C && ldmu >= C && ldsc >= C && ldl >= C && (mode == 1 || ldn >= C) && (!y_hat || ldh >= C),
+            "clc_gauss_lik_fwd: a leading dimension is below C = %d", C);
   const int nb = grid_for(rows * C);
   CLC_CHECK(!bits_partial || n_partials == nb, "clc_gauss_lik_fwd: n_partials must be clc_gauss_lik_partials() = %d", nb);
   hipLaunchKernelGGL(gauss_lik_fwd_kernel, dim3(nb), dim3(256), 0, ST, y, ldy, mu, ldmu, scale, ldsc, noise, ldn, lik, ldl, y_hat, ldh, rows, C,
@@ -334,7 +339,11 @@ extern "C" int clc_gauss_lik_bwd(const float* dlik, int lddl, const float* y, in
                                  int ldsc, const float* noise, int ldn, float* dy, int lddy, float* dmu, int lddmu, float* dscale,
                                  int lddsc, long rows, int C, int mode, const float* dy_add, int ldadd, clc_stream_t stream) {
   CLC_CHECK(dlik && y && mu && scale && dscale && rows > 0 && C > 0, "clc_gauss_lik_bwd: bad args");
+  CLC_CHECK(mode == 0 || mode == 1, "clc_gauss_lik_bwd: mode must be 0 (training) or 1 (eval) (got %d)", mode);
   CLC_CHECK(mode == 1 || noise, "clc_gauss_lik_bwd: training mode needs noise");
+  CLC_CHECK(lddl >= C && ldy >= C && ldmu >= C && ldsc >= C && lddsc >= C && (mode == 1 || ldn >= C) && (!dy || lddy >= C) &&
+                (!dmu || lddmu >= C) && (!dy_add || ldadd >= C),
+            "clc_gauss_lik_bwd: a leading dimension is below C = %d", C);
   hipLaunchKernelGGL(gauss_lik_bwd_kernel, dim3(grid_for(rows * C)), dim3(256), 0, ST, dlik, lddl, y, ldy, mu, ldmu, scale, ldsc, noise, ldn, dy,
                      lddy, dmu, lddmu, dscale, lddsc, rows, C, mode, dy_add, ldadd);
   CLC_LAUNCH_CHECK();
@@ -346,6 +355,7 @@ extern "C" int clc_quantize_build_indexes(const float* y, int ldy, const float* 
                                           int ldh, long rows, int C, clc_stream_t stream) {
   CLC_CHECK(y && mu && scale && scale_table && symbols && indexes && rows > 0 && C > 0, "clc_quantize_build_indexes: bad args");
   CLC_CHECK(n_scales > 1 && n_scales <= 256, "clc_quantize_build_indexes: n_scales out of range");
+  CLC_CHECK(ldy >= C && ldmu >= C && ldsc >= C && (!y_hat || ldh >= C), "clc_quantize_build_indexes: a leading dimension is below C = %d", C);
   hipLaunchKernelGGL(quantize_build_indexes_kernel, dim3(grid_for(rows * C)), dim3(256), 0, ST, y, ldy, mu, ldmu, scale, ldsc, scale_table,
                      n_scales, symbols, indexes, y_hat, ldh, rows, C);
   CLC_LAUNCH_CHECK();

@@ -40,8 +40,8 @@ __global__ __launch_bounds__(256) void gauss_lik_step_fwd_kernel(const float* __
     const float rq = rintf((yv - m) / s);
     const float deq = rq * s + m;
     const float yin = (mode == 0) ? yv + s * noise[r * ldn + c] : deq;
-    const float sg = fmaxf(scale[r * ldsc + c], kScaleBound);
-    const float lb = fmaxf(lik_of(fabsf(yin - m), sg, 0.5f * s), kLikBound);
+    const float sg = bound_below(scale[r * ldsc + c], kScaleBound);
+    const float lb = bound_below(lik_of(fabsf(yin - m), sg, 0.5f * s), kLikBound);
     lik[r * ldl + c] = lb;
     if (y_hat) y_hat[r * ldh + c] = deq;
     bits += log2f(lb);
@@ -94,24 +94,25 @@ __global__ __launch_bounds__(256) void gauss_lik_step_bwd_kernel(const float* __
       const float t = (yv - m) / s, rq = rintf(t);
       const float w = (mode == 0) ? noise[r * ldn + c] : rq;   // d(y_in - mu) / dstep
       const float yin = (mode == 0) ? yv + s * w : rq * s + m;
-      const float sg = fmaxf(sc, kScaleBound);
+      const float sg = bound_below(sc, kScaleBound);
       const float d = yin - m, v = fabsf(d);
       const float a = (h - v) / sg, b = (-h - v) / sg;
       const float l = std_cum(a) - std_cum(b);
       float g = dlik[r * lddl + c];
-      if (!(l >= kLikBound || g < 0.f)) g = 0.f;   // LowerBound(lik, 1e-9): pass if lik >= bound or grad < 0
+      if (!(g - g == 0.f)) g = g - g;   // an upstream gradient that is not finite: NaN in every gradient of the element, as under autograd
+      if (!(l >= kLikBound || g < 0.f)) g = g - g;   // LowerBound(lik, 1e-9): pass if lik >= bound or grad < 0, else 0 * g (+0, or NaN if g is)
       const float pa = kInvSqrt2Pi * expf(-0.5f * a * a), pb = kInvSqrt2Pi * expf(-0.5f * b * b);
       const float dl_dv = (pb - pa) / sg;
       const float dl_dsg = (pb * b - pa * a) / sg;
       float gs = g * dl_dsg;
-      if (!(sc >= kScaleBound || gs < 0.f)) gs = 0.f;   // LowerBound(scale, 0.11)
+      if (!(sc >= kScaleBound || gs < 0.f)) gs = gs - gs;   // LowerBound(scale, 0.11)
       dscale[r * lddsc + c] = gs;
       const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
       const float gv = g * dl_dv * sgn;   // d/d(y_in - mu)
       const float gy = (mode == 0) ? gv : 0.f;
       const float gh = g_hat ? g_hat[r * ldg + c] : 0.f;
       if (dy) dy[r * lddy + c] = g_hat ? gy + gh : gy;
-      if (dmu) dmu[r * lddmu + c] = -gy;
+      if (dmu) dmu[r * lddmu + c] = (mode == 0) ? -gv : -(gv - gv);   // eval: gv - gv, zero or NaN (mu enters y_in - mu twice)
       // the three ways the step reaches the loss: the half width, y_in, y_hat
       acc += (g * (0.5f * (pa + pb) / sg) + gv * w) + gh * (rq - t);
     }
@@ -183,13 +184,13 @@ __global__ __launch_bounds__(256) void gauss_rate_sweep_kernel(const float* __re
     for (long r = (long)blockIdx.y * rl + lr; r < rows_per_image; r += (long)gridDim.y * rl) {
       const long at = row0 + r;
       const float yv = y[at * ldy + c], m = mu[at * ldmu + c];
-      const float sg = fmaxf(scale[at * ldsc + c], kScaleBound);
+      const float sg = bound_below(scale[at * ldsc + c], kScaleBound);
       const float d = yv - m;
 #pragma unroll
       for (int k = 0; k < kMaxCandidates; ++k) {
         if (k < K) {   // (uniform)
           const float deq = rintf(d / s[k]) * s[k] + m;
-          acc[k] -= log2f(fmaxf(lik_of(fabsf(deq - m), sg, 0.5f * s[k]), kLikBound));
+          acc[k] -= log2f(bound_below(lik_of(fabsf(deq - m), sg, 0.5f * s[k]), kLikBound));
         }
       }
     }

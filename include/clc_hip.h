@@ -323,7 +323,14 @@ int clc_winattn_bwd_pair(const float* dout, int lddo, const float* qkv, int ldq,
  *   mode 0 (train): y_in = y + noise ; mode 1 (eval): y_in = round(y-mu)+mu
  *   sigma = max(scale, 0.11); lik = max(Phi((.5-|y_in-mu|)/sigma) - Phi((-.5-|..|)/sigma), 1e-9)
  * Writes lik, y_hat = round(y-mu)+mu (STE value) and adds sum(log2 lik) of this call into
- * bits_partial[blockIdx] (two-stage deterministic reduction; finish with clc_sum_partials). */
+ * bits_partial[blockIdx] (two-stage deterministic reduction; finish with clc_sum_partials).
+ * Both bounds are torch.max's: a NaN scale or a NaN likelihood stays NaN (in lik, in its block's partial and in every gradient of
+ * that element).  An upstream gradient dlik that is NaN or infinite makes dy, dmu, dscale (and dstep's term) of that element NaN,
+ * blocked by the LowerBound rule or not: autograd's g phi(a) - g phi(b) gives NaN or an infinity there by the signs of its halves, and
+ * an infinity must not reach an optimizer that zeroes only NaN.  In eval mode dmu is gv - gv (mu enters y_in - mu twice): zero, or NaN
+ * where the element's gradient is.  Finite operands give the bits they gave before.
+ * clc_gauss_lik_fwd, clc_gauss_lik_bwd and clc_quantize_build_indexes refuse, by name in clc_last_error and before any launch, a mode
+ * other than 0 or 1 and a leading dimension below C of any operand they are given (noise counts in mode 0 only). */
 int clc_gauss_lik_fwd(const float* y, int ldy, const float* mu, int ldmu, const float* scale, int ldsc,
                       const float* noise, int ldn, float* lik, int ldl, float* y_hat, int ldh, long rows, int C,
                       int mode, float* bits_partial, int n_partials, clc_stream_t stream);

@@ -197,6 +197,30 @@ def test_sign_trick_at_zero(dev, training):
     _report("sign 0", fig, want)
 
 
+@pytest.mark.parametrize("training", [False, True], ids=["eval", "train"])
+def test_a_nan_latent_stays_nan(dev, training):
+    """one NaN in z on (257, 3), set A: the likelihood of that element is NaN (LowerBound's forward is torch.max, which keeps a NaN;
+    fmaxf returned the bound), and so are its dz in training and its channel's parameter gradients, exactly where the float32 oracle's
+    are; every other element and every other channel has the bits of a run without the NaN"""
+    ps, rows, C = "A", 257, 3
+    P, clean = R.params(ps, C), R.latents(ps, rows, C)
+    d = dict(clean, z=clean["z"].clone())
+    d["z"][100, 1] = float("nan")
+    oracle = R.oracle_result(P, d, training, R.F32)
+    assert bool(torch.isnan(oracle["lik"][100, 1])) and int(torch.isnan(oracle["lik"]).sum()) == 1
+    lik, zh = _fwd(dev, P, d, rows, C, False, training)
+    lik0, _ = _fwd(dev, P, clean, rows, C, False, training)
+    dz, grads = _bwd(dev, P, d, rows, C, False, training)
+    dz0, grads0 = _bwd(dev, P, clean, rows, C, False, training)
+    keep = torch.ones(rows, C, dtype=torch.bool)
+    keep[100, 1] = False
+    assert torch.equal(torch.isnan(lik), torch.isnan(oracle["lik"])) and torch.equal(_bits(lik[keep]), _bits(lik0[keep]))
+    assert torch.equal(torch.isnan(dz), torch.isnan(oracle["dz"])) and torch.equal(_bits(dz[keep]), _bits(dz0[keep]))
+    for name, g, g0, go in zip(R.GRAD_NAMES, grads, grads0, oracle["grads"]):
+        assert torch.equal(torch.isnan(g), torch.isnan(go)), name
+        assert bool(torch.isnan(g[1]).all()) and torch.equal(_bits(g[[0, 2]]), _bits(g0[[0, 2]])), name
+
+
 @pytest.mark.parametrize("ps", ["A", "B", "C"])
 @pytest.mark.parametrize("C", R.AUX_CS)
 def test_aux_loss_and_dquantiles(dev, C, ps):
