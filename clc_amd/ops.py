@@ -2738,28 +2738,37 @@ def _ar_dense(t, rows, what, dtype=torch.float32):
 AR_KINDS = {"dense": _lib.AR_SRC_DENSE, "pixel": _lib.AR_SRC_PIXEL, "taps": _lib.AR_SRC_TAPS}
 
 
+def _ar_ranges(who, srcs, pix, B, H, W, max_ranges, taps, taps_k=12):
+    """The (kind, tensor) K ranges of ar_linear / row_gemm -> (pix pointer, P, rows, ArSrc array, K).  who: the caller, for the messages;
+    taps: whether a "taps" range is taken, which then contributes taps_k C to K."""
+    pp, P = _ar_pix(pix)
+    rows = B * P
+    if not 1 <= len(srcs) <= max_ranges:
+        raise ValueError(f"{who}: {'one or two' if max_ranges == 2 else 'one to four'} K ranges (got {len(srcs)})")
+    arr, K = (_lib.ArSrc * max_ranges)(), 0
+    for i, (kind, t) in enumerate(srcs):
+        if kind == "taps" and not taps:
+            raise ValueError(f"{who}: a 'taps' range is not taken (the gather stays with ar_linear)")
+        if kind not in AR_KINDS:
+            raise ValueError(f"{who}: unknown source kind {kind!r} ({'dense, pixel or taps' if taps else 'dense or pixel'})")
+        if kind == "dense":
+            _require_gpu(t, who)
+            p, ld = _ar_dense(t, rows, f"{who} dense range")
+            Cc = int(t.shape[1])
+        else:
+            p, Bm, Hm, Wm, Cc, ld = _ar_map(t, who)
+            if (Bm, Hm, Wm) != (B, H, W):
+                raise ValueError(f"{who}: map {tuple(t.shape)} does not match B, H, W = {B}, {H}, {W}")
+        arr[i] = _lib.ArSrc(p, ld, Cc, AR_KINDS[kind])
+        K += taps_k * Cc if kind == "taps" else Cc
+    return pp, P, rows, arr, K
+
+
 def ar_linear(srcs, pix, B, H, W, w, bias, out, act=ACT_NONE):
     """clc_ar_linear: out[r, :N] = act(bias + sum_k in(r, k) w[n, k]) for the rows r = b * P + p of the pixel list.  srcs: one or two
     (kind, tensor) ranges of the K axis — ("dense", [rows, C] buffer), ("pixel", map) or ("taps", map: the 12 live taps of mask A,
     K = 12 C).  w [N, K] row-major.  Every element's summation order depends on the K of each range alone (see ar_context.hip)."""
-    pp, P = _ar_pix(pix)
-    rows = B * P
-    if not 1 <= len(srcs) <= 2:
-        raise ValueError(f"ar_linear: one or two K ranges (got {len(srcs)})")
-    arr, K = (_lib.ArSrc * 2)(), 0
-    for i, (kind, t) in enumerate(srcs):
-        if kind not in AR_KINDS:
-            raise ValueError(f"ar_linear: unknown source kind {kind!r} (dense, pixel or taps)")
-        if kind == "dense":
-            _require_gpu(t, "ar_linear")
-            p, ld = _ar_dense(t, rows, "ar_linear dense range")
-            Cc = int(t.shape[1])
-        else:
-            p, Bm, Hm, Wm, Cc, ld = _ar_map(t, "ar_linear")
-            if (Bm, Hm, Wm) != (B, H, W):
-                raise ValueError(f"ar_linear: map {tuple(t.shape)} does not match B, H, W = {B}, {H}, {W}")
-        arr[i] = _lib.ArSrc(p, ld, Cc, AR_KINDS[kind])
-        K += 12 * Cc if kind == "taps" else Cc
+    pp, P, rows, arr, K = _ar_ranges("ar_linear", srcs, pix, B, H, W, 2, True)
     _require_gpu(w, "ar_linear")
     if w.dim() != 2 or not w.is_contiguous() or w.shape[1] != K:
         raise ValueError(f"ar_linear: the filter must be a contiguous [N, K = {K}] matrix (got {tuple(w.shape)})")
@@ -2779,26 +2788,7 @@ def row_gemm(srcs, pix, B, H, W, w, bias, out, act=ACT_NONE):
     the rows r = b * P + p of the pixel list.  srcs: one to four (kind, tensor) ranges of the K axis, ("dense", [rows, C] buffer) or
     ("pixel", map; a channel slice of a map is read in place); "taps" stays with ar_linear.  act: ACT_NONE, ACT_LRELU or ACT_RELU.
     Every element's summation order depends on the C of each range alone — and is NOT ar_linear's: never mix the two in one stream."""
-    pp, P = _ar_pix(pix)
-    rows = B * P
-    if not 1 <= len(srcs) <= 4:
-        raise ValueError(f"row_gemm: one to four K ranges (got {len(srcs)})")
-    arr, K = (_lib.ArSrc * 4)(), 0
-    for i, (kind, t) in enumerate(srcs):
-        if kind == "taps":
-            raise ValueError("row_gemm: a 'taps' range is not taken (the gather stays with ar_linear)")
-        if kind not in AR_KINDS:
-            raise ValueError(f"row_gemm: unknown source kind {kind!r} (dense or pixel)")
-        if kind == "dense":
-            _require_gpu(t, "row_gemm")
-            p, ld = _ar_dense(t, rows, "row_gemm dense range")
-            Cc = int(t.shape[1])
-        else:
-            p, Bm, Hm, Wm, Cc, ld = _ar_map(t, "row_gemm")
-            if (Bm, Hm, Wm) != (B, H, W):
-                raise ValueError(f"row_gemm: map {tuple(t.shape)} does not match B, H, W = {B}, {H}, {W}")
-        arr[i] = _lib.ArSrc(p, ld, Cc, AR_KINDS[kind])
-        K += Cc
+    pp, P, rows, arr, K = _ar_ranges("row_gemm", srcs, pix, B, H, W, 4, False)
     _require_gpu(w, "row_gemm")
     if w.dim() != 2 or not w.is_contiguous() or w.shape[1] != K or w.dtype != torch.float32:
         raise ValueError(f"row_gemm: the filter must be a contiguous float32 [N, K = {K}] matrix (got {tuple(w.shape)})")
